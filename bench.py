@@ -6,7 +6,12 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line on rank 0.  metric = simulator env-steps/s of the whole job (all ranks), with the PPO update
-inside the timed region; PPO minibatch-steps/s and the rollout/update split are reported alongside.
+inside the timed region; PPO minibatch-steps/s is reported alongside.  A plain run does only that: set-up, warm-up, the
+timed steps, the line.  --full adds everything else the benchmark measures or checks: the rollout/update split, the
+kernel roofline and minibatch-step probes, the extra timed passes (other tracker mode, C2, fresh policy), the secondary
+probes, the CPU baseline, and with N > 1 the rank-identity check and the scaled-batch variant.
+--dump-outputs DIR writes what the last timed step computed (trajectory, update losses, parameters after the update) as
+DIR/<name>.npy (float32 / float64); the inputs are seeded, so two builds can be compared output for output.
 Workloads (BASELINE.json configs): c3 (default) KuaishouEnv big_matrix-shaped 7176 x 10728, 1024 envs per GPU,
 recent-N = 10 (C4 = the same with 8 ranks: 8192 envs, weak scaling); c2 = 1411 x 3327, 64 envs.
 """
@@ -471,6 +476,93 @@ def self_launch(n_gpus):
     return subprocess.run(cmd, env=env, cwd=ROOT).returncode
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, losses, n, directory):
+    """--dump-outputs: what the last timed step handed back or left in the engine -- the collect's episode lengths and trajectory,
+    the update's per-minibatch losses and row count, the policy / tracker parameters after the update -- as DIR/<name>.npy in
+    float32 (fp32 tensors) or float64 (fp64 tensors; integer ids and flags, which it holds exactly)."""
+    tr = eng.rollout.traj
+    arrays = {"lengths": eng.lengths, "update_losses": losses, "update_rows": torch.tensor([n], dtype=torch.float64),
+              "traj_obs": tr.obs, "traj_act": tr.act, "traj_rew": tr.rew, "traj_done": tr.done, "traj_logp": tr.logp,
+              "traj_value": tr.value, "traj_ctr": tr.ctr, "policy_params": eng.policy_flat, "tracker_params": eng.tracker_flat}
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float32 if v.dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), v)
+
+
+def full_measurements(args, wl, eng, device, world, G, out, ranks_identical, scaled, n_ro, t_ro, tb, tc, l2):
+    """--full, rank 0: everything the line carries beyond the headline, added to `out`."""
+    t_mb, mb, t_k = hip_event_kernel_time(eng, wl)
+    I = wl["I"]
+    S, H = 20, 64
+    # Dominant kernel of the timed step (profiles/*_kernel_stats.csv): head_bwd_fused_kernel, the fused actor-head backward
+    # of a PPO minibatch step.  ALGORITHMIC flop per launch: the two backward products of the head layer,
+    # dWa = dZ^T H2 and dH2 = dZ Wa: 2 x 2*mb*I*64 (SURVEY 8(d): "fwd + 2 x bwd" of 2*mb*64*I each).  EXECUTED: + one
+    # recompute of the logits tile (2*mb*I*64) instead of reading a B x I probability matrix from HBM.
+    t_bwd = t_k["head_bwd_fused_kernel"]
+    flop_bwd = 4.0 * mb * I * H
+    exec_bwd = 6.0 * mb * I * H
+    # whole minibatch step (4 launches), SURVEY 8(d): 3 x 2*mb*(S*64 + 64*64 + 64*I) = 4.25 GFLOP at mb = 1024, I = 10728
+    flop_step = 6.0 * mb * (S * H + H * H + H * I)
+    exec_step = 8.0 * mb * I * H + 6.0 * mb * (S * H + H * H)
+    out.update({
+        "rank_parameters_bit_identical": ranks_identical,
+        "rollout_only_env_steps_per_s": n_ro / t_ro, "rollout_only_ms_per_collect": 1e3 * t_ro,
+        "update_only_ms": 1e3 * (tc - tb), "update_minibatch_steps": int(l2.shape[0]),
+        "roofline": {"bound": "mfma", "kernel": "head_bwd_fused_kernel (PPO minibatch step: fused actor-head backward; fp32 products from two fp16 pieces per operand = 3 x v_mfma_f32_32x32x16_f16 per product, fp32 accumulate)",
+                     "achieved": flop_bwd / t_bwd / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                     "frac": flop_bwd / t_bwd / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                     "achieved_executed": exec_bwd / t_bwd / 1e12, "frac_executed": exec_bwd / t_bwd / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                     "algorithmic_flop_per_launch": flop_bwd, "traffic": None, "seconds_per_launch": t_bwd, "rows": mb,
+                     "timing": "HIP events recorded by the library around each launch of this kernel on its launch stream (cirs_prof_start/stop)",
+                     "kernel_note": "since round 3 the kernel's prologue also merges the head-statistics partials of its rows and forms their loss terms / backward coefficients (~2.5 us that replace a 6.5 us launch): its duration includes that work, the algorithmic flop count does not",
+                     "peak_note": "fp32 MFMA dense peak: the kernel's results are fp32-accurate (DESIGN.md section 4); its 3x expanded f16 flops are exec_f16_flop_per_launch",
+                     "exec_f16_flop_per_launch": 3.0 * exec_bwd},
+        "minibatch_step": {"seconds": t_mb, "launches": len(MINIBATCH_KERNELS), "algorithmic_flop": flop_step, "achieved": flop_step / t_mb / 1e12,
+                           "achieved_executed": exec_step / t_mb / 1e12, "frac": flop_step / t_mb / 1e12 / PEAK_FP32_MFMA_TFLOPS,
+                           "unit": "TFLOP/s", "traffic": None,
+                           "head_stats_kernel_seconds": t_k["head_stats_kernel"],
+                           "note": "one step of cirs_ppo_learn's loop: head_stats_kernel + head_bwd_fused_kernel (whose prologue also merges the statistics partials and forms the row loss terms) + trunk_rows_kernel (chunk-slab sums of d h2, trunk backward, dWa slab sums, trunk-gradient sums, squared-norm partials) + adam_next_kernel (Adam + the trunk forward / advantage statistics / Wa planes of the NEXT step)"},
+    })
+    # HBM traffic per launch from the committed PMC passes -- only when they were taken on exactly these kernel sources
+    traffic, src = pmc_traffic(args.workload)
+    out["roofline"]["traffic"] = (traffic or {}).get("head_bwd_fused_kernel")
+    out["roofline"]["traffic_source"] = src
+    out["minibatch_step"]["traffic"] = sum(traffic.get(k, 0) for k in MINIBATCH_KERNELS) if traffic and all(k in traffic for k in MINIBATCH_KERNELS) else None
+    if traffic:
+        out["hbm_traffic_per_launch"] = {k: v for k, v in traffic.items() if k.split("<")[0] in ("actor_head_kernel", "actor_mass_kernel", "tracker_step_kernel", "sweep_kernel", "gather_fm_kernel")}
+    if scaled is not None:
+        out["scaled_batch_variant"] = scaled
+    if world > 1:
+        out["collectives_per_rank"] = {"calls": dict(eng.coll.calls), "bytes": dict(eng.coll.bytes),
+                                       "note": "totals over warm-up, timed and extra steps of this process"}
+    if world == 1 and not args.no_probes:  # secondary probes and the host baseline belong to the single-GPU run (task contract: rank 0 at N=1 only)
+        # the same warm-up / step protocol on more workloads, so that the full run carries them (never `value`):
+        # the C3 step in the OTHER tracker mode (headline = Dropout(0.1) live, extra = eval-mode tracker, or the reverse) and C2
+        if args.workload == "c3" and not args.dropout_redraw:
+            out["dropout_off" if args.dropout > 0 else "dropout_on"] = timed_pass(WORKLOADS["c3"], device, 0.0 if args.dropout > 0 else 0.1, args.warmup, args.steps, G,
+                                                                                  pretrain=args.pretrain_steps)
+            if args.pretrain_steps > 0:      # the transient the driver's line used to time (rounds 1-5): same flags, policy fresh at the first warm-up step
+                out["fresh_policy"] = timed_pass(WORKLOADS["c3"], device, args.dropout, args.warmup, args.steps, G)
+        if args.workload != "c2":
+            # (C2 learns from 2 minibatch steps per update: after the driver's 5 + 20 steps its episodes are still 12 steps long and the number says
+            #  nothing about the shape; a step is 1.7 ms, so this pass always runs >= 150 warm-up and >= 100 timed steps -- its own `steps` / `warmup` are reported)
+            out["c2"] = timed_pass(WORKLOADS["c2"], device, args.dropout, max(args.warmup, 150), max(args.steps, 100), G)
+        out["gather_fm"] = gather_fm_probe(device)
+        out["deepfm_sweep"] = deepfm_sweep_probe(wl, device)
+        out["sweep_mode"] = sweep_mode_probe(wl, eng, device)
+        out["c5_split"] = c5_split_probe(device)
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(wl, eng)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -493,14 +585,19 @@ def main():
                     help="with --dropout > 0: the reference's own procedure (fresh masks over the whole prefix at every build_state call, "
                          "core/state_tracker.py:170-186,243-246; cirs_hip/redraw.py) instead of position-keyed masks.  Single GPU; O(T^2) row-passes by definition")
     ap.add_argument("--scaled-batch-steps", type=int, default=-1,
-                    help="N > 1: extra steps timed with the global minibatch scaled to --global-batch x N (constant optimiser steps per update; "
+                    help="N > 1 with --full: extra steps timed with the global minibatch scaled to --global-batch x N (constant optimiser steps per update; "
                          "reported under scaled_batch_variant, never as value).  -1 = min(steps, 5), 0 = skip")
     ap.add_argument("--pretrain-steps", type=int, default=40,
                     help="untimed collect + update steps BEFORE the counted warm-up, so that the timed steps run in the steady state (episodes at max_turn) whatever "
                          "--warmup is: a fresh policy plays short episodes for its first ~25 updates and the driver's 5 + 20 steps would time that transient "
                          "(reported as config.pretrain_steps; the fresh-policy number stays in config.also_measured.fresh_policy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probes", action="store_true", help="skip the secondary probes (gather_fm / sweep / cpu baseline): contract line only")
+    ap.add_argument("--no-probes", action="store_true", help="with --full: skip the secondary probes (gather_fm / sweep / cpu baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: rollout/update split, kernel probes and roofline, extra timed passes, secondary "
+                         "probes, CPU baseline; N > 1: rank-identity check and scaled-batch variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
     wl = WORKLOADS[args.workload]
 
@@ -569,8 +666,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
     total_steps = float(steps_local)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, losses, n, args.dump_outputs)
     ranks_identical = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank must hold bit-identical policy / tracker parameters after the timed updates (order-fixed reductions)
         h = torch.stack([eng.policy_flat.view(torch.int32).sum(dtype=torch.int64), eng.tracker_flat.view(torch.int32).sum(dtype=torch.int64),
                          (eng.policy_flat.view(torch.int32).to(torch.int64) * torch.arange(1, eng.policy_flat.numel() + 1, device=device) % 1000003).sum()])
@@ -581,7 +680,7 @@ def main():
     # N > 1, extra: the same job with the global minibatch scaled by the number of ranks (G x N rows: the number of optimiser steps per
     # update stays that of one GPU).  A DIFFERENT PPO configuration than BASELINE's -- reported beside the headline, never as `value`.
     scaled = None
-    k_scaled = (min(args.steps, 5) if args.scaled_batch_steps < 0 else args.scaled_batch_steps) if world > 1 else 0
+    k_scaled = (min(args.steps, 5) if args.scaled_batch_steps < 0 else args.scaled_batch_steps) if world > 1 and args.full else 0
     if k_scaled > 0:
         eng.collect(); eng.update(batch_size=G * world, repeat=2)
         barrier()
@@ -600,34 +699,22 @@ def main():
                   "minibatch_steps_per_update": mb_s / k_scaled,
                   "note": "PPO batch_size scaled by the number of ranks: NOT the reference's configuration, shown for the Amdahl comparison only"}
 
-    # split (untimed extra pass, same state): rollout-only and update-only rates
-    barrier()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    n_ro, reps_ro = 0, 3
-    ev[0].record()
-    for _ in range(reps_ro):        # rollout only: HIP events on the launch stream, no host sync / reduction inside the window
-        eng.collect()
-    ev[1].record()
-    torch.cuda.synchronize()
-    t_ro = ev[0].elapsed_time(ev[1]) * 1e-3 / reps_ro
-    n_ro = int(eng.lengths.sum())    # env-steps of the LAST of the collects (same policy: the others differ by sampling noise only)
-    tb = time.perf_counter()
-    l2, n2 = eng.update(G, 2); torch.cuda.synchronize(); tc = time.perf_counter()
+    if args.full:
+        # split (untimed extra pass, same state): rollout-only and update-only rates
+        barrier()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        n_ro, reps_ro = 0, 3
+        ev[0].record()
+        for _ in range(reps_ro):        # rollout only: HIP events on the launch stream, no host sync / reduction inside the window
+            eng.collect()
+        ev[1].record()
+        torch.cuda.synchronize()
+        t_ro = ev[0].elapsed_time(ev[1]) * 1e-3 / reps_ro
+        n_ro = int(eng.lengths.sum())    # env-steps of the LAST of the collects (same policy: the others differ by sampling noise only)
+        tb = time.perf_counter()
+        l2, n2 = eng.update(G, 2); torch.cuda.synchronize(); tc = time.perf_counter()
 
     if rank == 0:
-        t_mb, mb, t_k = hip_event_kernel_time(eng, wl)
-        I = wl["I"]
-        S, H = 20, 64
-        # Dominant kernel of the timed step (profiles/*_kernel_stats.csv): head_bwd_fused_kernel, the fused actor-head backward
-        # of a PPO minibatch step.  ALGORITHMIC flop per launch: the two backward products of the head layer,
-        # dWa = dZ^T H2 and dH2 = dZ Wa: 2 x 2*mb*I*64 ("fwd + 2 x bwd" of 2*mb*64*I each).  EXECUTED: + one
-        # recompute of the logits tile (2*mb*I*64) instead of reading a B x I probability matrix from HBM.
-        t_bwd = t_k["head_bwd_fused_kernel"]
-        flop_bwd = 4.0 * mb * I * H
-        exec_bwd = 6.0 * mb * I * H
-        # whole minibatch step (4 launches), SURVEY 8(d): 3 x 2*mb*(S*64 + 64*64 + 64*I) = 4.25 GFLOP at mb = 1024, I = 10728
-        flop_step = 6.0 * mb * (S * H + H * H + H * I)
-        exec_step = 8.0 * mb * I * H + 6.0 * mb * (S * H + H * H)
         out = {
             "metric": "simulator env-steps/s (collect + PPO update in the timed region), KuaishouEnv",
             "value": total_steps / elapsed, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -652,62 +739,19 @@ def main():
                                                 "all-gather of 16 B/row + all-reduce of the d h2 partials per minibatch, head shards all-gathered per update"}[args.learner])
                        if world > 1 else "single GPU"},
             "dropout": args.dropout, "dropout_redraw": bool(args.dropout_redraw and args.dropout > 0),
-            "ppo_minibatch_steps_per_s": mb_steps / elapsed, "rank_parameters_bit_identical": ranks_identical,
-            "rollout_only_env_steps_per_s": n_ro / t_ro, "rollout_only_ms_per_collect": 1e3 * t_ro,
-            "update_only_ms": 1e3 * (tc - tb), "update_minibatch_steps": int(l2.shape[0]),
-            "roofline": {"bound": "mfma", "kernel": "head_bwd_fused_kernel (PPO minibatch step: fused actor-head backward; fp32 products from two fp16 pieces per operand = 3 x v_mfma_f32_32x32x16_f16 per product, fp32 accumulate)",
-                         "achieved": flop_bwd / t_bwd / 1e12, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": flop_bwd / t_bwd / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                         "achieved_executed": exec_bwd / t_bwd / 1e12, "frac_executed": exec_bwd / t_bwd / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                         "algorithmic_flop_per_launch": flop_bwd, "traffic": None, "seconds_per_launch": t_bwd, "rows": mb,
-                         "timing": "HIP events recorded by the library around each launch of this kernel on its launch stream (cirs_prof_start/stop)",
-                         "kernel_note": "since round 3 the kernel's prologue also merges the head-statistics partials of its rows and forms their loss terms / backward coefficients (~2.5 us that replace a 6.5 us launch): its duration includes that work, the algorithmic flop count does not",
-                         "peak_note": "fp32 MFMA dense peak: the kernel's results are fp32-accurate (DESIGN.md section 4); its 3x expanded f16 flops are exec_f16_flop_per_launch",
-                         "exec_f16_flop_per_launch": 3.0 * exec_bwd},
-            "minibatch_step": {"seconds": t_mb, "launches": len(MINIBATCH_KERNELS), "algorithmic_flop": flop_step, "achieved": flop_step / t_mb / 1e12,
-                               "achieved_executed": exec_step / t_mb / 1e12, "frac": flop_step / t_mb / 1e12 / PEAK_FP32_MFMA_TFLOPS,
-                               "unit": "TFLOP/s", "traffic": None,
-                               "head_stats_kernel_seconds": t_k["head_stats_kernel"],
-                               "note": "one step of cirs_ppo_learn's loop: head_stats_kernel + head_bwd_fused_kernel (whose prologue also merges the statistics partials and forms the row loss terms) + trunk_rows_kernel (chunk-slab sums of d h2, trunk backward, dWa slab sums, trunk-gradient sums, squared-norm partials) + adam_next_kernel (Adam + the trunk forward / advantage statistics / Wa planes of the NEXT step)"},
+            "ppo_minibatch_steps_per_s": mb_steps / elapsed,
         }
-        # HBM traffic per launch from the committed PMC passes -- only when they were taken on exactly these kernel sources
-        traffic, src = pmc_traffic(args.workload)
-        out["roofline"]["traffic"] = (traffic or {}).get("head_bwd_fused_kernel")
-        out["roofline"]["traffic_source"] = src
-        out["minibatch_step"]["traffic"] = sum(traffic.get(k, 0) for k in MINIBATCH_KERNELS) if traffic and all(k in traffic for k in MINIBATCH_KERNELS) else None
-        if traffic:
-            out["hbm_traffic_per_launch"] = {k: v for k, v in traffic.items() if k.split("<")[0] in ("actor_head_kernel", "actor_mass_kernel", "tracker_step_kernel", "sweep_kernel", "gather_fm_kernel")}
-        if scaled is not None:
-            out["scaled_batch_variant"] = scaled
-        if world > 1:
-            out["collectives_per_rank"] = {"calls": dict(eng.coll.calls), "bytes": dict(eng.coll.bytes),
-                                           "note": "totals over warm-up, timed and extra steps of this process"}
-        if world == 1 and not args.no_probes:  # secondary probes and the host baseline belong to the single-GPU run (task contract: rank 0 at N=1 only)
-            # the same warm-up / step protocol on more workloads, so that the driver's one default run carries them (never `value`):
-            # the C3 step in the OTHER tracker mode (headline = Dropout(0.1) live, extra = eval-mode tracker, or the reverse) and C2
-            if args.workload == "c3" and not args.dropout_redraw:
-                out["dropout_off" if args.dropout > 0 else "dropout_on"] = timed_pass(WORKLOADS["c3"], device, 0.0 if args.dropout > 0 else 0.1, args.warmup, args.steps, G,
-                                                                                      pretrain=args.pretrain_steps)
-                if args.pretrain_steps > 0:      # the transient the driver's line used to time (rounds 1-5): same flags, policy fresh at the first warm-up step
-                    out["fresh_policy"] = timed_pass(WORKLOADS["c3"], device, args.dropout, args.warmup, args.steps, G)
-            if args.workload != "c2":
-                # (C2 learns from 2 minibatch steps per update: after the driver's 5 + 20 steps its episodes are still 12 steps long and the number says
-                #  nothing about the shape; a step is 1.7 ms, so this pass always runs >= 150 warm-up and >= 100 timed steps -- its own `steps` / `warmup` are reported)
-                out["c2"] = timed_pass(WORKLOADS["c2"], device, args.dropout, max(args.warmup, 150), max(args.steps, 100), G)
-            out["gather_fm"] = gather_fm_probe(device)
-            out["deepfm_sweep"] = deepfm_sweep_probe(wl, device)
-            out["sweep_mode"] = sweep_mode_probe(wl, eng, device)
-            out["c5_split"] = c5_split_probe(device)
-            if not args.no_cpu_baseline:
-                out["cpu_baseline"] = cpu_baseline(wl, eng)
+        also = {"ppo_minibatch_steps_per_s": out["ppo_minibatch_steps_per_s"]}
+        if args.full:
+            full_measurements(args, wl, eng, device, world, G, out, ranks_identical, scaled, n_ro, t_ro, tb, tc, l2)
+            also = {"rollout_only_env_steps_per_s": out["rollout_only_env_steps_per_s"], "rollout_only_ms_per_collect": out["rollout_only_ms_per_collect"],
+                    "update_only_ms": out["update_only_ms"], "minibatch_step_us": 1e6 * out["minibatch_step"]["seconds"],
+                    "minibatch_step_launches": out["minibatch_step"]["launches"], "ppo_minibatch_steps_per_s": out["ppo_minibatch_steps_per_s"]}
+            brief = lambda e: {k: e[k] for k in ("value", "ms_per_step", "mean_episode_len", "tracker_dropout", "envs", "minibatch_steps_per_update", "steps", "warmup")}  # noqa: E731
+            for key in ("dropout_off", "dropout_on", "c2", "fresh_policy"):
+                if key in out:
+                    also[key] = brief(out[key])
         # what else this run measured, in `config` (the driver's record keeps config / roofline / cpu_baseline whole and everything else by name only)
-        brief = lambda e: {k: e[k] for k in ("value", "ms_per_step", "mean_episode_len", "tracker_dropout", "envs", "minibatch_steps_per_update", "steps", "warmup")}  # noqa: E731
-        also = {"rollout_only_env_steps_per_s": out["rollout_only_env_steps_per_s"], "rollout_only_ms_per_collect": out["rollout_only_ms_per_collect"],
-                "update_only_ms": out["update_only_ms"], "minibatch_step_us": 1e6 * t_mb, "minibatch_step_launches": out["minibatch_step"]["launches"],
-                "ppo_minibatch_steps_per_s": out["ppo_minibatch_steps_per_s"]}
-        for key in ("dropout_off", "dropout_on", "c2", "fresh_policy"):
-            if key in out:
-                also[key] = brief(out[key])
         out["config"]["also_measured"] = also
         # print order: the bulky probe objects first, the numbers a reader wants last (a log tail keeps the end of the line)
         tail_keys = ("roofline", "minibatch_step", "dropout_off", "dropout_on", "fresh_policy", "c2", "rollout_only_env_steps_per_s", "rollout_only_ms_per_collect",

@@ -21,7 +21,7 @@ def run_bench(*flags):
 
 
 def test_bench_json_line():
-    d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c2")
+    d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c2", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
                 "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -59,7 +59,7 @@ def test_bench_default_workload_carries_dropout_and_c2_passes():
     """the default (C3) single-GPU line runs the tracker in training mode and also carries a timed pass with the
     eval-mode tracker (the headline's warm-up / step protocol) and a timed pass of BASELINE configs[1] (C2, at its steady state) -- and their numbers sit in
     `config.also_measured`, which the driver's record keeps whole."""
-    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    d = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert "7176x10728" in d["config"]["workload"] and d["dropout"] == 0.1
     for key, envs, p in (("dropout_off", 1024, 0.0), ("c2", 64, 0.1)):
         e = d[key]
@@ -81,7 +81,7 @@ def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     env = dict(os.environ, CIRS_BENCH_SHARE_GPU="1", CIRS_DIST_CHECK="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -99,3 +99,28 @@ def test_bench_gpus_n_without_enough_gpus_fails_loudly():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode != 0 and "GPU(s)" in out.stderr
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run carries the headline keys and none of --full's extra measurements; --dump-outputs writes what the last timed step
+    computed as float32 / float64 .npy files (<= 64 MB in all), and the same arguments give the same outputs run after run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "c2", "--dump-outputs", str(tmp_path / f"run{k}"))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in d, key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "env-steps/s"
+        for key in ("roofline", "minibatch_step", "cpu_baseline", "c2", "dropout_off", "fresh_policy", "gather_fm", "rollout_only_env_steps_per_s"):
+            assert key not in d, key
+        files = sorted(os.listdir(tmp_path / f"run{k}"))
+        arrays = {f[:-4]: np.load(tmp_path / f"run{k}" / f) for f in files}
+        assert files and all(f.endswith(".npy") for f in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["lengths"].shape == (64,) and arrays["traj_act"].shape == (30, 64)
+        assert arrays["update_rows"][0] == arrays["lengths"].sum() and arrays["update_losses"].shape[0] >= 2
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for name in dumps[0]:
+        assert np.array_equal(dumps[0][name], dumps[1][name]), name

@@ -153,7 +153,7 @@ def test_two_process_rccl_bench_ranks_stay_bit_identical(nproc, learner):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--learner", learner, "--scaled-batch-steps", "1"]
+           "--full", "--learner", learner, "--scaled-batch-steps", "1"]
     env["CIRS_DIST_CHECK"] = "1"     # per-collective stream-order assertions (cirs_hip.distributed.Collectives)
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -178,7 +178,7 @@ def test_two_process_bench_on_one_gpu_ranks_stay_bit_identical(learner):
     port = 29500 + os.getpid() % 150
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CIRS_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-probes",
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-probes",
            "--learner", learner, "--scaled-batch-steps", "1"]
     env["CIRS_DIST_CHECK"] = "1"
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)

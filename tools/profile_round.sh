@@ -8,14 +8,14 @@ out=$root/gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 cd $root
 # (the default line is the reference's training mode: tracker Dropout 0.1, position-keyed masks; --dropout 0 = eval-mode tracker)
-python bench.py > $out/${tag}_bench_c3.json 2> $out/bench_c3.err
-python bench.py --workload c2 --no-cpu-baseline --no-probes > $out/${tag}_bench_c2.json 2>> $out/bench_c3.err
-python bench.py --dropout 0 --no-cpu-baseline --no-probes > $out/${tag}_bench_c3_dropout_off.json 2>> $out/bench_c3.err
-python bench.py --dropout 0.1 --dropout-redraw --steps 20 --warmup 5 --no-cpu-baseline --no-probes > $out/${tag}_bench_c3_dropout_redraw.json 2>> $out/bench_c3.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_c3_driver_flags.json 2>> $out/bench_c3.err
+python bench.py --full > $out/${tag}_bench_c3.json 2> $out/bench_c3.err
+python bench.py --full --workload c2 --no-cpu-baseline --no-probes > $out/${tag}_bench_c2.json 2>> $out/bench_c3.err
+python bench.py --full --dropout 0 --no-cpu-baseline --no-probes > $out/${tag}_bench_c3_dropout_off.json 2>> $out/bench_c3.err
+python bench.py --full --dropout 0.1 --dropout-redraw --steps 20 --warmup 5 --no-cpu-baseline --no-probes > $out/${tag}_bench_c3_dropout_redraw.json 2>> $out/bench_c3.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/${tag}_bench_c3_driver_flags.json 2>> $out/bench_c3.err
 cd /tmp
 for mode in train eval; do
-  flags="--no-probes --no-cpu-baseline --steps 50 --warmup 15"; [ $mode = eval ] && flags="$flags --dropout 0"
+  flags="--full --no-probes --no-cpu-baseline --steps 50 --warmup 15"; [ $mode = eval ] && flags="$flags --dropout 0"
   rm -rf /tmp/prof_$mode
   timeout 900 rocprofv3 --kernel-trace -d /tmp/prof_$mode -o p -- python $root/bench.py $flags > $out/${tag}_bench_c3_prof_$mode.json 2> $out/prof_$mode.err
   db=$(find /tmp/prof_$mode -name "*.db" | head -1)
@@ -25,12 +25,12 @@ for mode in train eval; do
 done
 # C2 (steady state) and the exact-redraw mode: kernel stats + timeline of the same commands as their bench lines
 rm -rf /tmp/prof_c2
-timeout 900 rocprofv3 --kernel-trace -d /tmp/prof_c2 -o p -- python $root/bench.py --workload c2 --no-probes --no-cpu-baseline > $out/${tag}_bench_c2_prof.json 2> $out/prof_c2.err
+timeout 900 rocprofv3 --kernel-trace -d /tmp/prof_c2 -o p -- python $root/bench.py --full --workload c2 --no-probes --no-cpu-baseline > $out/${tag}_bench_c2_prof.json 2> $out/prof_c2.err
 db=$(find /tmp/prof_c2 -name "*.db" | head -1)
 python $root/tools/kstats.py $db $out/${tag}_bench_c2_kernel_stats.csv 40 > $out/kstats_c2.txt
 python $root/tools/step_timeline.py $db $out/${tag}_c2_step_timeline.md > /dev/null
 rm -rf /tmp/prof_rd
-timeout 900 rocprofv3 --kernel-trace -d /tmp/prof_rd -o p -- python $root/bench.py --dropout 0.1 --dropout-redraw --steps 20 --warmup 5 --no-probes --no-cpu-baseline > $out/${tag}_bench_c3_dropout_redraw_prof.json 2> $out/prof_rd.err
+timeout 900 rocprofv3 --kernel-trace -d /tmp/prof_rd -o p -- python $root/bench.py --full --dropout 0.1 --dropout-redraw --steps 20 --warmup 5 --no-probes --no-cpu-baseline > $out/${tag}_bench_c3_dropout_redraw_prof.json 2> $out/prof_rd.err
 db=$(find /tmp/prof_rd -name "*.db" | head -1)
 python $root/tools/kstats.py $db $out/${tag}_bench_c3_dropout_redraw_kernel_stats.csv 40 > $out/kstats_rd.txt
 rm -rf /tmp/prof_k12
