@@ -108,6 +108,24 @@ class Redraw(C.Structure):      # cirs_redraw
                 ("env_base0", C.c_int64), ("env_stride", C.c_int64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class VtbCfg(C.Structure):       # cirs_vtb_cfg
+    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "num_leave_compute", "simulated", "version", "use_exposure", "mmoe_d_in",
+                                         "mmoe_dnn_layers", "mmoe_h1", "mmoe_h2", "mmoe_experts", "mmoe_expert_dim", "mmoe_tasks",
+                                         "mmoe_task_dim")] + [(k, C.c_double) for k in ("leave_threshold", "tau", "gamma_exposure")]
+
+
+VTB_WEIGHT_FIELDS = ("gen_w1", "gen_b1", "gen_w2", "gen_b2", "act_w1", "act_b1", "act_w2", "act_b2", "act_w3", "act_b3",
+                     "mm_w1", "mm_b1", "mm_w2", "mm_b2", "mm_we", "mm_be", "mm_wg", "mm_wt", "mm_wlin", "mm_bias")
+
+
+class VtbWeights(C.Structure):   # cirs_vtb_weights
+    _fields_ = [(k, C.c_void_p) for k in VTB_WEIGHT_FIELDS]
+
+
+class VtbState(C.Structure):     # cirs_vtb_state
+    _fields_ = [(k, C.c_void_p) for k in ("task_user", "sim_user", "turn", "event", "prev_reward", "cum_reward", "lst_action", "hist")]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -117,6 +135,11 @@ SIGNATURES = {
     "cirs_env_step": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), _P, _P, C.c_int32,
                                 _P, _P, _P, _P, _P, _P]),
     "cirs_dist_jaccard": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "cirs_vtb_reset": (C.c_int, [C.POINTER(VtbCfg), C.POINTER(VtbWeights), C.POINTER(VtbState), C.c_uint64, _P, C.c_int32, _P, _P]),
+    "cirs_vtb_step": (C.c_int, [C.POINTER(VtbCfg), C.POINTER(VtbWeights), C.POINTER(VtbState), C.c_uint64, _P, _P, C.c_int32,
+                                _P, _P, _P, _P, _P, _P]),
+    "cirs_vtb_noise": (C.c_int, [C.c_uint64, _P, _P, C.c_int32, _P, _P]),
+    "cirs_vtb_mmoe_forward": (C.c_int, [C.POINTER(VtbCfg), C.POINTER(VtbWeights), _P, C.c_int32, _P, _P]),
     "cirs_tracker_init": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,
                                     C.c_int32, _P, C.c_int64, _P]),
     "cirs_tracker_step": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,

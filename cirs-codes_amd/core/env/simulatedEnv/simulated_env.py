@@ -2,7 +2,8 @@
 + user-model reward discounted by the exposure effect.
 
 KuaishouEnv-v0: a spec object; the arithmetic is csrc/env.hip (one launch per vector step).
-VirtualTB-v0  : BASELINE configs[0], CPU plumbing like in the reference: a host env with the reference's reset / step protocol --
+VirtualTB-v0  : BASELINE configs[0], CPU plumbing like in the reference (build_device_env: the batched device env of
+                cirs_hip/virtualtb.py, opt-in through DummyVectorEnv(..., device="cuda")): a host env with the reference's reset / step protocol --
                 the wrapped VirtualTB decides `done`, the exposure effect uses L2 distances between the 27-d actions
                 (core/util.py:21-30), the reward is user_model.forward on [user (88) | reward, 0, turn | action (27)] clamped to
                 [0, 10] (simulated_env.py:78-86) and discounted by the exposure effect (v1: r / (1 + e), v2: r - e)."""
@@ -99,7 +100,14 @@ class SimulatedEnv(gym.Env):
             raise AttributeError(key)
         return getattr(self.env_task, key)
 
-    def build_device_env(self, n_env, device="cuda"):
+    def build_device_env(self, n_env, device="cuda", seed=0):
+        if self.env_name == "VirtualTB-v0":      # cirs_hip.virtualtb.DeviceVirtualTB, simulated kind
+            if self.env_task.static:
+                raise ValueError("the static state mode (set_state_mode(True)) has no device env")
+            from cirs_hip.virtualtb import DeviceVirtualTB
+            return DeviceVirtualTB(self.env_task, n_env, user_model=self.user_model, version=self.version, tau=self.tau,
+                                   gamma_exposure=self.gamma_exposure, use_exposure_intervention=self.use_exposure_intervention,
+                                   seed=seed, device=device)
         from cirs_hip.env import DeviceEnv
         t = self.env_task
         tables = t.device_tables(normed_mat=self.normed_mat, alpha_u=self.alpha_u, beta_i=self.beta_i, device=device)

@@ -145,6 +145,13 @@ class VirtualTB(gym.Env):
             self.lst_action = torch.FloatTensor([0, 0])
         return self.state, reward, done, {"CTR": self.cum_reward / self.total_turn / 10}
 
+    def build_device_env(self, n_env, device="cuda", seed=0):
+        """n_env copies of this env on the device (cirs_hip.virtualtb.DeviceVirtualTB, raw kind: reward = clicks)."""
+        if self.static:
+            raise ValueError("the static state mode (set_state_mode(True)) has no device env")
+        from cirs_hip.virtualtb import DeviceVirtualTB
+        return DeviceVirtualTB(self, n_env, seed=seed, device=device)
+
     def render(self, mode="human", close=False):
         a, b = np.clip(self.rend_action, a_min=0, a_max=None)
         print("Current State:\n\t", self.state, "\nUser's action:\n\tclick:%2d, leave:%s, index:%2d" %

@@ -704,6 +704,79 @@ int cirs_prof_stop(double* total_seconds, int32_t* n_samples);
 int cirs_eval_coverage(const int64_t* act, int64_t n, int32_t n_items, const uint8_t* item_flag, uint32_t* bitmap,
                        int64_t* out3, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Environment: batched VirtualTaobao (VirtualTB-v0 and SimulatedEnv(VirtualTB-v0)), csrc/virtualtb.hip
+ * replaces  environments/VirtualTaobao/virtualTB/envs/virtualTB.py:11-146 (VirtualTB.reset/step, the user generator,
+ *           the action model) and the VirtualTB branch of core/env/simulatedEnv/simulated_env.py:44-193 (exposure effect,
+ *           UserModel_MMOE reward), one env at a time in the reference.  One launch per vector step.
+ * Noise: Philox4x32-10, key = seed, counter = (env id, per-env event index, block, tag); tag 0 = the 21 Gumbels of a step
+ * (clicks: words 0..10, second draw: words 11..20), tag 1 = a user draw (words 0..127 -> z = u01, words 128..215 -> the 88
+ * Gumbels of the 11 groups).  Every reset and every step of an env is one event; a redraw inside a step uses that step's
+ * event with tag 1.  Weights are fp32, stored TRANSPOSED ([in][out], row-major) unless noted.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_VTB_USER_DIM 88
+#define CIRS_VTB_ACTION_DIM 27
+#define CIRS_VTB_GROUPS 11
+#define CIRS_VTB_NOISE_COLS 237 /* 21 step Gumbels | 128 z | 88 user Gumbels */
+
+typedef struct cirs_vtb_cfg {
+    int32_t n_env;             /* envs held by the state arrays; env ids must lie in [0, n_env)               */
+    int32_t max_turn;          /* VirtualTB.max_turn; history rows per env                                    */
+    int32_t num_leave_compute; /* N: the exit rule looks at the last min(t, N-1) actions          */
+    int32_t simulated;         /* 1: SimulatedEnv(VirtualTB-v0), MMoE reward; 0: raw VirtualTB-v0, reward = clicks */
+    int32_t version;           /* simulated: 1 = r/(1+e), 2 = r - e                                           */
+    int32_t use_exposure;      /* SimulatedEnv.use_exposure_intervention                                      */
+    /* MMoE shape (simulated kind): only UserModel_MMOE's all-dense one-task regression build is supported:
+     * d_in 118, dnn (128, 128), 4 experts of dim 8, 1 task of logit dim 1 */
+    int32_t mmoe_d_in, mmoe_dnn_layers, mmoe_h1, mmoe_h2, mmoe_experts, mmoe_expert_dim, mmoe_tasks, mmoe_task_dim;
+    double leave_threshold;    /* L2 distance                                                                  */
+    double tau;                /* exposure: tau <= 0 -> 0                                                      */
+    double gamma_exposure;
+} cirs_vtb_cfg;
+
+typedef struct cirs_vtb_weights {
+    const float *gen_w1, *gen_b1, *gen_w2, *gen_b2;                  /* generator 128 -> 128 -> 88          */
+    const float *act_w1, *act_b1, *act_w2, *act_b2, *act_w3, *act_b3; /* action model 116 -> 128 -> 256 -> 21 */
+    const float *mm_w1, *mm_b1, *mm_w2, *mm_b2;                      /* MMoE dnn 118 -> 128 -> 128 (ReLU)   */
+    const float *mm_we, *mm_be;                                       /* experts 128 -> 32 (column d*4 + e)  */
+    const float *mm_wg;                                               /* gate 128 -> 4, no bias              */
+    const float *mm_wt;                                               /* tower [8] (8 -> 1, no bias)         */
+    const float *mm_wlin;                                             /* linear_model_task [118]             */
+    const float *mm_bias;                                             /* [1]                                 */
+} cirs_vtb_weights;
+
+typedef struct cirs_vtb_state { /* mutable, SoA over n_env envs */
+    int32_t* task_user;   /* [n_env,11] one-hot positions (0..87) of the wrapped VirtualTB's cur_user        */
+    int32_t* sim_user;    /* [n_env,11] SimulatedEnv.cur_user (set by reset only)                            */
+    int32_t* turn;        /* [n_env]    total_turn                                                          */
+    uint32_t* event;      /* [n_env]    noise event counter                                                  */
+    double* prev_reward;  /* [n_env]    SimulatedEnv.reward (input of the next MMoE call)                    */
+    double* cum_reward;   /* [n_env]                                                                         */
+    int32_t* lst_action;  /* [n_env,2]  (clicks, second draw); (0, 0) after a done step                      */
+    float* hist;          /* [n_env,max_turn,27] the actions of turns 0..max_turn-1                          */
+} cirs_vtb_state;
+
+/* draw a user for envs env_ids[0..n) (NULL = 0..n-1) and zero their turn / rewards / history; obs_out [n,91] double
+ * (nullable) = [user one-hot 88 | 0, 0 | 0]. */
+int cirs_vtb_reset(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, cirs_vtb_state* st, uint64_t seed,
+                   const int32_t* env_ids, int32_t n, double* obs_out, void* stream);
+/* one vector step of envs env_ids[0..n) (distinct ids) with actions[n,27] fp32.  Outputs (position j):
+ *   obs_out [n,30] double  simulated: [action | reward, 0, t+1]; raw: [action | a, b, t+1], [action | 0, 0, t+1] when done
+ *   rew_out [n]    double  simulated: MMoE reward after the exposure effect; raw: clicks a
+ *   done_out[n]    uint8   exit rule OR t >= max_turn - 1
+ *   ctr_out [n]    double  cum_reward / (t+1) / 10
+ *   expo_out[n]    double  (nullable) exposure effect of the step (simulated kind; 0 otherwise)
+ * The simulated kind supports t <= max_turn (the caller rejects later steps); the raw kind any t. */
+int cirs_vtb_step(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, cirs_vtb_state* st, uint64_t seed,
+                  const float* actions, const int32_t* env_ids, int32_t n, double* obs_out, double* rew_out,
+                  uint8_t* done_out, double* ctr_out, double* expo_out, void* stream);
+/* the noise the kernels draw for (env_ids[j], events[j]): out [n,237] fp32 = [21 step Gumbels | z (128) | 88 user Gumbels],
+ * bit for bit. */
+int cirs_vtb_noise(uint64_t seed, const int32_t* env_ids, const uint32_t* events, int32_t n, float* out, void* stream);
+/* UserModel_MMOE.forward on x[n,118] -> y_out[n] (unclamped), the user-model part of cirs_vtb_step. */
+int cirs_vtb_mmoe_forward(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, const float* x, int32_t n, float* y_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
