@@ -144,7 +144,7 @@ static int validate_policy(const cirs_policy_cfg* cfg, const cirs_policy_weights
 extern "C" int64_t cirs_policy_workspace_bytes(const cirs_policy_cfg* cfg, int32_t n) {
     using namespace cirs;
     if (!cfg || n <= 0) return 0;
-    // + slack: the fused rollout may carve one (256-byte aligned) workspace per env group out of this buffer
+    // + slack for the 256-byte alignment of the fused rollout's carve-outs
     // + the packed weight image of the fused rollout's step kernel (internal.h: TrkImg) at its end
     // + the logit store of the fused rollout's sampler while it is small (policy_kernels.h: ws_zstore_floats)
     // + the bf16 planes of the actor head for the chunk-mass kernels (policy_kernels.h: ws_rplanes_bytes), in front of the image

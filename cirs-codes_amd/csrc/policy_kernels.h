@@ -913,12 +913,6 @@ __device__ __forceinline__ Cand actor_pick_wave(const PickArgs& a, int j, int e,
         const int c = lane + CIRS_WAVE * q;
         G[q] = c < a.n_chunks ? chunk_gumbel(a.seed, a.rng_step, (uint32_t)e, (uint32_t)(chunk_base + c)) : 0.f;
     }
-#ifdef CIRS_PICK_EXTRA_GUMBELS   // probe: what two more Gumbels cost at this point
-    float Gx = 0.f;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) Gx += chunk_gumbel(a.seed, a.rng_step, (uint32_t)e, (uint32_t)(chunk_base + 1000 + lane + CIRS_WAVE * q));
-    if (Gx == 12345.678f) G[0] = Gx;
-#endif
     CIRS_PICK_STAMP(26);
     Best c0{-INFINITY, 0.f, 0x7FFFFFFF};     // bi = chunk id here
     Mass ms{-INFINITY, 0.f};

@@ -862,20 +862,13 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
 // the next tile's global loads in flight; row strides 144 B / 80 B keep the ds_read_b128 of the operands conflict-free.
 
 
-// schedule knobs of head_bwd_fused_kernel (A/B-measured on one box with tools/ab_headbwd.py; defaults = the measured best)
-#ifndef CIRS_BWD_COMMIT_EARLY
-#define CIRS_BWD_COMMIT_EARLY 1   // 1: next tile's planes -> LDS before the dH2 product; 0: at the end of the iteration
-#endif
-#ifndef CIRS_BWD_REDUCE_POS
-#define CIRS_BWD_REDUCE_POS 0     // where the previous tile's dWa sum runs: 0 around the second logits MFMA group, 1 around the dH2 product
-#endif
 // kEnt: the entropy term of dZ is compiled in (ent_coef != 0); the reference's scripts train with ent_coef = 0 (CIRS-RL-kuaishou.py:97),
 // where dZ = c_logp (delta - p) and the entropy is only reported.
 // kMerge: the merge of the head-statistics partials and the row's loss terms / backward coefficients run in THIS kernel's prologue (every
 // workgroup for its own rows, the workgroups of chunk 0 store what later kernels read) instead of a launch of their own between the two head
 // kernels: a 6.5 us launch on the critical path of every minibatch step becomes ~1.5 us of prologue.  The item-sharded learner keeps the
 // merge kernel (its statistics cross the ranks first).
-struct HeadMergeArgs { cirs_ppo_cfg cfg; cirs_ppo_batch b; const int32_t* idx; int mb_norm, n_schunks; ActorPartialView pv; int t_all; /* A/B switch: every workgroup loads the E_p[z] partials */ };
+struct HeadMergeArgs { cirs_ppo_cfg cfg; cirs_ppo_batch b; const int32_t* idx; int mb_norm, n_schunks; ActorPartialView pv; };
 template <bool kEnt, bool kMerge>
 __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I, int mb, int n_pad, int tiles_per_chunk,
                                                                          const uint4* __restrict__ planes,
@@ -983,7 +976,7 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
         float M = -INFINITY, ssum = 0.f, tsum = 0.f;
         // E_p[z]'s partials only where somebody uses them: every workgroup when the entropy term is in dZ, else the chunk-0 workgroups (they store the reported
         // entropy) -- a third of the prologue's 86 KB per workgroup for the other 30 of 31 (a prologue costs what its bytes cost: ~11 B/cycle per CU)
-        const bool need_t = kEnt || blockIdx.x == 0 || ma.t_all;
+        const bool need_t = kEnt || blockIdx.x == 0;
         for (int cb = 0; cb < nsc; cb += 64) {          // (wave-uniform trip count: the two halves meet in a shuffle inside)
             const int c0 = cb + hi;
             float m32[32], s32[32], u32[32];
@@ -1118,11 +1111,11 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             // (acc: bias + the h*h terms, acc1 / acc2: the cross terms -- same split as head_stats_kernel, so that p = exp(z - lse) sums to one)
             hmfma_split2(za[0], hz[0], za[1], hz[1], acc, acc1, acc2);
             RedRegs rg;
-            if (CIRS_BWD_REDUCE_POS == 0 && it > 0) reduce_load(buf ^ 1, rg);
+            if (it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the second logits MFMA group
             hmfma_split2(za[2], hz[2], za[3], hz[3], acc, acc1, acc2);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc1[r] += acc2[r];
-            if (CIRS_BWD_REDUCE_POS == 0 && it > 0) reduce_store(rg, tile0 - kTileN);
+            if (it > 0) reduce_store(rg, tile0 - kTileN);
             // the B planes of the dH2 product are requested only now: the A planes of the logits are dead (the two sets never coexist:
             // the kernel runs at the 256-VGPR limit and every value beyond it costs an AGPR copy per use) and the dZ arithmetic below
             // covers their LDS latency
@@ -1207,14 +1200,12 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             }
             // next tile's planes -> the other LDS buffer (last read in iteration it - 1, one barrier ago): the prefetch was requested at
             // the top of this iteration, and no store of this iteration has been issued yet (the wait is for loads only)
-            if (CIRS_BWD_COMMIT_EARLY && it + 1 < n_tiles) CIRS_COMMIT(buf ^ 1);
-            if (CIRS_BWD_REDUCE_POS == 1 && it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the dH2 product
+            if (it + 1 < n_tiles) CIRS_COMMIT(buf ^ 1);
             {
                 const HPl a0 = hsplit8(acc, 0), a1 = hsplit8(acc, 8);   // element j: dZ[row lo][item acc_row(8 t + j, hi)]
                 hmfma_pair(a0, cb[0][0], cb[1][0], dh0, dh1);
                 hmfma_pair(a1, cb[0][1], cb[1][1], dh0, dh1);
             }
-            if (CIRS_BWD_REDUCE_POS == 1 && it > 0) reduce_store(rg, tile0 - kTileN);
             CIRS_HSTAMP(5);
             CIRS_HSTAMP(6);
 #pragma unroll
@@ -1236,7 +1227,6 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             }
             rr[kTileN * kH + lane] = db;     // slot 32 hi + lo: the reducer adds the two halves
         }
-        if (!CIRS_BWD_COMMIT_EARLY && wave_ok && it + 1 < n_tiles) CIRS_COMMIT(buf ^ 1);
         CIRS_HSTAMP(9);
         lds_barrier();   // ONE workgroup barrier per tile: partial tiles + next tile's planes are visible
         CIRS_HSTAMP(10);
@@ -1692,7 +1682,6 @@ __device__ __forceinline__ void st_sc1x2(float* p, float a, float b) {      // 8
 __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int n_chunks, int S, const float* __restrict__ w1, const float* __restrict__ w2,
                                                          const float* __restrict__ wc, MbView v, float* __restrict__ dobs_accum, float* __restrict__ g,
                                                          long wa_beg, long wa_len, long slab_stride, int n_slabs, int n_r, int rslab /* floats per R slab */,
-                                                         int w_delay /* W workgroups start this many x 1024 cycles late: the R workgroups' requests go first */,
                                                          float* __restrict__ tail_out /* data-parallel phase 1: {clip, vf, ent, 0} partials of this rank */, int mb_norm,
                                                          int n_w /* W workgroups */) {
     __shared__ RowsLds L;
@@ -1765,7 +1754,6 @@ __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int 
     }
     if (b >= n_r) {
         CIRS_PSTAMP(b == n_r, 26);
-        for (int q = 0; q < w_delay; ++q) __builtin_amdgcn_s_sleep(16);
         wa_slab_sum_block1(g, wa_beg, wa_len, v.dwap, slab_stride, n_slabs, b - n_r, n_w, v.normp + kNormBlocks + (b - n_r), sRed);
         CIRS_PSTAMP(b == n_r, 27);
         return;
@@ -2105,7 +2093,6 @@ struct AdamNext {
     uint4* planes;
     int n_a0;                                                      // A0 workgroups (set with or without a next step)
     int s_magic;                                                   // ceil(65536 / S): i / S = (i * s_magic) >> 16 for i < 2048
-    int pa_delay;                                                  // P / A workgroups start this many x 1024 cycles late (the T workgroups' requests go first)
     int drop_arrival;                                              // TEST HOOK (CIRS_PPO_TEST_DROP_ARRIVAL=1): A0 workgroup 0 never raises its flag -> the T workgroups' wait must time out LOUDLY
     cirs_ppo_batch bt; int n_env;
     TrunkRowOut out;
@@ -2422,7 +2409,6 @@ __global__ __launch_bounds__(256) void adam_next_kernel(AdamArgs a, MbView mv, A
     const bool pn = nx.n_t > 0;      // (probe builds stamp the launches that have a next step)
     CIRS_PSTAMP(pn && b == b_t, 0); CIRS_PSTAMP(pn && b == b_s - 1, 4); CIRS_PSTAMP(pn && b == b_s, 6); CIRS_PSTAMP(pn && b == b_p, 8);
     CIRS_PSTAMP(pn && b == b_a - 1, 12); CIRS_PSTAMP(pn && b == 0, 14); CIRS_PSTAMP(pn && b == nx.n_a0 - 1, 16);
-    if (b >= b_p) for (int q = 0; q < nx.pa_delay; ++q) __builtin_amdgcn_s_sleep(16);
     if (b < b_t) adam_next_trunk_params(a, mv, l, b, nx.drop_arrival);
     else if (b < b_s) adam_next_trunk(a, nx, l, b - b_t, mv.sync);
     else if (b < b_p) adv_stats_block(nx.adv_flat, nx.sidx, nx.m_stats, nx.enable, nx.red, l.sh);
@@ -2636,7 +2622,6 @@ extern "C" int cirs_adam_step(float* params, const float* grads, float* m, float
 
 // ---- the launches of a minibatch step as separate pieces, so that cirs_ppo_minibatch (one step), cirs_ppo_minibatch_dp (the step cut at the
 // gradient all-reduce) and cirs_ppo_learn (all steps of an update from one call) issue the SAME kernels on the same data ---------------
-static int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 struct PpoRun {     // what does not change between the steps of a call
     const cirs_ppo_cfg* cfg;
     float *params, *grads, *adam_m, *adam_v;
@@ -2700,7 +2685,7 @@ static int launch_head(const PpoRun& r, const PpoStep& st, int* n_bchunks_out, b
     CIRS_CHECK_LAUNCH("head_stats_kernel");
     // head backward; the merge of the statistics partials + row losses + backward coefficients (means over the global minibatch) run in
     // its prologue (CIRS_PPO_MERGE_KERNEL=1: as a launch of their own, the round-2 sequence, for A/B runs)
-    const HeadMergeArgs hma{*r.cfg, *r.batch, st.idx, st.mb_norm, n_schunks, pv, env_int("CIRS_PPO_MERGE_T_ALL", 0)};
+    const HeadMergeArgs hma{*r.cfg, *r.batch, st.idx, st.mb_norm, n_schunks, pv};
     if (r.merge_launch) {
         hipLaunchKernelGGL(head_stats_merge_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, r.s, *r.cfg, *r.batch, st.idx, mb, st.mb_norm, n_pad, n_schunks,
                            r.n_env, pv, r.w.wa, r.w.ba, v, (const float*)nullptr, 0);
@@ -2781,15 +2766,11 @@ static int launch_trunk_rows(const PpoRun& r, const PpoStep& st, int n_bchunks, 
     int n_w = (int)cdiv(n4, 512L);
     n_w = n_w > kWaSlotsMax ? kWaSlotsMax : n_w;
     // (round 6, second half) no more W workgroups than CUs the R workgroups leave free: a W workgroup that shares a CU with an R workgroup competes with its
-    // slab loads -- same box, 1024 rows: 340 / 256 / 170 / 128 / 84 W workgroups = 70.1 / 70.2 / 69.5 / 69.0 / 69.3 us per step; CIRS_PPO_W_WGS overrides
-    {
-        const int free_cus = std::max(64, device_cu_count() - n_r), wv = env_int("CIRS_PPO_W_WGS", 0);
-        if (wv > 0) n_w = std::min(n_w, wv);
-        else n_w = std::min(n_w, free_cus);
-    }
+    // slab loads -- same box, 1024 rows: 340 / 256 / 170 / 128 / 84 W workgroups = 70.1 / 70.2 / 69.5 / 69.0 / 69.3 us per step
+    n_w = std::min(n_w, std::max(64, device_cu_count() - n_r));
     hipLaunchKernelGGL(trunk_rows_kernel, dim3(n_r + n_w + n_f + (with_loss_partials ? 1 : 0)), dim3(512), 0, r.s, st.mb, n_pad, n_bchunks, r.S, r.w.w1,
                        r.w.w2, r.w.wc, r.v, st.dobs, r.grads, (long)r.L.wa, seg, (long)dwa_slab_stride(r.I), n_slabs, n_r, snap_stride(r.S),
-                       env_int("CIRS_PPO_W_DELAY", 0), with_loss_partials ? r.tail : (float*)nullptr, st.mb_norm, n_w);
+                       with_loss_partials ? r.tail : (float*)nullptr, st.mb_norm, n_w);
     CIRS_CHECK_LAUNCH("trunk_rows_kernel");
     return CIRS_OK;
 }
@@ -2828,8 +2809,8 @@ static int launch_norm_adam(const PpoRun& r, const PpoStep& st, int phase, bool 
         nx.pcfg = r.pcfg; nx.obs_flat = r.batch->obs; nx.idx = next->idx; nx.mb = next->mb; nx.n_pad = np;
         nx.adv_flat = r.batch->adv; nx.sidx = next->sidx; nx.m_stats = next->mb_norm; nx.enable = (int)r.cfg->norm_adv; nx.red = v.red;
         nx.bt = *r.batch; nx.n_env = r.n_env; nx.out = trunk_out_of(v); nx.s_magic = (65536 + r.S - 1) / r.S;
-        nx.pa_delay = env_int("CIRS_PPO_PA_DELAY", 0);      // (A/B on one box: 0 / 4 -> 78.0-78.6 / 78.5-78.9 us per step)
-        nx.drop_arrival = env_int("CIRS_PPO_TEST_DROP_ARRIVAL", 0);
+        const char* da_ = getenv("CIRS_PPO_TEST_DROP_ARRIVAL");
+        nx.drop_arrival = da_ ? atoi(da_) : 0;
     }
     nx.n_a0 = cdiv(r.L.trunk + kH + 1, 256);
     const int n_a = nx.n_a0 + cdiv(r.I, 256);

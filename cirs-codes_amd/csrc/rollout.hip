@@ -41,9 +41,8 @@ __global__ __launch_bounds__(256) void online_pairs_kernel(const int32_t* __rest
     o.dur_buf[j] = o.item_dur[a];
 }
 
-constexpr int kMaxGroups = 4;
-// sampler scratch of one env group (cirs_policy_workspace_bytes without its slack)
-static inline int64_t group_ws_bytes(const cirs_policy_cfg* cfg, int n) {
+// sampler scratch (cirs_policy_workspace_bytes without its slack): the logit store sits behind it
+static inline int64_t sampler_ws_bytes(const cirs_policy_cfg* cfg, int n) {
     return (int64_t)(ws_h2_floats(n) + 5 * ws_partial_elems(n, cfg->n_items)) * 4;
 }
 
@@ -186,81 +185,28 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
     CIRS_REQUIRE(workspace_bytes >= cirs_policy_workspace_bytes(pol_cfg, n_env), "workspace too small");
     CIRS_REQUIRE(env_tab->item_cats && (env_tab->normed_mat || !env_cfg->simulated) && (env_tab->mat || env_cfg->simulated), "env tables incomplete");
     if (t_begin >= t_end) return CIRS_OK;
-    // ---- env groups on separate streams ---------------------------------------------------------------------------------------
-    // The step kernel (one wavefront per env) is latency-bound: a chain of ~25 dependent stages that leaves the matrix / vector pipes
-    // idle, while the chunk-mass kernel of the sampler is throughput-bound.  Envs are independent (noise, masks and dropout are
-    // keyed by the env id), so the envs are split into G groups whose launch sequences run on G streams: one group's step kernel
-    // overlaps another group's mass kernel.  Results are identical to G = 1 (tests/test_gpu_rollout.py).
-    int G = 1;
-    if (!gumbel) {
-        static const int forced = [] { const char* ev = getenv("CIRS_ROLLOUT_GROUPS"); return ev ? atoi(ev) : 0; }();   // thread-safe magic static
-        // measured at C3 (1024 envs): rollout alone 1.96 ms (G = 1), 1.81 ms (2), 1.87 ms (4); the whole step (rollout + update)
-        // 8.82 / 8.93 / 10.46 ms -- the additional launches and the fork / join of the streams cost more host and queue time than the
-        // overlap returns, so one group is the default and CIRS_ROLLOUT_GROUPS opts in
-        G = forced > 0 ? forced : 1;
-        if (G > kMaxGroups) G = kMaxGroups;
-        if (redraw) G = 1;
-    }
-    int n_g = ((n_env + G - 1) / G + 127) / 128 * 128;       // rows per group: whole 128-row blocks of the mass kernel
-    if (G > 1) {   // room for one sampler workspace per group?
-        const int64_t per = (group_ws_bytes(pol_cfg, n_g) + 255) & ~(int64_t)255;
-        if (per * G > workspace_bytes - kTrkImgBytes - (int64_t)ws_rplanes_bytes(pol_cfg->n_items) - 512) { G = 1; n_g = n_env; }
-    } else {
-        n_g = n_env;
-    }
-    // packed weight image of the step kernel (tracker + policy trunk), rebuilt per call (the weights change between calls) on the
-    // caller's stream, before the group streams fork from it
+    // packed weight image of the step kernel (tracker + policy trunk), rebuilt per call (the weights change between calls)
     float* img = (float*)((char*)workspace + ((workspace_bytes - kTrkImgBytes) & ~(int64_t)255));
     // ... the fp16 planes of the actor head for the chunk-mass kernels, likewise once per call, and (cirs_rollout_collect) env.reset: one launch
     uint4* rplanes = ws_rplanes(workspace, workspace_bytes, pol_cfg->n_items);
     if (int rc = pack_tracker_image(trk_cfg, trk_w, pol_w, S, img, s, pol_w->wa, pol_cfg->n_items, gumbel ? nullptr : rplanes, init_users ? env_cfg : nullptr, env_st,
                                     init_users, n_env, (int64_t*)workspace))
         return rc;
-    // group streams / events: one set per (host thread, device) -- a stream belongs to the device that was current when it was
-    // created, and two host threads driving rollouts concurrently (the virtual-rank tests) must not share the event array
-    constexpr int kMaxDevices = 16;
-    struct GroupQueues { hipStream_t gs[kMaxGroups]; hipEvent_t gev[kMaxGroups + 1]; };
-    static thread_local GroupQueues tl_queues[kMaxDevices] = {};
-    int cur_dev = 0;
-    if (G > 1) {
-        CIRS_HIP(hipGetDevice(&cur_dev));
-        CIRS_REQUIRE(cur_dev >= 0 && cur_dev < kMaxDevices, "CIRS_ROLLOUT_GROUPS > 1 supports device ids below 16");
-    }
-    hipStream_t* gs = tl_queues[cur_dev].gs;
-    hipEvent_t* gev = tl_queues[cur_dev].gev;
-    if (G > 1) {
-        for (int g = 1; g < G; ++g)
-            if (!gs[g]) CIRS_HIP(hipStreamCreateWithFlags(&gs[g], hipStreamNonBlocking));
-        for (int g = 0; g <= G && g <= kMaxGroups; ++g)
-            if (!gev[g]) CIRS_HIP(hipEventCreateWithFlags(&gev[g], hipEventDisableTiming));
-        CIRS_HIP(hipEventRecord(gev[0], s));
-        for (int g = 1; g < G; ++g) CIRS_HIP(hipStreamWaitEvent(gs[g], gev[0], 0));
-    }
-    const int64_t ws_per = (group_ws_bytes(pol_cfg, n_g) + 255) & ~(int64_t)255;
+    // sampler scratch at the head of the workspace (the kernels below take the env id of their row 0: always 0 here)
+    const int n_pad = n_pad_of(n_env);
     const int n_mass_chunks = n_chunks_of(pol_cfg->n_items);
-    struct Group { int base, n, n_pad; float* h2; ActorPartialView pv; HeadGrid hg; int cpw; hipStream_t st; };
-    Group grp[kMaxGroups];
-    int n_groups = 0;
-    for (int g = 0; g < G; ++g) {
-        const int base = g * n_g;
-        if (base >= n_env) break;
-        Group& q = grp[n_groups++];
-        q.base = base; q.n = min(n_g, n_env - base); q.n_pad = n_pad_of(q.n);
-        void* wsg = (char*)workspace + (size_t)g * ws_per;
-        q.h2 = (float*)wsg;
-        q.pv = partial_view(wsg, q.n, pol_cfg->n_items);
-        q.hg = sampler_grid(pol_cfg->n_items, q.n_pad);
-        q.cpw = mass_chunks_per_wg(n_mass_chunks, q.hg.n_row_blocks);
-        q.st = g == 0 ? s : gs[g];
-    }
-    // logit store (one group, counter-based sampler, small env counts): behind the group's sampler scratch
+    float* h2 = (float*)workspace;
+    const ActorPartialView pv = partial_view(workspace, n_env, pol_cfg->n_items);
+    const HeadGrid hg = sampler_grid(pol_cfg->n_items, n_pad);
+    const int cpw = mass_chunks_per_wg(n_mass_chunks, hg.n_row_blocks);
+    // logit store (counter-based sampler, small env counts): behind the sampler scratch
     float* zstore = nullptr;
-    if (n_groups == 1 && !gumbel && ws_zstore_floats(n_env, pol_cfg->n_items) > 0) {
+    if (!gumbel && ws_zstore_floats(n_env, pol_cfg->n_items) > 0) {
         const char* ev = getenv("CIRS_ROLLOUT_ZSTORE");     // read per call (like CIRS_PPO_MERGE_KERNEL): a test may flip it between collects
-        if (ev ? atoi(ev) != 0 : true) zstore = (float*)((char*)workspace + ws_per);
+        if (ev ? atoi(ev) != 0 : true) zstore = (float*)((char*)workspace + ((sampler_ws_bytes(pol_cfg, n_env) + 255) & ~(int64_t)255));
     }
     const char* ms_ev = getenv("CIRS_ROLLOUT_MASS_SMALL");   // per call as well
-    const bool mass_small = (ms_ev ? atoi(ms_ev) != 0 : true) && n_groups == 1 && !gumbel && grp[0].n_pad <= 128;
+    const bool mass_small = (ms_ev ? atoi(ms_ev) != 0 : true) && !gumbel && n_pad <= 128;
     const uint8_t* done_all = (const uint8_t*)env_st->done;
     // Exact-redraw dropout (the reference's procedure, core/state_tracker.py:170-186,243-246): the state of vector step t is NOT the cached decode's -- it is
     // ONE batched causal pass over positions 0 .. t of every env with the masks of build_state call t (cirs_tracker_prefix_states, key = the collect's key with
@@ -273,26 +219,26 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
         cfg_t.drop_env_base = (int32_t)(redraw->env_base0 + (int64_t)t * redraw->env_stride);
         const size_t start = (size_t)B * t * (t + 1) / 2;
         TrunkFuse tf{};
-        if (with_trunk) { tf.on = 1; tf.cfg = *pol_cfg; tf.w = *pol_w; tf.skip = done_all; tf.h2 = grp[0].h2; tf.value = traj->value + (size_t)t * B; }
+        if (with_trunk) { tf.on = 1; tf.cfg = *pol_cfg; tf.w = *pol_w; tf.skip = done_all; tf.h2 = h2; tf.value = traj->value + (size_t)t * B; }
         int fused = 0;
         if (int rc = tracker_prefix_states_trunk(&cfg_t, trk_w, trk_st, redraw->row_env + start, redraw->row_t + start, redraw->offsets + (size_t)t * B,
                                                  redraw->lens + (size_t)t * B, (int32_t)(B * (t + 1)), traj->obs + (size_t)t * B * S, S, redraw->workspace,
                                                  redraw->workspace_bytes, stream, &tf, &fused))
             return rc;
         if (with_trunk && !fused) {
-            hipLaunchKernelGGL(trunk_kernel, dim3(cdiv(n_env, 4)), dim3(256), 0, s, *pol_cfg, *pol_w, traj->obs + (size_t)t * B * S, (long)S, n_env, done_all, grp[0].h2,
+            hipLaunchKernelGGL(trunk_kernel, dim3(cdiv(n_env, 4)), dim3(256), 0, s, *pol_cfg, *pol_w, traj->obs + (size_t)t * B * S, (long)S, n_env, done_all, h2,
                                traj->value + (size_t)t * B, (float*)nullptr);
             CIRS_CHECK_LAUNCH("trunk_kernel");
         }
         return CIRS_OK;
     };
     // cirs_rollout_collect: the tracker's first position (Collector.reset_env's preprocess_fn(obs = ...)) from the packed image, with the trunk of the first
-    // vector step in its launch (one group) -- cirs_tracker_init's row-major weight reads were 23 us per collect, the separate trunk launch 6
+    // vector step in its launch -- cirs_tracker_init's row-major weight reads were 23 us per collect, the separate trunk launch 6
     bool first_trunk_done = false;
     if (init_users) {
         TrunkFuse tf0{};
-        if (n_groups == 1 && !redraw) {
-            tf0.on = 1; tf0.cfg = *pol_cfg; tf0.w = *pol_w; tf0.skip = nullptr; tf0.h2 = grp[0].h2; tf0.value = traj->value + (size_t)t_begin * B;
+        if (!redraw) {
+            tf0.on = 1; tf0.cfg = *pol_cfg; tf0.w = *pol_w; tf0.skip = nullptr; tf0.h2 = h2; tf0.value = traj->value + (size_t)t_begin * B;
             first_trunk_done = true;
         }
         if (int rc = tracker_step_internal(trk_cfg, trk_w, trk_st, init_users, nullptr, nullptr, nullptr, nullptr, n_env, traj->obs + (size_t)t_begin * B * S, S, &tf0, s,
@@ -301,67 +247,54 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
     }
     if (redraw) { if (int rc = redraw_state(t_begin, true)) return rc; }
     // trunk of the first step of this call (later ones ride on the tracker step)
-    for (int gi = 0; gi < n_groups && !redraw && !first_trunk_done; ++gi) {
-        const Group& q = grp[gi];
-        hipLaunchKernelGGL(trunk_kernel, dim3(cdiv(q.n, 4)), dim3(256), 0, q.st, *pol_cfg, *pol_w,
-                           traj->obs + ((size_t)t_begin * B + q.base) * S, (long)S, q.n, done_all + q.base, q.h2,
-                           traj->value + (size_t)t_begin * B + q.base, (float*)nullptr);
-    }
+    if (!redraw && !first_trunk_done)
+        hipLaunchKernelGGL(trunk_kernel, dim3(cdiv(n_env, 4)), dim3(256), 0, s, *pol_cfg, *pol_w, traj->obs + (size_t)t_begin * B * S, (long)S, n_env, done_all,
+                           h2, traj->value + (size_t)t_begin * B, (float*)nullptr);
     CIRS_CHECK_LAUNCH("trunk_kernel");
     for (int t = t_begin; t < t_end; ++t) {
         const float* gum_t = gumbel ? gumbel + (size_t)t * B * pol_cfg->n_items : (const float*)nullptr;
-        for (int gi = 0; gi < n_groups; ++gi) {
-            const Group& q = grp[gi];
-            float* obs_n = traj->obs + ((size_t)(t + 1) * B + q.base) * S;
-            int64_t* act_t = traj->act + (size_t)t * B + q.base;
-            double* rew_t = traj->rew + (size_t)t * B + q.base;
-            uint8_t* done_t = traj->done + (size_t)t * B + q.base;
-            if (gum_t) {   // harness-supplied noise: plain Gumbel-max over the catalogue (reference-recorded fixtures); one group
-                CIRS_PROF_LAUNCH(3, q.st, hipLaunchKernelGGL(actor_head_kernel, dim3(q.hg.grid_x, q.hg.n_row_blocks), dim3(256), 0, q.st, *pol_cfg,
-                                                             pol_w->wa, pol_w->ba, (const float*)q.h2, q.n, gum_t, seed,
-                                                             rng_base + (uint32_t)t, (const int32_t*)nullptr, (const uint32_t*)visited,
-                                                             done_all, q.pv, q.n_pad, q.hg.tiles_per_chunk));
-            } else if (mass_small) {   // few envs: one workgroup per chunk, one wave per (row tile, item tile)
-                CIRS_PROF_LAUNCH(3, q.st, hipLaunchKernelGGL(actor_mass_small_kernel, dim3(n_mass_chunks), dim3(q.n_pad / kTileM * 256), 0, q.st, *pol_cfg, (const uint4*)rplanes,
-                                                             pol_w->ba, (const float*)q.h2, q.n, (const uint32_t*)visited, done_all + q.base, q.pv.m, q.n_pad, q.base,
-                                                             zstore));
-            } else {       // counter-based sampler: chunk log-masses now, chunk + item draws in the tail of the step kernel
-                CIRS_PROF_LAUNCH(3, q.st, hipLaunchKernelGGL(actor_mass_kernel, dim3(cdiv(n_mass_chunks, q.cpw), q.hg.n_row_blocks), dim3(kMassThreads), 0,
-                                                             q.st, *pol_cfg, (const uint4*)rplanes, pol_w->ba, (const float*)q.h2, q.n, (const int32_t*)nullptr,
-                                                             (const uint32_t*)visited, done_all + q.base, q.pv.m, q.n_pad, q.cpw, 0, 0, q.base, zstore));
-            }
-            CIRS_CHECK_LAUNCH("sampler kernel");
-            TrunkFuse tf{};
-            if (t + 1 < t_end && !redraw) {
-                tf.on = 1; tf.cfg = *pol_cfg; tf.w = *pol_w; tf.skip = done_all + q.base; tf.h2 = q.h2;
-                tf.value = traj->value + (size_t)(t + 1) * B + q.base;
-            }
-            // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
-            // ... in the same launch as the tail of this step: action / logp, visited bit, env step, forced length
-            TailFuse tl{};
-            tl.on = 1; tl.cfg = *env_cfg; tl.tab = *env_tab; tl.st = *env_st; tl.n_pad = q.n_pad; tl.n_chunks = q.hg.n_chunks; tl.pv = q.pv;
-            tl.env_base = q.base;
-            tl.visited = visited; tl.force_length = force_length;
-            if (!gum_t) {
-                tl.pick_on = 1;
-                tl.pick = PickArgs{q.pv.m, q.n_pad, n_mass_chunks, pol_w->wa, pol_w->ba, q.h2, visited, pol_cfg->n_items, 0, 0, seed, rng_base + (uint32_t)t, zstore};
-            }
-            tl.force_done = (t + 1 >= force_length) ? 1 : 0;
-            // (exact redraw: obs_{t+1} is overwritten by call t + 1's prefix pass below -- under the same condition -- so the cached decode is not run)
-            tl.slot_only = redraw && (t + 1 < t_end || t + 1 < trk_cfg->max_len) && !getenv("CIRS_REDRAW_FULL_DECODE") ? 1 : 0;
-            tl.act_out = act_t; tl.logp_out = traj->logp + (size_t)t * B + q.base; tl.rew_out = rew_t; tl.done_out = done_t;
-            tl.ctr_out = traj->ctr + (size_t)t * B + q.base;
-            if (int rc = tracker_step_internal(trk_cfg, trk_w, trk_st, nullptr, act_t, rew_t, nullptr, nullptr, q.n, obs_n, S, &tf, q.st, &tl, img))
-                return rc;
-            if (redraw && (t + 1 < t_end || t + 1 < trk_cfg->max_len)) {      // the state of call t + 1 (the last one: obs_next of the final step)
-                if (int rc = redraw_state(t + 1, t + 1 < t_end)) return rc;
-            }
+        float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
+        int64_t* act_t = traj->act + (size_t)t * B;
+        double* rew_t = traj->rew + (size_t)t * B;
+        uint8_t* done_t = traj->done + (size_t)t * B;
+        if (gum_t) {   // harness-supplied noise: plain Gumbel-max over the catalogue (reference-recorded fixtures)
+            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_head_kernel, dim3(hg.grid_x, hg.n_row_blocks), dim3(256), 0, s, *pol_cfg,
+                                                      pol_w->wa, pol_w->ba, (const float*)h2, n_env, gum_t, seed,
+                                                      rng_base + (uint32_t)t, (const int32_t*)nullptr, (const uint32_t*)visited,
+                                                      done_all, pv, n_pad, hg.tiles_per_chunk));
+        } else if (mass_small) {   // few envs: one workgroup per chunk, one wave per (row tile, item tile)
+            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_mass_small_kernel, dim3(n_mass_chunks), dim3(n_pad / kTileM * 256), 0, s, *pol_cfg, (const uint4*)rplanes,
+                                                      pol_w->ba, (const float*)h2, n_env, (const uint32_t*)visited, done_all, pv.m, n_pad, 0, zstore));
+        } else {       // counter-based sampler: chunk log-masses now, chunk + item draws in the tail of the step kernel
+            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_mass_kernel, dim3(cdiv(n_mass_chunks, cpw), hg.n_row_blocks), dim3(kMassThreads), 0,
+                                                      s, *pol_cfg, (const uint4*)rplanes, pol_w->ba, (const float*)h2, n_env, (const int32_t*)nullptr,
+                                                      (const uint32_t*)visited, done_all, pv.m, n_pad, cpw, 0, 0, 0, zstore));
         }
-    }
-    if (n_groups > 1) {
-        for (int gi = 1; gi < n_groups; ++gi) {
-            CIRS_HIP(hipEventRecord(gev[gi], grp[gi].st));
-            CIRS_HIP(hipStreamWaitEvent(s, gev[gi], 0));
+        CIRS_CHECK_LAUNCH("sampler kernel");
+        TrunkFuse tf{};
+        if (t + 1 < t_end && !redraw) {
+            tf.on = 1; tf.cfg = *pol_cfg; tf.w = *pol_w; tf.skip = done_all; tf.h2 = h2;
+            tf.value = traj->value + (size_t)(t + 1) * B;
+        }
+        // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
+        // ... in the same launch as the tail of this step: action / logp, visited bit, env step, forced length
+        TailFuse tl{};
+        tl.on = 1; tl.cfg = *env_cfg; tl.tab = *env_tab; tl.st = *env_st; tl.n_pad = n_pad; tl.n_chunks = hg.n_chunks; tl.pv = pv;
+        tl.env_base = 0;
+        tl.visited = visited; tl.force_length = force_length;
+        if (!gum_t) {
+            tl.pick_on = 1;
+            tl.pick = PickArgs{pv.m, n_pad, n_mass_chunks, pol_w->wa, pol_w->ba, h2, visited, pol_cfg->n_items, 0, 0, seed, rng_base + (uint32_t)t, zstore};
+        }
+        tl.force_done = (t + 1 >= force_length) ? 1 : 0;
+        // (exact redraw: obs_{t+1} is overwritten by call t + 1's prefix pass below -- under the same condition -- so the cached decode is not run)
+        tl.slot_only = redraw && (t + 1 < t_end || t + 1 < trk_cfg->max_len) ? 1 : 0;
+        tl.act_out = act_t; tl.logp_out = traj->logp + (size_t)t * B; tl.rew_out = rew_t; tl.done_out = done_t;
+        tl.ctr_out = traj->ctr + (size_t)t * B;
+        if (int rc = tracker_step_internal(trk_cfg, trk_w, trk_st, nullptr, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, &tf, s, &tl, img))
+            return rc;
+        if (redraw && (t + 1 < t_end || t + 1 < trk_cfg->max_len)) {      // the state of call t + 1 (the last one: obs_next of the final step)
+            if (int rc = redraw_state(t + 1, t + 1 < t_end)) return rc;
         }
     }
     return CIRS_OK;

@@ -254,27 +254,15 @@ static __global__ __launch_bounds__(256) void dw_multi_final(DwJobs jobs, int n_
 }
 
 // ---- a whole backward pass worth of dW problems: slab partials per problem, ONE final launch -----------------------
-// launch_dw_partial() runs dw_gemm_kernel into the problem's own region of `partial` and records the job; dw_list_final sums
-// the slabs of every recorded problem in slab order (diag: only the diagonal of a square problem is kept -- LayerNorm weight
-// gradients are the diagonal of dY^T Xhat).
+// launch_rows_gemm_dw() and dw_batch_add() (tracker_bwd.hip) give every problem its own region of `partial` for its slab partials and record
+// the job; dw_list_final sums the slabs of every recorded problem in slab order (diag: only the diagonal of a square problem is kept --
+// LayerNorm weight gradients are the diagonal of dY^T Xhat).
 constexpr int kMaxDwList = 3 + 6 * CIRS_MAX_TRACKER_LAYERS;   // the tracker backward pass: decoder, user ffn, gate + 6 per layer
 struct DwListJob { int O, K, part_off, diag; float* dW; float* db; };
 struct DwList { DwListJob j[kMaxDwList]; int n, total_out, part_floats; };
 
-static inline void launch_dw_partial(DwList& list, const float* dY, int ldy, const float* X, int ldx, int R, int O, int K, float* dW,
-                                     float* db, int diag, float* partial, hipStream_t s) {
-    const int slabs = dwg_slabs(R);
-    int rows_per_slab = (R + slabs - 1) / slabs;
-    rows_per_slab = (rows_per_slab + 15) & ~15;
-    DwListJob& jb = list.j[list.n++];
-    jb.O = O; jb.K = K; jb.part_off = list.part_floats; jb.diag = diag; jb.dW = dW; jb.db = db;
-    list.part_floats += slabs * O * (K + 1);
-    list.total_out += O * (K + 1);
-    const int tiles = cdiv(O, 32) * cdiv(K, 32);
-    hipLaunchKernelGGL(dw_gemm_kernel, dim3(tiles, slabs), dim3(64), 0, s, dY, ldy, X, ldx, R, O, K, rows_per_slab, partial + jb.part_off);
-}
-
-// launch_dw_partial(list, dY, ..) + launch_rows_gemm(nt, ..) as one launch (see rows_gemm_dw_kernel)
+// launch_rows_gemm(nt, ..) + the dW problem of its X (dY) into the problem's own region of `partial`, recorded in `list`: one launch
+// (see rows_gemm_dw_kernel)
 static inline void launch_rows_gemm_dw(DwList& list, const float* dwX, int dw_ldx, int dwO, int dwK, float* dW, float* db, float* partial,
                                        bool nt, const float* X, int ldx, const float* W, int ldw, const float* bias, int R, int Kd, int N,
                                        int relu, const float* relu_of, int accumulate, float* Y, int ldy, hipStream_t s) {

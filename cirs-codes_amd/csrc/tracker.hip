@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void tracker_step_kernel(cirs_tracker_cfg cfg,
         int64_t act = -1;
         // the env's own state (user, turn, history entry of this lane, running reward) does not depend on the action: its loads
         // are issued BEFORE the merge of the sampler partials and complete underneath it
-        const int et = tl.env_base + j;    // this row's env (env groups: row 0 of the launch is env env_base)
+        const int et = tl.env_base + j;    // this row's env (row 0 of the launch is env env_base)
         CIRS_STAMP(32);
         const EnvPrefetch epf = env_prefetch(tl.cfg, tl.st, et, lane);
         CIRS_STAMP(33);
@@ -712,14 +712,8 @@ static int launch_tracker(const cirs_tracker_cfg* cfg, const cirs_tracker_weight
     // + the row stage of the two-level sampler's item draw when the tail of the vector step is fused in (69.6 KB per workgroup)
     // Few rows (the 64-env shape): one wavefront per workgroup and an LDS request that keeps workgroups on DIFFERENT CUs -- four env rows on one CU share its
     // ~11 B/cycle load path (the pick's rows, the K/V caches, the weight image) while 240 CUs idle.  Same per-wavefront code: same bits.
-    int wpw = 4;
-    {
-        const int cus = device_cu_count();
-        const char* ev = getenv("CIRS_STEP_WAVES");
-        if (ev && (atoi(ev) == 1 || atoi(ev) == 2 || atoi(ev) == 4)) wpw = atoi(ev);
-        else if (n <= cus) wpw = 1;
-        else if (n <= 2 * cus) wpw = 2;
-    }
+    const int cus = device_cu_count();
+    const int wpw = n <= cus ? 1 : n <= 2 * cus ? 2 : 4;
     size_t shmem = wpw * sizeof(float) * (6 * kD + kHid + (size_t)cfg->nhead * lpad) + (tl.on && tl.pick_on ? wpw * sizeof(float) * kPickStage : 0);
     if (wpw < 4 && shmem <= 81 * 1024) shmem = 81 * 1024;      // (more than half a CU's 160 KB: one workgroup per CU)
     if (shmem > 160 * 1024) return fail(CIRS_E_UNSUPPORTED, "max_len too large for the LDS score buffer");

@@ -44,27 +44,6 @@ struct DropCfg {
 __device__ __forceinline__ float drop_apply(const DropCfg& dc, float v, int env, int pos, int layer, int site, int elem) {
     return dropout_keep(dc.seed, (uint32_t)(dc.env_base + env), (uint32_t)pos, (uint32_t)layer, (uint32_t)site, (uint32_t)elem, dc.thr) ? v * dc.inv : 0.f;
 }
-// elementwise: out[r, c] = mask(row r's (env, position), layer, site, c) * in[r, c]   (N columns per row; in == out allowed)
-__global__ __launch_bounds__(256) void drop_rows(DropCfg dc, const float* __restrict__ in, const int32_t* __restrict__ row_env,
-                                                 const int32_t* __restrict__ row_t, int R, int N, int layer, int site, float* __restrict__ out) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= (long)R * N) return;
-    const int r = (int)(i / N), c = (int)(i % N);
-    out[i] = drop_apply(dc, in[i], row_env[r], row_t[r], layer, site, c);
-}
-
-// slot gather + scale + positional encoding: X0[r] = x_hist[b,p], H0 = X0*sqrt(D) + pe[p]
-__global__ __launch_bounds__(256) void embed_rows(const float* __restrict__ x_hist, const float* __restrict__ pe,
-                                                  const int32_t* __restrict__ row_env, const int32_t* __restrict__ row_t, int R,
-                                                  int L, float* __restrict__ H0, DropCfg dc) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= (long)R * tD) return;
-    const int r = (int)(i / tD), d = (int)(i % tD);
-    const int b = row_env[r], p = row_t[r];
-    const float h = x_hist[((size_t)b * L + p) * tD + d] * 5.656854249492381f + pe[(size_t)p * tD + d];
-    H0[i] = dc.on ? drop_apply(dc, h, b, p, 0, CIRS_DROP_POS, d) : h;
-}
-
 // causal attention forward, one wavefront per row; Q/K/V live in QKV[R,96]; P[R,NH,Lp] keeps the probabilities for
 // the backward.  The probabilities are exchanged between lanes through a per-wave LDS strip (not through global).
 template <int NH>
@@ -722,37 +701,6 @@ __global__ __launch_bounds__(64) void attn_bwd_ep(const float* __restrict__ QKV,
 }
 #undef EP_KEEP
 
-// sum over the 32 lanes of a half-wave (one LayerNorm row per half-wave), result in every lane of the half
-__device__ __forceinline__ float half_sum32(float v) {
-#pragma unroll
-    for (int off = 16; off > 0; off >>= 1) v += __shfl_xor(v, off, CIRS_WAVE);
-    return v;
-}
-
-// LayerNorm(32) forward, one lane per element (a row = one half-wave, coalesced 128-byte rows):
-// y = Y + Y2 (residual); out = (y - mean) * rstd * g + b ; xhat and rstd kept for the backward
-__global__ __launch_bounds__(256) void ln_fwd(const float* __restrict__ Y, const float* __restrict__ Y2, const float* __restrict__ g,
-                                              const float* __restrict__ b, int R, float* __restrict__ xhat, float* __restrict__ rstd,
-                                              float* __restrict__ out, DropCfg dc, const int32_t* __restrict__ row_env,
-                                              const int32_t* __restrict__ row_t, int layer, int site) {
-    static_assert(tD == 32, "one half-wave per row");
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long r = i >> 5;
-    const int d = (int)(i & 31);
-    const bool ok = r < R;
-    float y2 = ok ? Y2[i] : 0.f;
-    if (dc.on && ok) y2 = drop_apply(dc, y2, row_env[r], row_t[r], layer, site, d);   // dropout1 / dropout2 on the branch
-    const float y = ok ? Y[i] + y2 : 0.f;   // the pre-LayerNorm residual sum rides along
-    const float mean = half_sum32(y) * (1.0f / tD);
-    const float t = y - mean;
-    const float var = half_sum32(t * t) * (1.0f / tD);
-    const float rs = 1.0f / sqrtf(var + 1e-5f);
-    if (!ok) return;
-    if (d == 0) rstd[r] = rs;
-    const float xh = t * rs;
-    xhat[i] = xh;
-    out[i] = xh * g[d] + b[d];
-}
 // ---- fused row chains of the forward recompute (round 3) ------------------------------------------------------------------------
 // Everything between two attention stages is row-local: out_proj + residual + LayerNorm1 + lin1 (relu) + lin2 + residual + LayerNorm2 +
 // the next layer's in_proj.  One wavefront owns a 32-row tile and walks the whole chain: the GEMMs on v_mfma_f32_32x32x2_f32 with the
@@ -969,7 +917,7 @@ __global__ __launch_bounds__(64) void layer_rows_fwd(LayerFwdArgs a, DropCfg dc)
     CIRS_BSTAMP(11);
 }
 
-// slot gather + scale + positional encoding (embed_rows) + the first layer's in_proj, one wavefront per 32 rows
+// slot gather + scale + positional encoding (H0[r] = x_hist[b, p] sqrt(D) + pe[p]) + the first layer's in_proj, one wavefront per 32 rows
 template <bool kDrop>
 __global__ __launch_bounds__(64) void embed_inproj(const float* __restrict__ x_hist, const float* __restrict__ pe,
                                                    const int32_t* __restrict__ row_env, const int32_t* __restrict__ row_t, int R, int L,
@@ -1213,48 +1161,6 @@ static inline void dw_batch_launch(const DwBatch& b, int R, hipStream_t s, int R
     int rows_per_slab = (R_rows + slabs - 1) / slabs;
     rows_per_slab = (rows_per_slab + 15) & ~15;
     hipLaunchKernelGGL(dw_batch_kernel, dim3(b.total_tiles, slabs), dim3(64), 0, s, b, R_rows, rows_per_slab);
-}
-
-// LayerNorm backward, same mapping: dY = rstd * (dxh - mean(dxh) - xhat * mean(dxh*xhat)), dxh = dOut * g
-// LayerNorm backward + the weight / bias gradient problem of the same LayerNorm (diag(dOut^T xhat), column sums of dOut: a dw_gemm
-// problem) in ONE launch of 64-thread workgroups: the first n_ln of them are the row-wise part, the rest the dW slabs (independent of
-// each other, same inputs; a launch of this size costs ~6 us whatever it computes)
-__global__ __launch_bounds__(64) void ln_bwd_dw_kernel(const float* __restrict__ dOut, const float* __restrict__ xhat, const float* __restrict__ rstd,
-                                                       const float* __restrict__ g, int R, float* __restrict__ dY, int n_ln, DwGemmArgs da, int dgx) {
-    if ((int)blockIdx.x >= n_ln) {
-        const int q = (int)blockIdx.x - n_ln;
-        dw_gemm_body(q % dgx, q / dgx, da.dY, da.ldy, da.X, da.ldx, da.R, da.O, da.K, da.rows_per_slab, da.partial);
-        return;
-    }
-    const long i = blockIdx.x * 64L + threadIdx.x;
-    const long r = i >> 5;
-    const int d = (int)(i & 31);
-    const bool ok = r < R;
-    const float dxh = ok ? dOut[i] * g[d] : 0.f;
-    const float xh = ok ? xhat[i] : 0.f;
-    const float m1 = half_sum32(dxh) * (1.0f / tD);
-    const float m2 = half_sum32(dxh * xh) * (1.0f / tD);
-    if (ok) dY[i] = rstd[r] * (dxh - m1 - xh * m2);
-}
-
-__global__ __launch_bounds__(256) void ln_bwd(const float* __restrict__ dOut, const float* __restrict__ xhat, const float* __restrict__ rstd,
-                                              const float* __restrict__ g, int R, float* __restrict__ dY) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long r = i >> 5;
-    const int d = (int)(i & 31);
-    const bool ok = r < R;
-    const float dxh = ok ? dOut[i] * g[d] : 0.f;
-    const float xh = ok ? xhat[i] : 0.f;
-    const float m1 = half_sum32(dxh) * (1.0f / tD);
-    const float m2 = half_sum32(dxh * xh) * (1.0f / tD);
-    if (ok) dY[i] = rstd[r] * (dxh - m1 - xh * m2);
-}
-// (the LayerNorm weight gradient d gamma = diag(dOut^T xhat) and d beta = column sums of dOut fall out of a 32 x 32 dW
-// problem with the diag flag: dw_list_final keeps the diagonal)
-
-__global__ __launch_bounds__(256) void scale_rows(float* __restrict__ x, long n, float a) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i < n) x[i] *= a;
 }
 
 // upstream gradient rows: G[r, s] = dstate[row_t, row_env, s]
@@ -1582,22 +1488,6 @@ static BwdScratch carve_bwd(void* ws, const cirs_tracker_cfg* cfg, long R) {
 
 }  // namespace cirs
 
-namespace cirs {
-static inline void launch_ln_bwd_dw(DwList& list, const float* dOut, const float* xhat, const float* rstd, const float* g, int R, float* dY,
-                                    float* dW, float* db, float* partial, hipStream_t s) {
-    const int slabs = dwg_slabs(R);
-    int rows_per_slab = (R + slabs - 1) / slabs;
-    rows_per_slab = (rows_per_slab + 15) & ~15;
-    DwListJob& jb = list.j[list.n++];
-    jb.O = tD; jb.K = tD; jb.part_off = list.part_floats; jb.diag = 1; jb.dW = dW; jb.db = db;
-    list.part_floats += slabs * tD * (tD + 1);
-    list.total_out += tD * (tD + 1);
-    const DwGemmArgs da{dOut, tD, xhat, tD, R, tD, tD, rows_per_slab, partial + jb.part_off};
-    const int n_ln = (int)cdiv((long)R * tD, 64L);
-    hipLaunchKernelGGL(ln_bwd_dw_kernel, dim3(n_ln + slabs), dim3(64), 0, s, dOut, xhat, rstd, g, R, dY, n_ln, da, 1);
-}
-}  // namespace cirs
-
 #ifdef CIRS_TBWD_PROF
 extern "C" int cirs_debug_tbwd_wg(unsigned long long* out_host) {
     return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(cirs::g_tbwd_wg), 2048 * 3 * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
@@ -1624,16 +1514,14 @@ __global__ __launch_bounds__(256) void prefix_last_rows_kernel(const float* __re
     if (c == 0) { env_c[e] = r >= 0 ? row_env[r] : e; t_c[e] = r >= 0 ? row_t[r] : 0; }
 }
 // cirs_tracker_prefix_states: state of the LAST row of every env that has rows = decoder(H_last[row]); one wavefront per env, lane j < S owns
-// output j (fma chain over the 32 features in ascending order)
-// compact != 0: H holds one row per env (the last layer ran on the envs' last rows only, below)
-__global__ __launch_bounds__(256) void prefix_decoder_kernel(const float* __restrict__ H, const int32_t* __restrict__ offsets, const int32_t* __restrict__ lens,
-                                                             int B, int S, const float* __restrict__ dec_w, const float* __restrict__ dec_b,
-                                                             float* __restrict__ out, long out_stride, int compact) {
+// output j (fma chain over the 32 features in ascending order).  H holds one row per env (the last layer ran on the envs' last rows only, below)
+__global__ __launch_bounds__(256) void prefix_decoder_kernel(const float* __restrict__ H, const int32_t* __restrict__ lens, int B, int S,
+                                                             const float* __restrict__ dec_w, const float* __restrict__ dec_b,
+                                                             float* __restrict__ out, long out_stride) {
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6), j = threadIdx.x & 63;
     if (e >= B || j >= S) return;
-    const int n = lens[e];
-    if (n <= 0) return;
-    const float* h = H + (size_t)(compact ? e : offsets[e] + n - 1) * tD;
+    if (lens[e] <= 0) return;
+    const float* h = H + (size_t)e * tD;
     float acc = dec_b[j];
 #pragma unroll
     for (int k = 0; k < tD; ++k) acc = __builtin_fmaf(h[k], dec_w[(size_t)j * tD + k], acc);
@@ -2214,7 +2102,7 @@ extern "C" int64_t cirs_tracker_backward_workspace_bytes(const cirs_tracker_cfg*
 // Few workgroups (the 64-env shape: 60 row tiles, 64 episodes): an LDS request of more than half a CU's 160 KB keeps them on DIFFERENT CUs -- the dispatcher otherwise
 // stacks several one-wavefront workgroups on a CU, where they share its load path while most CUs idle (round 6: what the step kernel gained from the same change).
 static inline size_t spread_dyn_lds(long n_blocks, size_t static_bytes, size_t dyn_bytes) {
-    if (n_blocks > cirs::device_cu_count() || getenv("CIRS_NO_SPREAD")) return dyn_bytes;
+    if (n_blocks > cirs::device_cu_count()) return dyn_bytes;
     const size_t want = 81 * 1024;
     return static_bytes + dyn_bytes >= want ? dyn_bytes : want - static_bytes;
 }
@@ -2251,7 +2139,6 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
     auto g1 = [&](long n) { return dim3(cdiv(n, 256)); };
 
     DwList dwl{};
-#define DW(dY, X, O, K, dWp, dbp) launch_dw_partial(dwl, dY, O, X, K, R, O, K, dWp, dbp, 0, sc.partial, s)
 #define ATT_DISPATCH_SH(KERNEL, SHMEM, ...)                                                               \
     do {                                                                                                  \
         switch (NH) {                                                                                     \
@@ -2294,7 +2181,7 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
         dc.seed = cfg->dropout_seed; dc.env_base = cfg->drop_env_base;
     }
     // ---------------- prefix states, one launch: one wavefront per env (prefixes of at most 32 rows) ----------------
-    if (state_out && ep && L <= 32 && S <= 64 && !getenv("CIRS_TRACKER_ROWS_UNFUSED") && !getenv("CIRS_TRACKER_PREFIX_FULL") && !getenv("CIRS_TRACKER_PREFIX_LAUNCHES")) {
+    if (state_out && ep && L <= 32 && S <= 64 && !getenv("CIRS_TRACKER_PREFIX_LAUNCHES")) {
         PrefixEnvArgs pa{};
         pa.x_hist = st->x_hist; pa.pe = w->pe; pa.row_env = row_env; pa.row_t = row_t; pa.offsets = offsets; pa.lens = lens;
         for (int l = 0; l < nl; ++l) pa.layer[l] = w->layer[l];
@@ -2320,22 +2207,13 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
         CIRS_CHECK_LAUNCH("prefix_env_kernel");
         return CIRS_OK;
     }
-    // ---------------- forward recompute ----------------
-    // fused row chains (embed + in_proj; out_proj .. LayerNorm2 + the next in_proj) unless CIRS_TRACKER_ROWS_UNFUSED asks for the
-    // per-op launches (kept for A/B runs and for alignment-free inputs)
-    const bool fused_rows = !getenv("CIRS_TRACKER_ROWS_UNFUSED");
-    if (fused_rows) {
-        const dim3 gt(cdiv(R, 32));
-        if (dc.on) CIRS_LAUNCH_SPREAD(embed_inproj<true>, gt.x, 0, 0, s, st->x_hist, w->pe, row_env, row_t, R, L, w->layer[0].in_proj_w,
-                                      w->layer[0].in_proj_b, sc.H[0], sc.QKV[0], dc);
-        else CIRS_LAUNCH_SPREAD(embed_inproj<false>, gt.x, 0, 0, s, st->x_hist, w->pe, row_env, row_t, R, L, w->layer[0].in_proj_w,
-                                w->layer[0].in_proj_b, sc.H[0], sc.QKV[0], dc);
-    } else {
-        hipLaunchKernelGGL(embed_rows, g1((long)R * tD), dim3(256), 0, s, st->x_hist, w->pe, row_env, row_t, R, L, sc.H[0], dc);
-    }
-    bool last_compact = false;
+    // ---------------- forward recompute: fused row chains (embed + in_proj; out_proj .. LayerNorm2 + the next in_proj) ----------------
+    if (dc.on) CIRS_LAUNCH_SPREAD(embed_inproj<true>, cdiv(R, 32), 0, 0, s, st->x_hist, w->pe, row_env, row_t, R, L, w->layer[0].in_proj_w,
+                                  w->layer[0].in_proj_b, sc.H[0], sc.QKV[0], dc);
+    else CIRS_LAUNCH_SPREAD(embed_inproj<false>, cdiv(R, 32), 0, 0, s, st->x_hist, w->pe, row_env, row_t, R, L, w->layer[0].in_proj_w,
+                            w->layer[0].in_proj_b, sc.H[0], sc.QKV[0], dc);
     // last-row pass (dstate_last): the top layer on ONE row per env -- its attention for the one query, its row chain on B compact rows
-    const bool top_last = dstate_last && fused_rows && ep && nl >= 2 && !getenv("CIRS_TRACKER_LAST_FULL");
+    const bool top_last = dstate_last && ep && nl >= 2 && !getenv("CIRS_TRACKER_LAST_FULL");
     float *dY1c = sc.LC, *att_stats = sc.LC + (size_t)B * tD;
     int32_t *env_c = reinterpret_cast<int32_t*>(att_stats + (size_t)B * 16), *t_c = env_c + B;
 #define ATT_LAST1(KERNEL, N, ...)                                                                                        \
@@ -2354,7 +2232,6 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
     } while (0)
     for (int l = 0; l < nl; ++l) {
         const cirs_tracker_layer& y = w->layer[l];
-        if (!fused_rows) launch_rows_gemm(true, sc.H[l], tD, y.in_proj_w, tD, y.in_proj_b, R, tD, 96, 0, nullptr, 0, sc.QKV[l], 96, s);
         if (top_last && l == nl - 1) {
             float* Hc = sc.T1;
             ATT_LAST(attn_last_fwd, (const float*)sc.QKV[l], (const float*)sc.H[l], row_env, row_t, offsets, lens, B, L, sc.ATT[l], Hc, att_stats, env_c, t_c,
@@ -2368,7 +2245,7 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
         // (dropout: the forward launch leaves its keep bits in the probability scratch of the row-wise path, unused here, for the backward launch -- not in the prefix pass)
         if (ep) ATT_EP(attn_fwd_ep, false, (const float*)sc.QKV[l], offsets, lens, L, sc.ATT[l], dc, l, (dc.on && !state_out) ? reinterpret_cast<uint32_t*>(sc.P[l]) : (uint32_t*)nullptr);
         else ATT_DISPATCH_SH(attn_fwd, (size_t)4 * NH * L * sizeof(float), sc.QKV[l], row_env, row_t, offsets, R, L, sc.P[l], sc.ATT[l], dc, l, sc.PM[l]);
-        if (fused_rows && state_out && l == nl - 1 && !getenv("CIRS_TRACKER_PREFIX_FULL")) {      // prefix states: the last layer's row chain on the envs' last rows only
+        if (state_out && l == nl - 1) {      // prefix states: the last layer's row chain on the envs' last rows only
             static_assert(tD == 32, "prefix_last_rows_kernel maps 32 columns to 32 threads");
             float *ATTc = sc.T0, *Hc = sc.T1;
             int32_t *env_c = reinterpret_cast<int32_t*>(sc.T2), *t_c = env_c + B;
@@ -2378,47 +2255,34 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
                             env_c, t_c, B, l};
             if (dc.on) CIRS_LAUNCH_SPREAD(layer_rows_fwd<true>, cdiv(B, 32), 40 * 1024, 0, s, fa, dc);
             else CIRS_LAUNCH_SPREAD(layer_rows_fwd<false>, cdiv(B, 32), 40 * 1024, 0, s, fa, dc);
-            last_compact = true;
             continue;
         }
-        if (fused_rows) {
-            LayerFwdArgs fa{sc.ATT[l], sc.H[l], y, l + 1 < nl ? w->layer[l + 1].in_proj_w : nullptr, l + 1 < nl ? w->layer[l + 1].in_proj_b : nullptr,
-                            sc.XH1[l], sc.RS1[l], sc.H1N[l], sc.FF1[l], sc.XH2[l], sc.RS2[l], sc.H[l + 1], l + 1 < nl ? sc.QKV[l + 1] : nullptr,
-                            row_env, row_t, R, l};
-            if (dc.on) CIRS_LAUNCH_SPREAD(layer_rows_fwd<true>, cdiv(R, 32), 40 * 1024, 0, s, fa, dc);
-            else CIRS_LAUNCH_SPREAD(layer_rows_fwd<false>, cdiv(R, 32), 40 * 1024, 0, s, fa, dc);
-            continue;
-        }
-        launch_rows_gemm(true, sc.ATT[l], tD, y.out_proj_w, tD, y.out_proj_b, R, tD, tD, 0, nullptr, 0, sc.T0, tD, s);
-        hipLaunchKernelGGL(ln_fwd, g1((long)R * tD), dim3(256), 0, s, sc.H[l], sc.T0, y.norm1_w, y.norm1_b, R, sc.XH1[l], sc.RS1[l], sc.H1N[l],
-                           dc, row_env, row_t, l, (int)CIRS_DROP_RES1);
-        launch_rows_gemm(true, sc.H1N[l], tD, y.lin1_w, tD, y.lin1_b, R, tD, tH, 1, nullptr, 0, sc.FF1[l], tH, s);
-        if (dc.on)   // FF1 holds relu(.) * mask / (1 - p): the input of lin2, the relu-and-dropout gate of the backward
-            hipLaunchKernelGGL(drop_rows, g1((long)R * tH), dim3(256), 0, s, dc, (const float*)sc.FF1[l], row_env, row_t, R, tH, l, (int)CIRS_DROP_FF, sc.FF1[l]);
-        launch_rows_gemm(true, sc.FF1[l], tH, y.lin2_w, tH, y.lin2_b, R, tH, tD, 0, nullptr, 0, sc.T0, tD, s);
-        hipLaunchKernelGGL(ln_fwd, g1((long)R * tD), dim3(256), 0, s, sc.H1N[l], sc.T0, y.norm2_w, y.norm2_b, R, sc.XH2[l], sc.RS2[l], sc.H[l + 1],
-                           dc, row_env, row_t, l, (int)CIRS_DROP_RES2);
+        LayerFwdArgs fa{sc.ATT[l], sc.H[l], y, l + 1 < nl ? w->layer[l + 1].in_proj_w : nullptr, l + 1 < nl ? w->layer[l + 1].in_proj_b : nullptr,
+                        sc.XH1[l], sc.RS1[l], sc.H1N[l], sc.FF1[l], sc.XH2[l], sc.RS2[l], sc.H[l + 1], l + 1 < nl ? sc.QKV[l + 1] : nullptr,
+                        row_env, row_t, R, l};
+        if (dc.on) CIRS_LAUNCH_SPREAD(layer_rows_fwd<true>, cdiv(R, 32), 40 * 1024, 0, s, fa, dc);
+        else CIRS_LAUNCH_SPREAD(layer_rows_fwd<false>, cdiv(R, 32), 40 * 1024, 0, s, fa, dc);
     }
     CIRS_CHECK_LAUNCH("tracker forward recompute");
     if (state_out) {
-        hipLaunchKernelGGL(prefix_decoder_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, (const float*)sc.H[nl], offsets, lens, B, S, w->dec_w, w->dec_b,
-                           state_out, (long)state_stride, last_compact ? 1 : 0);
+        hipLaunchKernelGGL(prefix_decoder_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, (const float*)sc.H[nl], lens, B, S, w->dec_w, w->dec_b,
+                           state_out, (long)state_stride);
         CIRS_CHECK_LAUNCH("prefix_decoder_kernel");
         return CIRS_OK;
     }
     // ---------------- backward ----------------
     float* dH = sc.T0;  // gradient w.r.t. the current layer output
-    // (each weight-gradient problem rides in the launch of the row GEMM that consumes the same dY: DW_ROWS)
-#define DW_ROWS(X2, O, K, dWp, dbp, ...) launch_rows_gemm_dw(dwl, X2, K, O, K, dWp, dbp, sc.partial, __VA_ARGS__, s)
     if (top_last) {
         hipLaunchKernelGGL(dstate_last_rows, g1((long)B * S), dim3(256), 0, s, dstate_last, lens, B, S, sc.G);
         launch_rows_gemm(false, sc.G, S, w->dec_w, tD, nullptr, B, S, tD, 0, nullptr, 0, dH, tD, s);      // (the decoder's dW problem joins the top layer's batch)
     } else {
         if (dstate_last) hipLaunchKernelGGL(dstate_last_full, g1((long)R * S), dim3(256), 0, s, dstate_last, row_env, offsets, lens, R, S, sc.G);
         else hipLaunchKernelGGL(gather_dstate, g1((long)R * S), dim3(256), 0, s, dstate, row_env, row_t, R, S, B, sc.G);
-        DW_ROWS(sc.H[nl], S, tD, grads->dec_w, grads->dec_b, false, sc.G, S, w->dec_w, tD, nullptr, R, S, tD, 0, nullptr, 0, dH, tD);
+        // (the decoder's weight-gradient problem rides in the launch of the row GEMM that consumes the same dY)
+        launch_rows_gemm_dw(dwl, sc.H[nl], tD, S, tD, grads->dec_w, grads->dec_b, sc.partial, false, sc.G, S, w->dec_w, tD, nullptr, R, S, tD, 0, nullptr, 0,
+                            dH, tD, s);
     }
-    for (int l = nl - 1; l >= 0 && fused_rows; --l) {
+    for (int l = nl - 1; l >= 0; --l) {
         // fused row chain (layer_rows_bwd) + one batched launch of the layer's weight-gradient problems + the attention backward
         const cirs_tracker_layer& y = w->layer[l];
         const cirs_tracker_layer_grads& gy = grads->layer[l];
@@ -2463,100 +2327,44 @@ static int tracker_rows_impl(const cirs_tracker_cfg* cfg, const cirs_tracker_wei
             ATT_DISPATCH(attn_bwd_kv, sc.QKV[l], dc.on ? sc.PM[l] : sc.P[l], sc.dS, dATT, row_env, row_t, offsets, lens, R, L, sc.dQKV);
         }
     }
-    if (fused_rows) {   // layer 0's in_proj backward (+ the positional-encoding dropout): the pre stage alone; its dW problem joins the slot problems below
+    {   // layer 0's in_proj backward (+ the positional-encoding dropout): the pre stage alone; its dW problem joins the slot problems below
         LayerBwdArgs ba{};
         ba.dY1p = sc.T2; ba.dQKVp = sc.dQKV; ba.winp = w->layer[0].in_proj_w; ba.dHout = sc.T0; ba.only_pre = 1;
         ba.row_env = row_env; ba.row_t = row_t; ba.R = R;
         if (dc.on) CIRS_LAUNCH_SPREAD(layer_rows_bwd<true>, cdiv(R, 32), 40 * 1024, 0, s, ba, dc);
         else CIRS_LAUNCH_SPREAD(layer_rows_bwd<false>, cdiv(R, 32), 40 * 1024, 0, s, ba, dc);
-        dH = sc.T0;
-    }
-    for (int l = nl - 1; l >= 0 && !fused_rows; --l) {
-        const cirs_tracker_layer& y = w->layer[l];
-        const cirs_tracker_layer_grads& gy = grads->layer[l];
-        // LN2
-        float* dY2 = sc.T1;
-        launch_ln_bwd_dw(dwl, dH, sc.XH2[l], sc.RS2[l], y.norm2_w, R, dY2, gy.norm2_w, gy.norm2_b, sc.partial, s);   // + diag(dH^T Xhat), column sums
-        // FF: with dropout the lin2 branch sees dY2 * mask2 / (1 - p) (the residual keeps dY2) and the gate of the hidden layer is
-        // relu' * mask_ff / (1 - p): FF1 > 0 already encodes "relu active and kept", the scale is applied to dFF1
-        const float* dB2 = dY2;
-        if (dc.on) {
-            hipLaunchKernelGGL(drop_rows, g1((long)R * tD), dim3(256), 0, s, dc, (const float*)dY2, row_env, row_t, R, tD, l, (int)CIRS_DROP_RES2, sc.T3);
-            dB2 = sc.T3;
-        }
-        DW_ROWS(sc.FF1[l], tD, tH, gy.lin2_w, gy.lin2_b, false, dB2, tD, y.lin2_w, tH, nullptr, R, tD, tH, 0, sc.FF1[l], 0, sc.dFF1, tH);
-        if (dc.on) hipLaunchKernelGGL(scale_rows, g1((long)R * tH), dim3(256), 0, s, sc.dFF1, (long)R * tH, dc.inv);
-        // d H1N = dY2 (residual) + dFF1 * W1
-        DW_ROWS(sc.H1N[l], tH, tD, gy.lin1_w, gy.lin1_b, false, sc.dFF1, tH, y.lin1_w, tD, nullptr, R, tH, tD, 0, nullptr, 1, dY2, tD);
-        // LN1
-        float* dY1 = sc.T2;
-        launch_ln_bwd_dw(dwl, dY2, sc.XH1[l], sc.RS1[l], y.norm1_w, R, dY1, gy.norm1_w, gy.norm1_b, sc.partial, s);
-        // out_proj (its branch sees dY1 * mask1 / (1 - p); the residual keeps dY1)
-        const float* dB1 = dY1;
-        if (dc.on) {
-            hipLaunchKernelGGL(drop_rows, g1((long)R * tD), dim3(256), 0, s, dc, (const float*)dY1, row_env, row_t, R, tD, l, (int)CIRS_DROP_RES1, sc.T3);
-            dB1 = sc.T3;
-        }
-        float* dATT = sc.T1;
-        DW_ROWS(sc.ATT[l], tD, tD, gy.out_proj_w, gy.out_proj_b, false, dB1, tD, y.out_proj_w, tD, nullptr, R, tD, tD, 0, nullptr, 0, dATT, tD);
-        // attention (dropout: V is weighted by the masked probabilities PM; the softmax backward runs on P)
-        if (ep) {
-            ATT_EP(attn_bwd_ep, true, (const float*)sc.QKV[l], (const float*)dATT, offsets, lens, L, sc.dQKV, dc, l, dc.on ? reinterpret_cast<const uint32_t*>(sc.P[l]) : (const uint32_t*)nullptr);
-        } else {
-            ATT_DISPATCH_SH(attn_bwd_q, (size_t)4 * NH * L * sizeof(float), sc.QKV[l], sc.P[l], dATT, row_env, row_t, offsets, R, L, sc.dS, sc.dQKV,
-                            (const float*)sc.PM[l], dc.inv);
-            ATT_DISPATCH(attn_bwd_kv, sc.QKV[l], dc.on ? sc.PM[l] : sc.P[l], sc.dS, dATT, row_env, row_t, offsets, lens, R, L, sc.dQKV);
-        }
-        // in_proj
-        // d H_l = dY1 (residual) + dQKV * W_in
-        DW_ROWS(sc.H[l], 96, tD, gy.in_proj_w, gy.in_proj_b, false, sc.dQKV, 96, y.in_proj_w, tD, nullptr, R, 96, tD, 0, nullptr, 1, dY1, tD);
-        dH = dY1;
-        if (l > 0) {  // keep dH in T0 for the next iteration (T2 is reused as dY1)
-            CIRS_HIP(hipMemcpyAsync(sc.T0, dY1, sizeof(float) * (size_t)R * tD, hipMemcpyDeviceToDevice, s));
-            dH = sc.T0;
-        }
     }
     CIRS_CHECK_LAUNCH("tracker backward layers");
-    if (dc.on && !fused_rows)   // gradient through the PositionalEncoding dropout
-        hipLaunchKernelGGL(drop_rows, g1((long)R * tD), dim3(256), 0, s, dc, (const float*)dH, row_env, row_t, R, tD, 0, (int)CIRS_DROP_POS, dH);
     // input slots + embeddings (forward activations are no longer needed: reuse their scratch)
     float* DU = sc.T1;
     float* EU = sc.H[nl];
-    float* DPRE = fused_rows ? sc.H1N[0] : sc.H[0];   // (fused: H[0] is still an operand of layer 0's in_proj weight-gradient problem)
+    float* DPRE = sc.H1N[0];               // (H[0] is still an operand of layer 0's in_proj weight-gradient problem)
     float* CU = sc.QKV[0];                 // [R,32] per-row contribution to Emb_user
     float* CI = sc.QKV[0] + (size_t)R * tD; // [R,32] per-row contribution to Emb_item  (QKV is [R,96])
     int32_t* key_user = (int32_t*)sc.RS1[0];
     int32_t* key_item = (int32_t*)sc.RS2[0];
-    const bool merged = fused_rows && B <= R;      // one sort for both tables: the per-env user rows sit behind the item rows (third part of QKV[0])
+    const bool merged = B <= R;      // one sort for both tables: the per-env user rows sit behind the item rows (third part of QKV[0])
     const int slot_rpw = R >= (1 << 17) ? 8 : 1;
     hipLaunchKernelGGL(slot_bwd, dim3(cdiv(R, 4 * slot_rpw)), dim3(256), 0, s, *w, dH, users, act, rew, row_env, row_t, R, B, DU, EU, DPRE,
                        sc.GIN, CU, CI, key_user, key_item, merged ? CI + (size_t)R * tD : nullptr, slot_rpw);
     if (merged) {
         if (int rc = emb_scatter_merged(key_item, users, lens, CI, R, B, cfg->n_items, cfg->n_users, grads->emb_item, grads->emb_user, sc.sort,
                                         emb_sort_bytes(R + B), s)) return rc;
-    } else {
-    {   // user embeddings: one pair per env (T0 and T2 = [R, 32] each, R >= B, are free after slot_bwd)
+    } else {   // user embeddings: one pair per env (T0 and T2 = [R, 32] each, R >= B, are free after slot_bwd)
         int32_t* keys_c = (int32_t*)sc.T0;
         float* contrib_c = sc.T2;
         CIRS_HIP(hipMemsetAsync(keys_c, 0xFF, sizeof(int32_t) * (size_t)B, s));   // -1: env without rows in this call
         hipLaunchKernelGGL(compact_user_rows, dim3(cdiv(R, 8)), dim3(256), 0, s, row_env, row_t, users, (const float*)CU, R, keys_c, contrib_c);
         if (int rc = emb_scatter_sorted(keys_c, contrib_c, B, cfg->n_users, grads->emb_user, sc.sort, emb_sort_bytes(R), s)) return rc;
+        if (int rc = emb_scatter_sorted(key_item, CI, R, cfg->n_items, grads->emb_item, sc.sort, emb_sort_bytes(R), s)) return rc;
     }
-    if (int rc = emb_scatter_sorted(key_item, CI, R, cfg->n_items, grads->emb_item, sc.sort, emb_sort_bytes(R), s)) return rc;
-    }
-    if (fused_rows) {
-        DwBatch bt{};
-        dw_batch_add(bt, dwl, sc.dQKV, 96, sc.H[0], tD, R, 96, tD, grads->layer[0].in_proj_w, grads->layer[0].in_proj_b, 0, sc.partial);
-        dw_batch_add(bt, dwl, DU, tD, EU, tD, R, tD, tD, grads->ffn_user_w, grads->ffn_user_b, 0, sc.partial);
-        dw_batch_add(bt, dwl, DPRE, tD, sc.GIN, tD + 1, R, tD, tD + 1, grads->gate_w, grads->gate_b, 0, sc.partial);
-        dw_batch_launch(bt, R, s);
-    } else {
-        DW(DU, EU, tD, tD, grads->ffn_user_w, grads->ffn_user_b);
-        DW(DPRE, sc.GIN, tD, tD + 1, grads->gate_w, grads->gate_b);
-    }
+    DwBatch bt{};
+    dw_batch_add(bt, dwl, sc.dQKV, 96, sc.H[0], tD, R, 96, tD, grads->layer[0].in_proj_w, grads->layer[0].in_proj_b, 0, sc.partial);
+    dw_batch_add(bt, dwl, DU, tD, EU, tD, R, tD, tD, grads->ffn_user_w, grads->ffn_user_b, 0, sc.partial);
+    dw_batch_add(bt, dwl, DPRE, tD, sc.GIN, tD + 1, R, tD, tD + 1, grads->gate_w, grads->gate_b, 0, sc.partial);
+    dw_batch_launch(bt, R, s);
     launch_dw_list_final(dwl, R, sc.partial, s);   // every weight / bias gradient of the pass: slab sums in one launch
     CIRS_CHECK_LAUNCH("tracker backward slots");
-#undef DW
 #undef ATT_LAST
 #undef ATT_LAST1
 #undef ATT_DISPATCH
