@@ -126,6 +126,37 @@ class VtbState(C.Structure):     # cirs_vtb_state
     _fields_ = [(k, C.c_void_p) for k in ("task_user", "sim_user", "turn", "event", "prev_reward", "cum_reward", "lst_action", "hist")]
 
 
+VTB_RO_MAX_LAYERS, VTB_RO_MAX_HIDDEN = 4, 3
+
+
+class VtbRolloutCfg(C.Structure):    # cirs_vtb_rollout_cfg
+    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "force_length", "dim_model", "nhead", "d_hid", "nlayers", "dim_state", "max_len",
+                                         "n_hidden")] + [("hidden", C.c_int32 * VTB_RO_MAX_HIDDEN)] + \
+        [(k, C.c_int32) for k in ("unbounded", "conditioned_sigma", "bound_method", "action_scaling")] + \
+        [("max_action", C.c_float), ("dropout_p", C.c_float), ("drop_env_base", C.c_int32), ("dropout_seed", C.c_uint64), ("env_seed", C.c_uint64)]
+
+
+VTB_LAYER_FIELDS = ("in_w", "in_b", "out_w", "out_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")
+
+
+class VtbPolicyLayer(C.Structure):   # cirs_vtb_policy_layer
+    _fields_ = [(k, C.c_void_p) for k in VTB_LAYER_FIELDS]
+
+
+class VtbPolicyWeights(C.Structure):  # cirs_vtb_policy_weights
+    _fields_ = [(k, C.c_void_p) for k in ("user_w", "user_b", "gate_w", "gate_b", "pe")] + [("layer", VtbPolicyLayer * VTB_RO_MAX_LAYERS)] + \
+        [("dec_w", C.c_void_p), ("dec_b", C.c_void_p), ("trunk_w", C.c_void_p * VTB_RO_MAX_HIDDEN), ("trunk_b", C.c_void_p * VTB_RO_MAX_HIDDEN)] + \
+        [(k, C.c_void_p) for k in ("mu_w", "mu_b", "sigma_w", "sigma_b", "sigma_param", "act_low", "act_high")]
+
+
+VTB_TRAJ_FIELDS = ("state", "act", "act_mapped", "obs0", "obs", "rew", "done", "ctr", "len", "kcache", "vcache", "lists", "counts", "act_buf",
+                   "step_obs", "step_rew", "step_ctr", "step_done")
+
+
+class VtbTraj(C.Structure):          # cirs_vtb_traj
+    _fields_ = [(k, C.c_void_p) for k in VTB_TRAJ_FIELDS]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -140,6 +171,11 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P]),
     "cirs_vtb_noise": (C.c_int, [C.c_uint64, _P, _P, C.c_int32, _P, _P]),
     "cirs_vtb_mmoe_forward": (C.c_int, [C.POINTER(VtbCfg), C.POINTER(VtbWeights), _P, C.c_int32, _P, _P]),
+    "cirs_vtb_rollout_collect": (C.c_int, [C.POINTER(VtbRolloutCfg), C.POINTER(VtbPolicyWeights), C.POINTER(VtbCfg), C.POINTER(VtbWeights),
+                                           C.POINTER(VtbState), C.POINTER(VtbTraj), C.c_uint64, C.c_uint32, _P]),
+    "cirs_vtb_rollout_noise": (C.c_int, [C.c_uint64, C.c_uint32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
+    "cirs_vtb_rollout_masks": (C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         _P, _P]),
     "cirs_tracker_init": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,
                                     C.c_int32, _P, C.c_int64, _P]),
     "cirs_tracker_step": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,

@@ -38,15 +38,22 @@ def result_from_trajectory(traj, lengths: np.ndarray, offsets: np.ndarray) -> Di
 
 
 class Collector:
-    def __new__(cls, policy=None, env=None, *args, **kwargs):
-        """Host vector envs (VirtualTB-v0: BASELINE configs[0], CPU plumbing) are collected by the per-step loop of core.host_rl."""
+    def __new__(cls, policy=None, env=None, *args, rollout=None, **kwargs):
+        """Host vector envs (VirtualTB-v0: BASELINE configs[0], CPU plumbing) are collected by the per-step loop of core.host_rl;
+        rollout="device" collects a VirtualTB-v0 vector env built with device= on the GPU instead (core.vtb_collector)."""
+        if cls is Collector and rollout is not None:
+            if rollout != "device":
+                raise ValueError(f"rollout must be None or 'device', got {rollout!r}")
+            from core.vtb_collector import DeviceVtbCollector, check_device_vtb
+            check_device_vtb(policy, env, kwargs.get("preprocess_fn", args[1] if len(args) > 1 else None))
+            return DeviceVtbCollector(policy, env, *args, **kwargs)
         if cls is Collector and getattr(env, "host_mode", False):
             from core.host_rl import HostCollector
             return HostCollector(policy, env, *args, **kwargs)
         return super().__new__(cls)
 
     def __init__(self, policy, env, buffer: Optional[VectorReplayBuffer] = None, preprocess_fn: Optional[Callable[..., Any]] = None,
-                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0):
+                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0, rollout=None):
         assert hasattr(env, "__len__"), "pass a tianshou.env.DummyVectorEnv"
         assert preprocess_fn is not None and hasattr(preprocess_fn, "__self__"), \
             "preprocess_fn must be StateTrackerTransformer.build_state (CIRS-RL-kuaishou.py:291)"

@@ -1,0 +1,418 @@
+// vtb_rollout.hip -- the policy side of the VirtualTaobao PPO rollout (CIRS-RL-taobao.py) on gfx950.
+//
+// Per vector step t, vtb_policy_step_kernel runs one 64-lane wavefront per env of the previous step's active list:
+//   record      the env step t-1 of this env (obs, reward, done, CTR) into the trajectory; force_length overrides done
+//   input slot  t = 0: x = ffn_user(obs0[:88]); t > 0: x = sigmoid(fnn_gate([r, a])) * a, a = the 27 action columns of obs
+//               (core/host_rl.py HostStateTracker.build_state, same order of operations)
+//   decode      h = x * sqrt(D) + pe[t]; nlayers post-norm TransformerEncoderLayers with per-layer K/V caches (causal attention of
+//               position t over 0..t), decoder -> state s_t (traj.state[t])
+//   actor       envs that are not done: Net trunk (ReLU), mu = max_action * tanh(head) (or the head when unbounded), sigma = exp(param)
+//               or exp(clamp(head, -20, 2)); act = mu + sigma * z, z ~ N(0, 1) (Box-Muller on Philox, see gauss_z); the raw act goes
+//               to traj.act, the mapped action (HostPPOPolicy.map_action: clip / tanh, then scaled to the box) to the env's action
+//               buffer at a compacted position of the next active list (one atomic per env)
+// and then vtb_step_kernel (csrc/virtualtb.hip) steps the envs of that list.  The rows of an env do not depend on its position in the
+// list, so the order the atomics produce changes no result.
+//
+// Dropout (DROP): the production mode of csrc/rng.h, position-keyed masks at the five sites of tracker.hip with its element
+// convention (ATTN: key_pos * nhead + head); a cached position keeps its masks for the rest of the episode.
+// fp32 throughout; matrices are [in][out] so that the lanes of a mat-vec read consecutive floats; the weights stay in L2.
+#include "common.h"
+#include "rng.h"
+
+#define CIRS_RNG_STREAM_GAUSS 0x47415553u /* 'GAUS' */
+
+namespace cirs {
+namespace {
+
+constexpr int kWaves = 4;
+constexpr int kMaxD = 64, kMaxHid = 256, kMaxW = 128, kMaxAttn = 2048;
+constexpr int kA = CIRS_VTB_ACTION_DIM, kU = CIRS_VTB_USER_DIM, kObs = kA + 3, kObs0 = kU + 3;
+// per-wave LDS: xs, qs, ks, vs, att, h1 [64 each] | ff [256] | hb, hc [128 each] | head norms [64] | scores [nhead * max_len]
+constexpr int kFixed = 6 * kMaxD + kMaxHid + 2 * kMaxW + kMaxD;
+
+// ---- Gaussian noise ---------------------------------------------------------------------------------------------------
+// sin / cos of x in [0, pi/2): Taylor polynomials in x^2 (truncation < 6e-8 at pi/2), fixed fmaf order
+__host__ __device__ __forceinline__ float det_sin_q(float x) {
+    const float z = x * x;
+    float p = -2.5052108385e-8f;
+    p = __builtin_fmaf(p, z, 2.7557319224e-6f);
+    p = __builtin_fmaf(p, z, -1.9841269841e-4f);
+    p = __builtin_fmaf(p, z, 8.3333333333e-3f);
+    p = __builtin_fmaf(p, z, -1.6666666667e-1f);
+    p = __builtin_fmaf(p, z, 1.0f);
+    return x * p;
+}
+__host__ __device__ __forceinline__ float det_cos_q(float x) {
+    const float z = x * x;
+    float p = 2.0876756988e-9f;
+    p = __builtin_fmaf(p, z, -2.7557319224e-7f);
+    p = __builtin_fmaf(p, z, 2.4801587302e-5f);
+    p = __builtin_fmaf(p, z, -1.3888888889e-3f);
+    p = __builtin_fmaf(p, z, 4.1666666667e-2f);
+    p = __builtin_fmaf(p, z, -0.5f);
+    p = __builtin_fmaf(p, z, 1.0f);
+    return p;
+}
+
+// z of (env, t, dim): see include/cirs_hip.h cirs_vtb_rollout_noise
+__device__ __forceinline__ float gauss_z(uint64_t seed, uint32_t collect_id, uint32_t env, uint32_t t, uint32_t dim) {
+    const u32x4 r = philox4x32_10(dim >> 2, env, t, collect_id, (uint32_t)seed ^ CIRS_RNG_STREAM_GAUSS, (uint32_t)(seed >> 32));
+    const bool hi = (dim & 2u) != 0;
+    const float u1 = u01_from_bits(hi ? r.z : r.x), u2 = u01_from_bits(hi ? r.w : r.y);
+    const float rad = sqrtf(-2.0f * det_logf(u1));
+    const float v = u2 * 4.0f;                     // exact
+    const int q = (int)v;                          // quadrant 0..3
+    const float x = (v - (float)q) * 1.5707963267948966f;
+    const float s = det_sin_q(x), c = det_cos_q(x);
+    const float cs = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;   // cos(2 pi u2)
+    const float sn = q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c;   // sin(2 pi u2)
+    return rad * ((dim & 1u) ? sn : cs);
+}
+
+// ---- wave helpers -------------------------------------------------------------------------------------------------------
+// b[o] + sum_k W[k][o] x[k] for the output o of this lane (o < O is the caller's business)
+__device__ __forceinline__ float mv(const float* __restrict__ W, const float* __restrict__ b, const float* x, int K, int O, int o) {
+    float acc = b ? b[o] : 0.f;
+#pragma unroll 8
+    for (int k = 0; k < K; ++k) acc = __builtin_fmaf(W[(size_t)k * O + o], x[k], acc);
+    return acc;
+}
+
+// LayerNorm over the D values of lanes 0..D-1 (torch: biased variance, eps 1e-5); other lanes get 0
+__device__ __forceinline__ float layer_norm(float v, int lane, int D, const float* __restrict__ w, const float* __restrict__ b) {
+    const bool on = lane < D;
+    const float mean = wave_sum_f32(on ? v : 0.f) / (float)D;
+    const float d = v - mean;
+    const float var = wave_sum_f32(on ? d * d : 0.f) / (float)D;
+    return on ? d / sqrtf(var + 1e-5f) * w[lane] + b[lane] : 0.f;
+}
+
+__device__ __forceinline__ void wbar() { __builtin_amdgcn_wave_barrier(); }
+
+template <bool DROP>
+__global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w, cirs_vtb_traj tr,
+                                                                       int t, int steps, uint64_t seed, uint32_t collect_id) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j = blockIdx.x * kWaves + wv;
+    const int B = cfg.n_env;
+    if (j >= B) return;
+    const int e = t == 0 ? j : tr.lists[(size_t)(t - 1) * B + j];
+    if (e < 0 || e >= B) return;      // wave-uniform: past the end of the previous step's active list
+    const int D = cfg.dim_model, H = cfg.nhead, HD = D / H, S = cfg.dim_state, L = cfg.max_len;
+    float* base = smem + (size_t)wv * (kFixed + H * L);
+    float* xs = base;
+    float* qs = base + kMaxD;
+    float* ks = base + 2 * kMaxD;
+    float* vs = base + 3 * kMaxD;
+    float* att = base + 4 * kMaxD;
+    float* h1s = base + 5 * kMaxD;
+    float* ffs = base + 6 * kMaxD;
+    float* hb = ffs + kMaxHid;
+    float* hc = hb + kMaxW;
+    float* hinv = hc + kMaxW;
+    float* ps = hinv + kMaxD;
+
+    // ---- record the env step t-1 and build the input slot ------------------------------------------------------------
+    bool finished = false;
+    float x = 0.f;
+    if (t == 0) {
+        const double* o0 = tr.obs0 + (size_t)e * kObs0;
+        if (lane < kU) hc[lane] = (float)o0[lane];                 // the last 3 entries are not user features
+        if (lane + 64 < kU) hc[64 + lane] = (float)o0[64 + lane];
+        wbar();
+        if (lane < D) x = mv(w.user_w, w.user_b, hc, kU, D, lane);
+    } else {
+        const size_t row = (size_t)(t - 1) * B + e;
+        const double* so = tr.step_obs + (size_t)j * kObs;
+        if (lane < kObs) tr.obs[row * kObs + lane] = so[lane];
+        const double r64 = tr.step_rew[j];
+        const bool done = cfg.force_length > 0 ? t >= cfg.force_length : tr.step_done[j] != 0;
+        finished = done || t >= steps;
+        if (lane == 0) {
+            tr.rew[row] = r64;
+            tr.ctr[row] = tr.step_ctr[j];
+            tr.done[row] = (uint8_t)done;
+            if (finished) tr.len[e] = t;
+        }
+        // gate input [r, a_0..a_26]: hc[0] = r (the fp64 reward rounded once), hc[1 + k] = a_k
+        if (lane < kA) hc[1 + lane] = (float)so[lane];
+        if (lane == 0) hc[0] = (float)r64;
+        wbar();
+        if (lane < D) {
+            const float g = mv(w.gate_w, w.gate_b, hc, 1 + kA, D, lane);
+            x = (1.0f / (1.0f + expf(-g))) * hc[1 + lane];     // sigmoid(gate) * a_t, feature-wise (D == 27)
+        }
+    }
+    wbar();
+
+    // ---- decode position t ---------------------------------------------------------------------------------------------
+    const int pos = t;
+    const uint32_t d_thr = DROP ? dropout_threshold(cfg.dropout_p) : 0u;
+    const float d_inv = DROP ? 1.0f / (1.0f - cfg.dropout_p) : 1.0f;
+    const uint32_t d_env = (uint32_t)(cfg.drop_env_base + e);
+#define VTB_DROP(V, LAYER, SITE, ELEM) \
+    (dropout_keep(cfg.dropout_seed, d_env, (uint32_t)pos, (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), d_thr) ? (V) * d_inv : 0.f)
+    float h = 0.f;
+    if (lane < D) {
+        h = x * sqrtf((float)D) + w.pe[(size_t)pos * D + lane];
+        if (DROP) h = VTB_DROP(h, 0, CIRS_DROP_POS, lane);
+    }
+    const float qscale = 1.0f / sqrtf((float)HD);
+    for (int l = 0; l < cfg.nlayers; ++l) {
+        const cirs_vtb_policy_layer& ly = w.layer[l];
+        if (lane < D) xs[lane] = h;
+        wbar();
+        float* kc = tr.kcache + (((size_t)l * B + e) * L) * D;
+        float* vc = tr.vcache + (((size_t)l * B + e) * L) * D;
+        if (lane < D) {
+            const float q = mv(ly.in_w, ly.in_b, xs, D, 3 * D, lane);
+            const float k = mv(ly.in_w, ly.in_b, xs, D, 3 * D, D + lane);
+            const float v = mv(ly.in_w, ly.in_b, xs, D, 3 * D, 2 * D + lane);
+            qs[lane] = q * qscale;
+            ks[lane] = k;
+            vs[lane] = v;
+            kc[(size_t)pos * D + lane] = k;
+            vc[(size_t)pos * D + lane] = v;
+        }
+        wbar();
+        // causal attention of position pos over 0..pos, one head after the other; lanes stride over the key positions
+        for (int hh = 0; hh < H; ++hh) {
+            float mx = -INFINITY;
+            for (int jp = lane; jp <= pos; jp += 64) {
+                const float* kr = jp == pos ? ks : kc + (size_t)jp * D;
+                float sc = 0.f;
+                for (int d = 0; d < HD; ++d) sc = __builtin_fmaf(qs[hh * HD + d], kr[hh * HD + d], sc);
+                ps[hh * L + jp] = sc;
+                mx = fmaxf(mx, sc);
+            }
+            mx = wave_max_f32(mx);
+            float sm = 0.f;
+            for (int jp = lane; jp <= pos; jp += 64) {
+                const float ex = expf(ps[hh * L + jp] - mx);
+                sm += ex;
+                // attention-probability dropout acts after the softmax: the normaliser sums the unmasked terms
+                ps[hh * L + jp] = DROP ? VTB_DROP(ex, l, CIRS_DROP_ATTN, jp * H + hh) : ex;
+            }
+            sm = wave_sum_f32(sm);
+            if (lane == 0) hinv[hh] = 1.0f / sm;
+        }
+        wbar();
+        if (lane < D) {
+            const int hh = lane / HD;
+            const float* pr = ps + hh * L;
+            float acc = 0.f;
+#pragma unroll 4
+            for (int jp = 0; jp < pos; ++jp) acc = __builtin_fmaf(pr[jp], vc[(size_t)jp * D + lane], acc);
+            acc = __builtin_fmaf(pr[pos], vs[lane], acc);
+            att[lane] = acc * hinv[hh];
+        }
+        wbar();
+        // out_proj + residual + LayerNorm 1
+        float sa = lane < D ? mv(ly.out_w, ly.out_b, att, D, D, lane) : 0.f;
+        if (DROP && lane < D) sa = VTB_DROP(sa, l, CIRS_DROP_RES1, lane);
+        const float h1 = layer_norm(h + sa, lane, D, ly.norm1_w, ly.norm1_b);
+        if (lane < D) h1s[lane] = h1;
+        wbar();
+        // feed-forward (ReLU) + residual + LayerNorm 2
+        for (int i = lane; i < cfg.d_hid; i += 64) {
+            float f = fmaxf(mv(ly.lin1_w, ly.lin1_b, h1s, D, cfg.d_hid, i), 0.f);
+            if (DROP) f = VTB_DROP(f, l, CIRS_DROP_FF, i);
+            ffs[i] = f;
+        }
+        wbar();
+        float f2 = lane < D ? mv(ly.lin2_w, ly.lin2_b, ffs, cfg.d_hid, D, lane) : 0.f;
+        if (DROP && lane < D) f2 = VTB_DROP(f2, l, CIRS_DROP_RES2, lane);
+        h = layer_norm(h1 + f2, lane, D, ly.norm2_w, ly.norm2_b);
+        wbar();
+    }
+#undef VTB_DROP
+    if (lane < D) xs[lane] = h;
+    wbar();
+    float s = 0.f;
+    if (lane < S) {
+        s = mv(w.dec_w, w.dec_b, xs, D, S, lane);
+        tr.state[((size_t)pos * B + e) * S + lane] = s;
+    }
+    if (finished) return;      // wave-uniform
+
+    // ---- actor --------------------------------------------------------------------------------------------------------
+    if (lane < S) hb[lane] = s;
+    wbar();
+    float* in = hb;
+    float* out = hc;
+    int width = S;
+    for (int li = 0; li < cfg.n_hidden; ++li) {
+        const int O = cfg.hidden[li];
+        for (int o = lane; o < O; o += 64) out[o] = fmaxf(mv(w.trunk_w[li], w.trunk_b[li], in, width, O, o), 0.f);
+        wbar();
+        float* tmp = in;
+        in = out;
+        out = tmp;
+        width = O;
+    }
+    if (lane < kA) {
+        const float pre = mv(w.mu_w, w.mu_b, in, width, kA, lane);
+        const float mu = cfg.unbounded ? pre : cfg.max_action * tanhf(pre);
+        float sigma;
+        if (cfg.conditioned_sigma) sigma = expf(fminf(fmaxf(mv(w.sigma_w, w.sigma_b, in, width, kA, lane), -20.f), 2.f));
+        else sigma = expf(w.sigma_param[lane]);
+        const float z = gauss_z(seed, collect_id, (uint32_t)e, (uint32_t)t, (uint32_t)lane);
+        const float act = mu + sigma * z;
+        float u = act;
+        if (cfg.bound_method == 1) u = fminf(fmaxf(act, -1.0f), 1.0f);
+        else if (cfg.bound_method == 2) u = tanhf(act);
+        float m = u;
+        if (cfg.action_scaling) {
+            const float lo = w.act_low[lane], hi = w.act_high[lane];
+            m = lo + ((hi - lo) * (u + 1.0f)) / 2.0f;   // numpy's order: low + (high - low) * (unit + 1.0) / 2.0
+        }
+        const size_t row = ((size_t)t * B + e) * kA + lane;
+        tr.act[row] = act;
+        tr.act_mapped[row] = m;
+        xs[lane] = m;
+    }
+    int p = 0;
+    if (lane == 0) p = atomicAdd(&tr.counts[t], 1);
+    p = __shfl(p, 0, CIRS_WAVE);
+    wbar();
+    if (lane < kA) tr.act_buf[(size_t)p * kA + lane] = xs[lane];
+    if (lane == 0) tr.lists[(size_t)t * B + p] = e;
+}
+
+__global__ __launch_bounds__(256) void vtb_gauss_kernel(uint64_t seed, uint32_t collect_id, const int32_t* __restrict__ ids,
+                                                        const int32_t* __restrict__ ts, int n, int dims, float* __restrict__ out) {
+    const long total = (long)n * dims;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int r = (int)(i / dims), c = (int)(i % dims);
+        out[i] = gauss_z(seed, collect_id, (uint32_t)ids[r], (uint32_t)ts[r], (uint32_t)c);
+    }
+}
+
+__global__ __launch_bounds__(256) void vtb_mask_kernel(uint64_t dseed, float p, int env0, int n_env, int pos0, int n_pos, int layer, int site,
+                                                       int n_elem, float* __restrict__ out) {
+    const long total = (long)n_env * n_pos * n_elem;
+    const uint32_t thr = dropout_threshold(p);
+    const float inv = 1.0f / (1.0f - p);
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int el = (int)(i % n_elem);
+        const long rest = i / n_elem;
+        const int q = (int)(rest % n_pos), ev = (int)(rest / n_pos);
+        out[i] = dropout_keep(dseed, (uint32_t)(env0 + ev), (uint32_t)(pos0 + q), (uint32_t)layer, (uint32_t)site, (uint32_t)el, thr) ? inv : 0.f;
+    }
+}
+
+int grid_of(long total) {
+    const int g = cdiv(total, 256);
+    return g < 4096 ? g : 4096;
+}
+
+int validate_rollout(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* w, const cirs_vtb_cfg* vc, const cirs_vtb_traj* tr) {
+    CIRS_REQUIRE(cfg && w && vc && tr, "null rollout argument");
+    CIRS_REQUIRE(cfg->n_env >= 1, "n_env must be >= 1");
+    CIRS_REQUIRE(cfg->n_env == vc->n_env, "rollout n_env must equal the env's n_env");
+    CIRS_REQUIRE(cfg->max_turn >= 1, "max_turn must be >= 1");
+    CIRS_REQUIRE(!vc->simulated || cfg->max_turn == vc->max_turn, "rollout max_turn must equal the simulated env's max_turn");
+    CIRS_REQUIRE(vc->simulated || cfg->max_turn >= vc->max_turn, "rollout max_turn must be >= the raw env's max_turn (it ends every episode there)");
+    CIRS_REQUIRE(cfg->max_len >= 2 && cfg->max_turn <= cfg->max_len - 1,
+                 "max_turn exceeds the tracker's MAX_TURN - 1 (positions 0..max_turn need pe / cache rows)");
+    CIRS_REQUIRE(cfg->force_length >= 0 && cfg->force_length <= cfg->max_turn, "force_length must lie in [0, max_turn]");
+    CIRS_REQUIRE(cfg->dim_model >= 1 && cfg->dim_model <= kMaxD, "dim_model must lie in [1, 64]");
+    CIRS_REQUIRE(cfg->dim_model == kA, "dim_model must be 27: the input slot is sigmoid(fnn_gate([r, a])) * a with the 27 action features");
+    CIRS_REQUIRE(cfg->nhead >= 1 && cfg->dim_model % cfg->nhead == 0, "dim_model must be a multiple of nhead");
+    CIRS_REQUIRE((long)cfg->nhead * cfg->max_len <= kMaxAttn, "nhead * max_len must be <= 2048");
+    CIRS_REQUIRE(cfg->d_hid >= 1 && cfg->d_hid <= kMaxHid, "d_hid must lie in [1, 256]");
+    CIRS_REQUIRE(cfg->nlayers >= 1 && cfg->nlayers <= CIRS_VTB_RO_MAX_LAYERS, "nlayers must lie in [1, 4]");
+    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= kMaxD, "dim_state must lie in [1, 64]");
+    CIRS_REQUIRE(cfg->n_hidden >= 1 && cfg->n_hidden <= CIRS_VTB_RO_MAX_HIDDEN, "the actor trunk must have 1..3 hidden layers");
+    for (int i = 0; i < cfg->n_hidden; ++i) CIRS_REQUIRE(cfg->hidden[i] >= 1 && cfg->hidden[i] <= kMaxW, "actor hidden widths must lie in [1, 128]");
+    CIRS_REQUIRE(cfg->bound_method >= 0 && cfg->bound_method <= 2, "bound_method must be 0 (none), 1 (clip) or 2 (tanh)");
+    CIRS_REQUIRE(cfg->dropout_p >= 0.f && cfg->dropout_p < 1.f, "dropout_p must lie in [0, 1)");
+    CIRS_REQUIRE(cfg->drop_env_base >= 0, "drop_env_base must be >= 0");
+    CIRS_REQUIRE(w->user_w && w->user_b && w->gate_w && w->gate_b && w->pe && w->dec_w && w->dec_b && w->mu_w && w->mu_b,
+                 "tracker / actor weight is null");
+    for (int l = 0; l < cfg->nlayers; ++l) {
+        const cirs_vtb_policy_layer& y = w->layer[l];
+        CIRS_REQUIRE(y.in_w && y.in_b && y.out_w && y.out_b && y.lin1_w && y.lin1_b && y.lin2_w && y.lin2_b && y.norm1_w && y.norm1_b &&
+                         y.norm2_w && y.norm2_b,
+                     "encoder layer weight is null");
+    }
+    for (int i = 0; i < cfg->n_hidden; ++i) CIRS_REQUIRE(w->trunk_w[i] && w->trunk_b[i], "actor trunk weight is null");
+    CIRS_REQUIRE(cfg->conditioned_sigma ? (w->sigma_w && w->sigma_b) : (w->sigma_param != nullptr), "sigma weight is null");
+    CIRS_REQUIRE(!cfg->action_scaling || (w->act_low && w->act_high), "action box is null");
+    CIRS_REQUIRE(tr->state && tr->act && tr->act_mapped && tr->obs0 && tr->obs && tr->rew && tr->done && tr->ctr && tr->len && tr->kcache &&
+                     tr->vcache && tr->lists && tr->counts && tr->act_buf && tr->step_obs && tr->step_rew && tr->step_ctr && tr->step_done,
+                 "trajectory buffer is null");
+    return CIRS_OK;
+}
+
+}  // namespace
+}  // namespace cirs
+
+extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                        const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
+                                        uint32_t collect_id, void* stream) {
+    using namespace cirs;
+    if (int rc = validate_rollout(cfg, pw, vtb_cfg, traj)) return rc;
+    CIRS_REQUIRE(vtb_w && vtb_st, "null env weights / state");
+    const hipStream_t s = (hipStream_t)stream;
+    const cirs_vtb_rollout_cfg c = *cfg;
+    const cirs_vtb_traj tr = *traj;
+    const int B = c.n_env;
+    const int steps = c.force_length > 0 ? c.force_length : (vtb_cfg->simulated ? c.max_turn : vtb_cfg->max_turn);
+    const size_t T = (size_t)c.max_turn;
+    CIRS_HIP(hipMemsetAsync(tr.lists, 0xFF, (T + 1) * B * sizeof(int32_t), s));
+    CIRS_HIP(hipMemsetAsync(tr.counts, 0, (T + 1) * sizeof(int32_t), s));
+    CIRS_HIP(hipMemsetAsync(tr.len, 0, (size_t)B * sizeof(int32_t), s));
+    CIRS_HIP(hipMemsetAsync(tr.state, 0, (T + 1) * B * c.dim_state * sizeof(float), s));
+    CIRS_HIP(hipMemsetAsync(tr.act, 0, T * B * kA * sizeof(float), s));
+    CIRS_HIP(hipMemsetAsync(tr.act_mapped, 0, T * B * kA * sizeof(float), s));
+    CIRS_HIP(hipMemsetAsync(tr.obs, 0, T * B * kObs * sizeof(double), s));
+    CIRS_HIP(hipMemsetAsync(tr.rew, 0, T * B * sizeof(double), s));
+    CIRS_HIP(hipMemsetAsync(tr.ctr, 0, T * B * sizeof(double), s));
+    CIRS_HIP(hipMemsetAsync(tr.done, 0, T * B, s));
+    if (int rc = cirs_vtb_reset(vtb_cfg, vtb_w, vtb_st, c.env_seed, nullptr, B, tr.obs0, stream)) return rc;
+    const size_t shmem = (size_t)kWaves * (kFixed + (size_t)c.nhead * c.max_len) * sizeof(float);
+    const dim3 grid(cdiv(B, kWaves)), block(64 * kWaves);
+    const bool drop = c.dropout_p > 0.f;
+    for (int t = 0; t <= steps; ++t) {
+        if (drop) hipLaunchKernelGGL(vtb_policy_step_kernel<true>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);
+        else hipLaunchKernelGGL(vtb_policy_step_kernel<false>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);
+        CIRS_CHECK_LAUNCH("vtb_policy_step_kernel");
+        if (t == steps) break;
+        // the env step of list t (ids past the active count are -1: empty slots)
+        if (int rc = cirs_vtb_step(vtb_cfg, vtb_w, vtb_st, c.env_seed, tr.act_buf, tr.lists + (size_t)t * B, B, tr.step_obs, tr.step_rew,
+                                   tr.step_done, tr.step_ctr, nullptr, stream))
+            return rc;
+    }
+    return CIRS_OK;
+}
+
+extern "C" int cirs_vtb_rollout_noise(uint64_t seed, uint32_t collect_id, const int32_t* env_ids, const int32_t* ts, int32_t n, int32_t dims,
+                                      float* out, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(n >= 0 && dims >= 0, "n and dims must be >= 0");
+    if (n == 0 || dims == 0) return CIRS_OK;
+    CIRS_REQUIRE(env_ids && ts && out, "null argument");
+    hipLaunchKernelGGL(vtb_gauss_kernel, dim3(grid_of((long)n * dims)), dim3(256), 0, (hipStream_t)stream, seed, collect_id, env_ids, ts, n, dims,
+                       out);
+    CIRS_CHECK_LAUNCH("vtb_gauss_kernel");
+    return CIRS_OK;
+}
+
+extern "C" int cirs_vtb_rollout_masks(uint64_t dropout_seed, float p, int32_t env0, int32_t n_env, int32_t pos0, int32_t n_pos, int32_t layer,
+                                      int32_t site, int32_t n_elem, float* out, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(p >= 0.f && p < 1.f, "p must lie in [0, 1)");
+    CIRS_REQUIRE(n_env >= 0 && n_pos >= 0 && n_elem >= 0, "sizes must be >= 0");
+    CIRS_REQUIRE(env0 >= 0 && pos0 >= 0 && pos0 + (long)n_pos <= 4096, "env0 / positions out of range (positions < 4096)");
+    CIRS_REQUIRE(layer >= 0 && layer < CIRS_VTB_RO_MAX_LAYERS, "layer out of range");
+    CIRS_REQUIRE(site >= CIRS_DROP_POS && site <= CIRS_DROP_RES2, "site out of range");
+    const long total = (long)n_env * n_pos * n_elem;
+    if (total == 0) return CIRS_OK;
+    CIRS_REQUIRE(out != nullptr, "null output");
+    hipLaunchKernelGGL(vtb_mask_kernel, dim3(grid_of(total)), dim3(256), 0, (hipStream_t)stream, dropout_seed, p, env0, n_env, pos0, n_pos, layer,
+                       site, n_elem, out);
+    CIRS_CHECK_LAUNCH("vtb_mask_kernel");
+    return CIRS_OK;
+}

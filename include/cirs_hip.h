@@ -777,6 +777,96 @@ int cirs_vtb_noise(uint64_t seed, const int32_t* env_ids, const uint32_t* events
 int cirs_vtb_mmoe_forward(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, const float* x, int32_t n, float* y_out,
                           void* stream);
 
+/* ---- VirtualTaobao PPO rollout on the device (csrc/vtb_rollout.hip) -------------------------------------------------------
+ * The policy side of CIRS-RL-taobao.py's per-step loop: the dense-feature state tracker (HostStateTracker: ffn_user / fnn_gate
+ * input slot, positional encoding, post-norm causal TransformerEncoder, decoder) as a K/V-cached decode step, and ActorProb over
+ * its Net trunk with a Gaussian draw.  One vtb_policy_step_kernel launch + one vtb_step_kernel launch per vector step. */
+#define CIRS_VTB_RO_MAX_LAYERS 4
+#define CIRS_VTB_RO_MAX_HIDDEN 3
+
+typedef struct cirs_vtb_rollout_cfg {
+    int32_t n_env;             /* == vtb_cfg->n_env                                                              */
+    int32_t max_turn;          /* vector steps of a collect; == vtb_cfg->max_turn and <= max_len - 1             */
+    int32_t force_length;      /* > 0: every episode ends after this many steps, overriding the env (<= max_turn) */
+    int32_t dim_model;         /* D <= 64, D % nhead == 0                                                        */
+    int32_t nhead;
+    int32_t d_hid;             /* <= 256                                                                         */
+    int32_t nlayers;           /* 1..4                                                                           */
+    int32_t dim_state;         /* <= 64                                                                          */
+    int32_t max_len;           /* tracker MAX_TURN rows (pe rows, K/V cache rows); nhead * max_len <= 2048        */
+    int32_t n_hidden;          /* actor trunk layers 1..3                                                        */
+    int32_t hidden[CIRS_VTB_RO_MAX_HIDDEN]; /* trunk widths <= 128                                               */
+    int32_t unbounded;         /* 1: mu = head output; 0: max_action * tanh(head output)                         */
+    int32_t conditioned_sigma; /* 1: sigma = exp(clamp(sigma head, -20, 2)); 0: exp(sigma_param)                */
+    int32_t bound_method;      /* mapped action: 0 none, 1 clip to [-1, 1], 2 tanh                               */
+    int32_t action_scaling;    /* 1: [-1, 1] -> [act_low, act_high]                                              */
+    float max_action;
+    float dropout_p;           /* 0 <= p < 1; 0 = no mask work                                                    */
+    int32_t drop_env_base;     /* dropout env id = drop_env_base + env                                           */
+    uint64_t dropout_seed;     /* dropout key of this collect                                                    */
+    uint64_t env_seed;         /* Philox key of the env (DeviceVirtualTB.seed)                                   */
+} cirs_vtb_rollout_cfg;
+
+typedef struct cirs_vtb_policy_layer { /* one post-norm TransformerEncoderLayer, matrices stored [in][out] */
+    const float *in_w, *in_b;     /* [D][3D], [3D] (q | k | v)  */
+    const float *out_w, *out_b;   /* [D][D], [D]                */
+    const float *lin1_w, *lin1_b; /* [D][d_hid], [d_hid]        */
+    const float *lin2_w, *lin2_b; /* [d_hid][D], [D]            */
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} cirs_vtb_policy_layer;
+
+typedef struct cirs_vtb_policy_weights { /* fp32, matrices stored [in][out] */
+    const float *user_w, *user_b;   /* ffn_user [88][D], [D]                                  */
+    const float *gate_w, *gate_b;   /* fnn_gate [1 + 27][D] (row 0: reward), [D]              */
+    const float* pe;                /* [max_len][D]                                           */
+    cirs_vtb_policy_layer layer[CIRS_VTB_RO_MAX_LAYERS];
+    const float *dec_w, *dec_b;     /* [D][dim_state], [dim_state]                            */
+    const float* trunk_w[CIRS_VTB_RO_MAX_HIDDEN]; /* Net: [in][hidden[i]] (ReLU after each)   */
+    const float* trunk_b[CIRS_VTB_RO_MAX_HIDDEN];
+    const float *mu_w, *mu_b;       /* [hidden[n-1]][27], [27]                                */
+    const float *sigma_w, *sigma_b; /* conditioned_sigma: [hidden[n-1]][27], [27]; else NULL  */
+    const float* sigma_param;       /* [27] (not conditioned)                                 */
+    const float *act_low, *act_high; /* [27] action box (action_scaling)                      */
+} cirs_vtb_policy_weights;
+
+typedef struct cirs_vtb_traj { /* device buffers owned by the caller; t = vector step, e = env id */
+    float* state;       /* [max_turn + 1][n_env][dim_state] tracker state of every visited position     */
+    float* act;         /* [max_turn][n_env][27] raw action (what the buffer stores)                     */
+    float* act_mapped;  /* [max_turn][n_env][27] the action the env received                              */
+    double* obs0;       /* [n_env][91] reset observations                                                */
+    double* obs;        /* [max_turn][n_env][30] observation of step t, as the env returns it            */
+    double* rew;        /* [max_turn][n_env]                                                             */
+    uint8_t* done;      /* [max_turn][n_env] after force_length                                          */
+    double* ctr;        /* [max_turn][n_env]                                                             */
+    int32_t* len;       /* [n_env] episode lengths                                                       */
+    /* scratch */
+    float* kcache;      /* [nlayers][n_env][max_len][D] */
+    float* vcache;      /* [nlayers][n_env][max_len][D] */
+    int32_t* lists;     /* [max_turn + 1][n_env] active env ids per step                                 */
+    int32_t* counts;    /* [max_turn + 1]                                                                */
+    float* act_buf;     /* [n_env][27] mapped actions of the current step, in list order                 */
+    double* step_obs;   /* [n_env][30] */
+    double* step_rew;   /* [n_env] */
+    double* step_ctr;   /* [n_env] */
+    uint8_t* step_done; /* [n_env] */
+} cirs_vtb_traj;
+
+/* One collect of n_env whole episodes on `stream`, no host synchronisation: vtb_reset of every env, then per vector step the policy
+ * kernel (record the previous step, input slot, decode, actor, mapped action, compaction of the active ids) and vtb_step over the
+ * envs still active; finished envs are dropped, not reset.  The Gaussian noise of (env, t, dim) is keyed by (seed, collect_id). */
+int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                             const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
+                             uint32_t collect_id, void* stream);
+/* the standard normals z the policy kernel draws for (env_ids[j], ts[j], dim 0..dims-1): out [n][dims] fp32, bit for bit.
+ * Box-Muller on Philox (counter (dim / 4, env, t, collect_id), key seed ^ 'GAUS'): the words (w0, w1) give dims 4b, 4b+1, (w2, w3)
+ * dims 4b+2, 4b+3; u = u01_from_bits(w); z = sqrt(-2 det_logf(u1)) * {cos, sin}(2 pi u2) with fixed polynomials. */
+int cirs_vtb_rollout_noise(uint64_t seed, uint32_t collect_id, const int32_t* env_ids, const int32_t* ts, int32_t n, int32_t dims,
+                           float* out, void* stream);
+/* keep masks of dropout envs env0..env0+n_env-1, positions pos0..pos0+n_pos-1, (layer, site), elements 0..n_elem-1:
+ * out [n_env][n_pos][n_elem] = keep ? 1 / (1 - p) : 0 (csrc/rng.h dropout_keep; ATTN element = key_pos * nhead + head). */
+int cirs_vtb_rollout_masks(uint64_t dropout_seed, float p, int32_t env0, int32_t n_env, int32_t pos0, int32_t n_pos, int32_t layer,
+                           int32_t site, int32_t n_elem, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
