@@ -157,6 +157,23 @@ class VtbTraj(C.Structure):          # cirs_vtb_traj
     _fields_ = [(k, C.c_void_p) for k in VTB_TRAJ_FIELDS]
 
 
+class VtbLearnCfg(C.Structure):      # cirs_vtb_learn_cfg
+    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "dim_model", "nhead", "d_hid", "nlayers", "dim_state", "max_len", "n_hidden")] + \
+        [("hidden", C.c_int32 * VTB_RO_MAX_HIDDEN), ("unbounded", C.c_int32), ("conditioned_sigma", C.c_int32), ("max_action", C.c_float),
+         ("dropout_p", C.c_float), ("drop_env_base", C.c_int32), ("dropout_seed", C.c_uint64)] + \
+        [(k, C.c_int32) for k in ("n_rows", "n_seg", "scale_returns", "whiten_adv", "clip_value", "has_dual", "has_max_norm")] + \
+        [(k, C.c_float) for k in ("clip", "dual", "c_value", "c_entropy", "max_norm")] + [(k, C.c_double) for k in ("discount", "lam", "floor")] + \
+        [(k, C.c_float) for k in ("lr", "beta1", "beta2", "eps", "t_lr", "t_beta1", "t_beta2", "t_eps")]
+
+
+VTB_LEARN_BUF_FIELDS = ("tparams", "t_m", "t_v", "pparams", "p_m", "p_v", "pe", "obs0", "obs", "rew", "done", "act", "len", "rows", "boundary",
+                        "seg_end", "grad_rows", "grad_start", "rms", "ws", "losses")
+
+
+class VtbLearnBufs(C.Structure):     # cirs_vtb_learn_bufs
+    _fields_ = [(k, C.c_void_p) for k in VTB_LEARN_BUF_FIELDS]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -176,6 +193,10 @@ SIGNATURES = {
     "cirs_vtb_rollout_noise": (C.c_int, [C.c_uint64, C.c_uint32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "cirs_vtb_rollout_masks": (C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          _P, _P]),
+    "cirs_vtb_learn_sizes": (C.c_int, [C.POINTER(VtbLearnCfg), _P]),
+    "cirs_vtb_learn_prepare": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P]),
+    "cirs_vtb_learn_update": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int64, _P]),
     "cirs_tracker_init": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,
                                     C.c_int32, _P, C.c_int64, _P]),
     "cirs_tracker_step": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,

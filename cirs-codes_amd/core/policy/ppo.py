@@ -21,9 +21,18 @@ class PPOPolicy(nn.Module):
         """A continuous actor (tianshou.utils.net.continuous.ActorProb: CIRS-RL-taobao.py:208, BASELINE configs[0], CPU plumbing) is
         served by the host PPO of core.host_rl; the discrete catalogue actor by the device learner below."""
         from tianshou.utils.net.continuous import ActorProb
+        learner = kwargs.pop("learner", None)      # caught here: HostPPOPolicy swallows unknown keywords
+        if learner not in (None, "device"):
+            raise ValueError(f"learner must be None or 'device', got {learner!r}")
         if cls is PPOPolicy and isinstance(actor, ActorProb):
+            if learner == "device":      # the update on the GPU (core.vtb_learner, csrc/vtb_learn.hip)
+                from core.vtb_learner import DeviceVtbPPOPolicy
+                return DeviceVtbPPOPolicy(actor, critic, optim, dist_fn, *args, **kwargs)
             from core.host_rl import HostPPOPolicy
             return HostPPOPolicy(actor, critic, optim, dist_fn, *args, **kwargs)
+        if learner is not None:
+            raise ValueError("learner='device' is the VirtualTaobao (ActorProb) learner; the discrete catalogue policy always learns on "
+                             "the device (build PPOPolicy without learner=)")
         return super().__new__(cls)
 
     def __init__(self, actor, critic, optim, dist_fn=None, eps_clip=0.2, dual_clip=None, value_clip=False,

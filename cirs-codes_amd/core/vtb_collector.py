@@ -111,7 +111,10 @@ class DeviceVtbCollector:
         self._collect_count += 1
         self.last_collect = (seed, cid, dseed)
         tr = {k: ro.traj[k].cpu() for k in ("obs0", "obs", "rew", "done", "ctr", "act", "state")}
-        if self._keep_buffer:
+        from core.vtb_learner import DeviceVtbPPOPolicy
+        if self._keep_buffer and isinstance(self.policy, DeviceVtbPPOPolicy):
+            res = self._fill_device(ro, tr, lens, (seed, cid, dseed))
+        elif self._keep_buffer:
             res = self._fill_buffer(ro, tr, lens, dseed)
         else:
             res = self._summary_only(tr, lens)
@@ -156,6 +159,13 @@ class DeviceVtbCollector:
             if len(over):
                 closed.append((ep_return[over], ep_length[over], ep_first[over]))
         return self._stats(closed, n_st)
+
+    def _fill_device(self, ro, tr, lens, keys):
+        """The device learner's buffer: HostCollector's row order and bookkeeping in one vectorised step (no state rebuild, no per-step
+        add); rows are built from the trajectory on first access and the learner reads the device trajectory itself."""
+        from core.vtb_learner import VtbDeviceRows
+        self.buffer.fill_from_trajectory(VtbDeviceRows(self, ro, lens, keys, tr), lens)
+        return self._summary_only(tr, lens)
 
     def _summary_only(self, tr, lens):
         """The result dict without buffer rows: every episode starts at its sub-buffer's first row of a fresh buffer."""

@@ -204,6 +204,9 @@ class VectorReplayBuffer:
     def _materialise(self):
         if not self._meta.is_empty() or self._traj is None:
             return
+        if hasattr(self._traj, "materialise"):      # a device VirtualTaobao collect (core.vtb_learner.VtbDeviceRows)
+            self._meta = self._traj.materialise(self)
+            return
         tr, n = self._traj, self.maxsize
         S = tr.obs.shape[-1]
         e, t = self._rows_env, self._rows_t

@@ -867,6 +867,69 @@ int cirs_vtb_rollout_noise(uint64_t seed, uint32_t collect_id, const int32_t* en
 int cirs_vtb_rollout_masks(uint64_t dropout_seed, float p, int32_t env0, int32_t n_env, int32_t pos0, int32_t n_pos, int32_t layer,
                            int32_t site, int32_t n_elem, float* out, void* stream);
 
+/* ---- VirtualTaobao PPO update on the device (csrc/vtb_learn.hip) ---------------------------------------------------------
+ * Replaces HostPPOPolicy.update (core/host_rl.py: _returns_stage, process_fn, learn) over a buffer of one device collect, with the
+ * tracker gradient through the teacher-forced causal pass of cirs_hip/vtb_host.py tracker_states (reference core/state_tracker.py:
+ * 129-250, core/policy/ppo.py:96-246, tianshou/policy/base.py:219-244, modelfree/a2c.py:80-109).
+ * Parameter images are fp32 in torch's own layout ([out][in] row-major), in module registration order:
+ *   tracker: ffn_user W b | fnn_gate W b | per layer: in_proj W b, out_proj W b, linear1 W b, linear2 W b, norm1 w b, norm2 w b |
+ *            decoder W b
+ *   policy:  trunk (Net) W b per hidden layer | mu W b | sigma W b (conditioned) or sigma_param [27] | critic W [width] b [1]
+ * Adam moments have the layout of their image.  The trunk is the first part of the policy image: it is listed twice in the policy
+ * optimiser (actor + critic share the Net), so its squared norm counts twice, the clip coefficient is applied twice and it takes two
+ * Adam sub-steps per minibatch. */
+typedef struct cirs_vtb_learn_cfg {
+    int32_t n_env, max_turn;                     /* the collect's shape (trajectory [max_turn][n_env])                      */
+    int32_t dim_model, nhead, d_hid, nlayers, dim_state, max_len;
+    int32_t n_hidden;
+    int32_t hidden[CIRS_VTB_RO_MAX_HIDDEN];
+    int32_t unbounded, conditioned_sigma;
+    float max_action, dropout_p;
+    int32_t drop_env_base;
+    uint64_t dropout_seed;
+    int32_t n_rows, n_seg;                       /* sampled rows, GAE segments of the sample order                           */
+    int32_t scale_returns, whiten_adv, clip_value, has_dual, has_max_norm;
+    float clip, dual, c_value, c_entropy, max_norm;
+    double discount, lam, floor;
+    float lr, beta1, beta2, eps;                 /* policy Adam                                                              */
+    float t_lr, t_beta1, t_beta2, t_eps;         /* tracker Adam                                                             */
+} cirs_vtb_learn_cfg;
+
+typedef struct cirs_vtb_learn_bufs {
+    float* tparams; float* t_m; float* t_v;      /* tracker image + Adam moments                                             */
+    float* pparams; float* p_m; float* p_v;      /* policy image + Adam moments                                              */
+    const float* pe;                             /* [max_len][D] positional encoding                                         */
+    const double* obs0;                          /* the rollout's trajectory: [n_env][91]                                    */
+    const double* obs;                           /* [max_turn][n_env][30]                                                    */
+    const double* rew;                           /* [max_turn][n_env]                                                        */
+    const uint8_t* done;                         /* [max_turn][n_env]                                                        */
+    const float* act;                            /* [max_turn][n_env][27] raw actions                                        */
+    const int32_t* len;                          /* [n_env]                                                                  */
+    const int32_t* rows;                         /* [2][n_rows]: t, env of each sampled row                                  */
+    const uint8_t* boundary;                     /* [n_rows] done | unfinished                                               */
+    const int32_t* seg_end;                      /* [n_seg] exclusive ends of the GAE segments                               */
+    const int32_t* grad_rows;                    /* [n_rows] sample positions sorted by (env, t)                             */
+    const int32_t* grad_start;                   /* [n_env * max_turn + 1] CSR starts into grad_rows                          */
+    double* rms;                                 /* [3] running return mean, var, count (merged on the device)              */
+    float* ws;                                   /* workspace of cirs_vtb_learn_sizes()[2] floats                           */
+    float* losses;                               /* [n_minibatches][4] loss, clip, vf, ent                                   */
+} cirs_vtb_learn_bufs;
+
+/* out[0] tracker image floats, out[1] policy image floats, out[2] workspace floats, out[3] offset of the states [max_turn + 1]
+ * [n_env][dim_state] in the workspace, out[4] offset of the per-row block (v_s, adv, returns, logp_old: [4][n_rows]). */
+int cirs_vtb_learn_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out);
+/* Returns stage (HostPPOPolicy._returns_stage + process_fn): the teacher-forced tracker forward over every episode (states and the
+ * saved activations), critic values of obs / obs_next, GAE per segment in fp64, returns on the pre-update scale, the block merged
+ * into rms, logp_old of the stored actions. */
+int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, void* stream);
+/* HostPPOPolicy.learn after prepare: `repeat` passes over the rows in the orders perms [repeat][n_rows] (device), minibatches of
+ * batch_size rows (a short tail joins the last one); per minibatch the row objective and its gradient, clip_grad_norm_ and Adam on the
+ * policy image (step counts continue from p_step0 heads / 2 * p_step0 trunk); recompute_adv reruns the returns stage before every
+ * pass after the first; after the last pass the tracker gradient through each row's obs state and one tracker Adam step (t_step0 + 1).
+ * No host synchronisation. */
+int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
+                          int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
