@@ -174,6 +174,11 @@ class VtbLearnBufs(C.Structure):     # cirs_vtb_learn_bufs
     _fields_ = [(k, C.c_void_p) for k in VTB_LEARN_BUF_FIELDS]
 
 
+class MmoeTrainCfg(C.Structure):    # cirs_mmoe_train_cfg
+    _fields_ = [(k, C.c_int32) for k in ("d_in", "h1", "h2", "n_experts", "expert_dim", "n_tasks", "task_dim")] + \
+        [(k, C.c_float) for k in ("l2_linear", "l2_all", "lr", "beta1", "beta2", "eps")]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -273,6 +278,12 @@ SIGNATURES = {
     "cirs_deepfm_train_step": (C.c_int, [C.POINTER(DeepFMCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int32,
                                          C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                          _P, _P, C.c_int64, _P]),
+    "cirs_mmoe_train_param_count": (C.c_int64, [C.POINTER(MmoeTrainCfg)]),
+    "cirs_mmoe_train_workspace_bytes": (C.c_int64, [C.POINTER(MmoeTrainCfg), C.c_int32]),
+    "cirs_mmoe_train_step": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_mmoe_train_epoch": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32,
+                                        _P, _P, C.c_int64, _P]),
+    "cirs_vtb_exposure_history": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P, _P]),
     "cirs_exposure_history": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_double, _P, _P]),
     "cirs_find_negative": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int64, _P, _P]),
     "cirs_select_items": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, _P, C.c_uint64, C.c_uint32,

@@ -1,0 +1,90 @@
+"""Host restatements for the VirtualTaobao user-model training (csrc/mmoe_train.hip); imports without libcirs_hip.so.
+
+exposure_virtualtaobao   compute_exposure_effect_virtualTaobao (reference CIRS-UserModel-taobao.py:52-70) in numpy float64.
+torch_train              the optimiser steps of UserModel_MMOE.fit_data (reference core/user_model.py:150-170) restated in plain torch
+                         (autograd + torch.optim.Adam) over a state_dict under the reference's names: loss_taobao, the regulariser
+                         over linear_model (l2_linear) and over EVERY parameter (l2_all).  The comparison object of the device step, in
+                         tests and in tools/probe_mmoe_train.py.
+"""
+import numpy as np
+import torch
+
+D_IN, N_EXPERTS, EXPERT_DIM = 118, 4, 8
+USER_COLS, ACTION_COLS = 91, 27
+
+
+def shapes(h1, h2):
+    """(state_dict name, shape) of UserModel_MMOE's all-dense one-task build, in state_dict order."""
+    return [("linear_model.weight", (D_IN, 1)), ("dnn.linears.0.weight", (h1, D_IN)), ("dnn.linears.0.bias", (h1,)),
+            ("dnn.linears.1.weight", (h2, h1)), ("dnn.linears.1.bias", (h2,)),
+            ("mmoe_layer.expert_network.weight", (N_EXPERTS * EXPERT_DIM, h2)), ("mmoe_layer.expert_network.bias", (N_EXPERTS * EXPERT_DIM,)),
+            ("mmoe_layer.gating_networks.0.weight", (N_EXPERTS, h2)), ("tower_network.0.weight", (1, EXPERT_DIM)), ("out.0.bias", (1, 1)),
+            ("linear_model_task.0.weight", (D_IN, 1))]
+
+
+def exposure_virtualtaobao(timestamp, action, tau):
+    """timestamp [n] (a row with 1 opens a session), action [n, 27] -> exposure [n, 1] float64:
+    sum over the session's earlier rows j of exp(-(r - j) * ||a_r - a_j||_2 / tau); 0 for tau <= 0."""
+    timestamp = np.asarray(timestamp).astype(np.int64).reshape(-1)
+    action = np.asarray(action, np.float64)
+    n = len(timestamp)
+    out = np.zeros((n, 1))
+    if n == 0:
+        return out
+    if timestamp[0] != 1:
+        raise ValueError("the first row of the log must open a session (timestamp column == 1)")
+    if tau <= 0:
+        return out
+    start = 0
+    for r in range(n):
+        if timestamp[r] == 1:
+            start = r
+            continue
+        dist = np.sqrt(((action[start:r] - action[r]) ** 2).sum(1))
+        out[r, 0] = np.exp(-(r - np.arange(start, r)) * dist / tau).sum()
+    return out
+
+
+def forward(p, x):
+    """UserModel_MMOE.forward over the parameter dict p (reference names) -> [n, 1]."""
+    h = torch.relu(x @ p["dnn.linears.0.weight"].t() + p["dnn.linears.0.bias"])
+    h = torch.relu(h @ p["dnn.linears.1.weight"].t() + p["dnn.linears.1.bias"])
+    experts = (h @ p["mmoe_layer.expert_network.weight"].t() + p["mmoe_layer.expert_network.bias"]).reshape(-1, EXPERT_DIM, N_EXPERTS)
+    gate = (h @ p["mmoe_layer.gating_networks.0.weight"].t()).softmax(1)
+    mix = torch.bmm(experts, gate.unsqueeze(-1)).squeeze(-1)
+    logit = x @ p["linear_model_task.0.weight"] + mix @ p["tower_network.0.weight"].t()
+    return logit + p["out.0.bias"]
+
+
+def loss_taobao(y_pred, y, exposure):
+    return (((1 / (1 + exposure) * y_pred - y) ** 2) * (y + 1)).mean()
+
+
+def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_linear=1e-5, l2_all=1e-2, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                dtype=torch.float32, device="cpu", keep=()):
+    """-> (losses [steps, 2] = {loss, reg}, {step index: parameters after that step (numpy) for the indices in `keep`}, final parameters)."""
+    p = {k: torch.nn.Parameter(torch.as_tensor(np.asarray(v)).to(device, dtype).clone()) for k, v in init.items()}
+    names = list(p)      # state_dict order = the reference's parameter order
+    opt = torch.optim.Adam([p[k] for k in names], lr=lr, betas=betas, eps=eps)
+    X = torch.as_tensor(np.asarray(x)).to(device, dtype)
+    Y = torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, 1)
+    E = torch.as_tensor(np.asarray(exposure)).to(device, dtype).reshape(-1, 1)
+    order = torch.arange(X.shape[0], device=device) if order is None else torch.as_tensor(order).to(device)
+    n_steps = (len(order) + batch_size - 1) // batch_size
+    steps = n_steps if steps is None else min(steps, n_steps)
+    losses, kept = [], {}
+    for st in range(steps):
+        idx = order[st * batch_size:(st + 1) * batch_size]
+        loss = loss_taobao(forward(p, X[idx]), Y[idx], E[idx])
+        opt.zero_grad()
+        reg = torch.zeros((1,), dtype=dtype, device=device)
+        w = p["linear_model.weight"]
+        reg = reg + torch.sum(l2_linear * w * w)
+        for k in names:
+            reg = reg + torch.sum(l2_all * p[k] * p[k])
+        (loss + reg.squeeze()).backward()
+        opt.step()
+        losses.append([float(loss.detach()), float(reg.detach())])
+        if st in keep:
+            kept[st] = {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
+    return np.array(losses), kept, {k: v.detach().cpu().numpy().copy() for k, v in p.items()}

@@ -167,3 +167,48 @@ def write_kuairec_workspace(datapath: str, *, n_users: int = 48, n_items: int = 
     with open(os.path.join(datapath, "photo_mean_duration.json"), "w") as fh:
         json.dump({str(i): float(d) for i, d in enumerate(durations)}, fh)
     return dict(list_feat=list_feat, durations=durations, env_users=env_users, env_items=env_items, big=big)
+
+
+def write_virtualtaobao_log(path: str, n_sessions: int, seed: int = 0, *, vtb_env=None, n_env: int = 64, device: str = "cuda") -> int:
+    """A `dataset.txt`-shaped VirtualTaobao log (reference CIRS-UserModel-taobao.py:85-93) from the RAW device VirtualTB env rolled with
+    uniformly random actions in the action box: one line per step = the 91-column state in front of the step (88 user features, the two
+    last-action columns, the turn counter -- reference virtualTB.py:48-57), the 27-column action, the clicks; space separated.
+    The turn counter is written 1-BASED per session (the env counts from 0): the loader's rule "timestamp == 1 opens a session"
+    (compute_exposure_effect_virtualTaobao) keys on this last state column.  Sessions are written one after the other, each until
+    the env reports done.  `vtb_env`: the VirtualTB whose simulator weights the device env uses (default: VirtualTB()).  Returns
+    the number of rows.  For tests, the example and the probe only."""
+    import torch
+    from cirs_hip.virtualtb import DeviceVirtualTB
+    if vtb_env is None:
+        from environments.VirtualTaobao.virtualTB.envs.virtualTB import VirtualTB
+        vtb_env = VirtualTB()
+    n_env = max(1, min(int(n_env), int(n_sessions)))
+    env = DeviceVirtualTB(vtb_env, n_env, seed=seed, device=device)
+    rng = np.random.RandomState(seed)
+    sessions, open_rows = [], [[] for _ in range(n_env)]
+    live = np.ones(n_env, bool)
+    state = env.reset().cpu().numpy().copy()          # [n_env, 91]: user one-hot | last action (0, 0) | turn 0
+    started = n_env
+    while live.any():
+        ids = np.flatnonzero(live)
+        act = rng.uniform(-1.0, 1.0, (len(ids), 27)).astype(np.float32)
+        obs, rew, done, _ = (t.cpu().numpy() for t in env.step(torch.as_tensor(act), ids))
+        fresh = []
+        for j, e in enumerate(ids):
+            open_rows[e].append(np.concatenate([state[e, :90], [state[e, 90] + 1.0], act[j].astype(np.float64), [rew[j]]]))
+            state[e, 88:91] = obs[j, 27:30]
+            if done[j]:
+                sessions.append(open_rows[e])
+                open_rows[e] = []
+                if started < n_sessions:
+                    started += 1
+                    fresh.append(e)
+                else:
+                    live[e] = False
+        if fresh:
+            state[fresh] = env.reset(np.asarray(fresh)).cpu().numpy()
+    rows = [r for s in sessions for r in s]
+    with open(path, "w") as fh:
+        for r in rows:
+            fh.write(" ".join(repr(float(v)) if v != int(v) else str(int(v)) for v in r) + "\n")
+    return len(rows)

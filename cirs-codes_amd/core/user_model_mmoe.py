@@ -1,7 +1,8 @@
 """UserModel_MMOE (reference core/user_model_mmoe.py:15-262 over core/layers.py MMOELayer/Linear and DeepCTR-Torch's DNN /
 PredictionLayer): the user model of the VirtualTaobao experiments (CIRS-UserModel-taobao.py:100-148) -- BASELINE configs[0], CPU
-plumbing.  Inference side only: parameters under the reference's state_dict names and `forward`; plain torch on whatever device
-the module lives on (this is not a hot path: one 1 x 118 row per env step).
+plumbing.  Parameters under the reference's state_dict names; `forward` is plain torch on whatever device the module lives on (this
+is not a hot path: one 1 x 118 row per env step); `compile` / `fit_data` train on the device (cirs_hip.mmoe_train.MMoETrainer:
+cirs_mmoe_train_epoch, two launches per optimiser step, loss_taobao inside the kernel).
 
     y_task = PredictionLayer_task( Linear_task(X)  [+ FM over the sparse embeddings, none for the all-dense Taobao features]
                                    + tower_task( MMoE_task( DNN(X) ) ) )
@@ -13,6 +14,15 @@ from torch import nn
 from core.inputs import compute_input_dim
 from core.user_model import UserModel
 from deepctr_torch.inputs import DenseFeat, build_input_features
+
+
+def loss_taobao(y_predict=None, y_true=None, exposure=None, y_index=None):
+    """Marker of the reference's loss (CIRS-UserModel-taobao.py:185-191), mean((y_predict / (1 + exposure) - y)^2 (y + 1)): pass it to
+    UserModel_MMOE.compile; the loss itself runs inside cirs_mmoe_train_step."""
+    raise RuntimeError("loss_taobao is evaluated on the device by cirs_mmoe_train_step; it is a marker for UserModel_MMOE.compile")
+
+
+loss_taobao.device_loss = "taobao"
 
 
 class _Dense(nn.Module):
@@ -85,6 +95,64 @@ class UserModel_MMOE(UserModel):
         for m in [self.linear_model] + [m for m in self.linear_model_task if m is not None]:
             nn.init.normal_(m.weight, mean=0, std=init_std)
         self.to(device)
+        self._l2 = (1e-5, float(l2_reg_dnn))     # (linear_model: the base class's l2_reg_linear default, every parameter)
+        self.optim = None
+        self._trainer = None
+
+    # ---- training (reference core/user_model.py:74-170 with loss_taobao) ------------------------------------------------------
+    def compile(self, optimizer, loss_dict=None, metrics=None, metric_fun=None, loss_func=None):
+        if not (optimizer == "adam" or isinstance(optimizer, torch.optim.Adam)):
+            raise ValueError("the device step implements torch.optim.Adam: pass optimizer=\"adam\" or a torch.optim.Adam instance")
+        if getattr(loss_func, "device_loss", None) != "taobao":
+            raise ValueError("pass core.user_model_mmoe.loss_taobao: the loss runs inside cirs_mmoe_train_step")
+        shape = [tuple(l.weight.shape) for l in self.dnn.linears]
+        if len(shape) != 2 or shape[0][1] != 118 or any(s[0] not in (64, 128) for s in shape) or len(self.tower_network) != 1 or \
+                self.mmoe_layer.num_experts != 4 or self.mmoe_layer.out_dim != 8 or self.tower_network[0].out_features != 1:
+            raise ValueError("the device step trains the VirtualTaobao build only: 118 dense inputs, two hidden layers with widths from "
+                             "{64, 128}, 4 experts of dim 8, one regression task of logit dim 1")
+        self.metrics_names = ["loss"]
+        self.loss_func, self.metric_fun, self.metrics = loss_func, metric_fun, metrics
+        self.optim = "adam"
+        g = optimizer.param_groups[0] if isinstance(optimizer, torch.optim.Adam) else dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+        self._adam = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"])
+        self._trainer = None
+
+    def fit_data(self, dataset_train, dataset_val=None, batch_size=256, epochs=1, verbose=1, initial_epoch=0, callbacks=None, shuffle=True):
+        """One pass per epoch over (x, y, exposure) minibatches, the last one short; an epoch is one cirs_mmoe_train_epoch call on the
+        device-resident data set.  Returns [{"loss": summed total loss / sample count}, ...] like UserModel.fit_data."""
+        from cirs_hip.mmoe_train import MMoETrainer
+        assert self.optim is not None, "call compile() first"
+        if self._trainer is None:
+            self._trainer = MMoETrainer(self.state_dict(), l2_linear=self._l2[0], l2_all=self._l2[1], **self._adam)
+        tr = self._trainer
+        x = torch.as_tensor(dataset_train.x_numpy).to(tr.device, torch.float32).contiguous()
+        y = torch.as_tensor(dataset_train.y_numpy).to(tr.device, torch.float32).reshape(-1).contiguous()
+        score = torch.as_tensor(dataset_train.score).to(tr.device, torch.float32).reshape(-1).contiguous()
+        n_all = x.shape[0]
+        callbacks = callbacks or []
+        for cb in callbacks:
+            cb.on_train_begin()
+        history = []
+        for epoch in range(initial_epoch, epochs):
+            for cb in callbacks:
+                cb.on_epoch_begin(epoch)
+            order = torch.randperm(n_all, device=tr.device) if shuffle else torch.arange(n_all, device=tr.device)
+            losses = tr.epoch(x, y, score, order, batch_size)
+            logs = {"loss": float(losses.sum(dtype=torch.float64)) / n_all}       # total_loss_epoch / sample_num (core/user_model.py:205)
+            history.append(logs)
+            for cb in callbacks:
+                cb.on_epoch_end(epoch, logs)
+        for cb in callbacks:
+            cb.on_train_end()
+        with torch.no_grad():      # publish the trained parameters under the module's state_dict names
+            mine = dict(self.named_parameters())
+            for k, v in tr.state_dict().items():
+                mine[k].copy_(v.reshape(mine[k].shape).to(mine[k].device))
+        return history
+
+    def load_state_dict(self, state_dict, strict=True):
+        self._trainer = None       # the Adam moments belong to the parameters they were fitted on
+        return super().load_state_dict(state_dict, strict=strict)
 
     def forward(self, x):
         x = x.to(torch.float32)

@@ -56,3 +56,36 @@ def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, **ov
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, paths.state_dict)
     return SimpleNamespace(model=model, history=history, normed_mat=normed_mat, paths=paths, val_set=val_set,
                            lbe_user=lbe_user, lbe_photo=lbe_photo)
+
+
+TAOBAO_DEFAULTS = dict(env="VirtualTB-v0", user_model_name="MLP", message="UM", tau=0.01, feature_dim=8, dnn=(64, 64), batch_size=100,
+                       epoch=5, seed=2022)
+
+
+def train_user_model_taobao(dataset_path, save_root=".", callbacks=None, exposure_fn=None, shuffle=True, **overrides):
+    """The user-model training run of CIRS-UserModel-taobao.py:115-182 (`main`) without logging: the `dataset.txt`-shaped log ->
+    training set with its exposure effect -> UserModel_MMOE fitted on the device -> the two artefacts CIRS-RL-taobao.py:134-142 loads
+    (`<name>_params_<msg>.pickle`, `<name>_<msg>.pt`) under saved_models/VirtualTB-v0/<name>/, weights saved on the CPU.
+    Returns SimpleNamespace(model, history, paths, dataset).  The device SimulatedEnv steps a (128, 128) model only: pass
+    dnn=(128, 128) when the trained model is to drive `SimulatedEnv.build_device_env` (the script's default is (64, 64))."""
+    import collections
+    from core.user_data_taobao import load_dataset_virtualTaobao
+    from core.user_model_mmoe import UserModel_MMOE, loss_taobao
+    from deepctr_torch.inputs import DenseFeat
+    a = SimpleNamespace(**{**TAOBAO_DEFAULTS, **overrides})
+    model_dir = os.path.join(save_root, "saved_models", a.env, a.user_model_name)
+    os.makedirs(os.path.join(model_dir, "logs"), exist_ok=True)
+    dataset, x_columns, y_columns = load_dataset_virtualTaobao(a.tau, dataset_path, feature_dim=a.feature_dim, exposure_fn=exposure_fn)
+    tasks = collections.OrderedDict({feat.name: "regression" for feat in y_columns})
+    task_logit_dim = {feat.name: feat.dimension if isinstance(feat, DenseFeat) else feat.embedding_dim for feat in y_columns}
+    params = {"feature_columns": x_columns, "y_columns": y_columns, "num_tasks": len(tasks), "tasks": tasks, "task_logit_dim": task_logit_dim,
+              "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cpu"}
+    model = UserModel_MMOE(**params)
+    model.compile(optimizer="adam", loss_func=loss_taobao, metrics=None)
+    history = model.fit_data(dataset, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []), shuffle=shuffle) if a.epoch > 0 else []
+    paths = SimpleNamespace(params=os.path.join(model_dir, "{}_params_{}.pickle".format(a.user_model_name, a.message)),
+                            state_dict=os.path.join(model_dir, "{}_{}.pt".format(a.user_model_name, a.message)))
+    with open(paths.params, "wb") as fh:
+        pickle.dump(params, fh)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, paths.state_dict)
+    return SimpleNamespace(model=model, history=history, paths=paths, dataset=dataset)

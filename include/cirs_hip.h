@@ -930,6 +930,50 @@ int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_b
 int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
                           int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream);
 
+/* ---- VirtualTaobao user-model training (csrc/mmoe_train.hip) ---------------------------------------------------------------
+ * One optimiser step of UserModel_MMOE.fit_data's inner loop (reference core/user_model.py:150-170, core/user_model_mmoe.py:144-233,
+ * CIRS-UserModel-taobao.py:185-191) for the all-dense one-regression-task build cirs_vtb_mmoe_forward accepts:
+ *   h1 = relu(W1 x + b1); h2 = relu(W2 h1 + b2); experts = (We h2 + be) as [expert_dim, n_experts]; gate = softmax(Wg h2)
+ *   y_pred = (x . w_lin_task + tower . (experts @ gate)) + out_bias
+ *   loss = mean((y_pred / (1 + exposure) - y)^2 (y + 1))                                        (loss_taobao)
+ *   reg  = l2_linear |linear_model.weight|^2 + l2_all sum over EVERY parameter of |p|^2          (biases, gate and the unused
+ *          duplicate linear_model.weight included: add_regularization_weight(self.parameters(), l2_reg_dnn))
+ *   (loss + reg).backward(); torch.optim.Adam step (no weight decay, no amsgrad).
+ * Shapes: d_in 118, h1 and h2 from {64, 128}, 4 experts of dim 8, one task of logit dim 1; anything else: CIRS_E_UNSUPPORTED.
+ * Parameters, gradients and both Adam moments are flat fp32 buffers of cirs_mmoe_train_param_count(cfg) floats (16-byte aligned) in
+ * the order  dnn.linears.1.weight [h2,h1] | expert_network.weight [32,h2] | gating_networks.0.weight [4,h2]
+ *          | dnn.linears.0.weight TRANSPOSED [118,h1] | dnn.linears.0.bias [h1] | dnn.linears.1.bias [h2] | expert_network.bias [32]
+ *          | tower_network.0.weight [8] | linear_model.weight [118] | linear_model_task.0.weight [118] | out.0.bias [1].
+ * Two launches per step, every sum in a fixed order (no float atomics): two runs from one state give identical bits. */
+typedef struct cirs_mmoe_train_cfg {
+    int32_t d_in, h1, h2, n_experts, expert_dim, n_tasks, task_dim;
+    float l2_linear, l2_all;      /* the two regularisation lists of the reference (linear_model, all parameters)  */
+    float lr, beta1, beta2, eps;  /* torch.optim.Adam                                                              */
+} cirs_mmoe_train_cfg;
+int64_t cirs_mmoe_train_param_count(const cirs_mmoe_train_cfg* cfg);               /* 0 for an unsupported shape */
+int64_t cirs_mmoe_train_workspace_bytes(const cirs_mmoe_train_cfg* cfg, int32_t n); /* n = rows of the largest batch */
+/* one step on the batch x [n,118], y [n], exposure [n] (fp32, device); step_before = optimiser steps taken so far;
+ * loss_out[2] = {loss, reg} (device). */
+int cirs_mmoe_train_step(const cirs_mmoe_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                         int64_t step_before, const float* x, const float* y, const float* exposure, int32_t n, float* loss_out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+/* all steps of one pass: the data set x [n_rows,118], y [n_rows], exposure [n_rows] stays on the device, batch b is the rows
+ * order[b * batch_size .. min(n_order, (b + 1) * batch_size)) (int64, device, every entry in [0, n_rows); the last batch may be
+ * short, as in DataLoader).  losses_out [ceil(n_order / batch_size)][2] = per-step {loss, reg} (device).  The launches are queued
+ * back to back: no host synchronisation, no host round trip between steps.  Bit-identical to the same steps issued through
+ * cirs_mmoe_train_step.  workspace: cirs_mmoe_train_workspace_bytes(cfg, min(batch_size, n_order)). */
+int cirs_mmoe_train_epoch(const cirs_mmoe_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                          int64_t step_before, const float* x, const float* y, const float* exposure, int64_t n_rows,
+                          const int64_t* order, int64_t n_order, int32_t batch_size, float* losses_out, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+/* compute_exposure_effect_virtualTaobao (CIRS-UserModel-taobao.py:52-70).  Rows are in log order; a row whose timestamp is 1 opens a
+ * session: exposure_out[r] = sum_{j in [start(r), r)} exp(-(r - j) ||a_r - a_j||_2 / tau) in float64, 0 for a session's first row and
+ * for tau <= 0.  timestamp_host [n_rows] int32 in HOST memory (the session starts are found and checked on the host: a log whose
+ * first row does not open a session is refused, the reference would read an undefined `start` there); action [n_rows,27] float64,
+ * start_scratch [n_rows] int64 and exposure_out [n_rows] float64 on the device. */
+int cirs_vtb_exposure_history(const int32_t* timestamp_host, const double* action, int64_t n_rows, double tau,
+                              int64_t* start_scratch, double* exposure_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
