@@ -129,11 +129,15 @@ class VtbState(C.Structure):     # cirs_vtb_state
 VTB_RO_MAX_LAYERS, VTB_RO_MAX_HIDDEN = 4, 3
 
 
+class VtbModelCfg(C.Structure):      # cirs_vtb_model_cfg: the one description of the tracker + actor both stages embed
+    _fields_ = [(k, C.c_int32) for k in ("dim_model", "nhead", "d_hid", "nlayers", "dim_state", "max_len", "n_hidden")] + \
+        [("hidden", C.c_int32 * VTB_RO_MAX_HIDDEN), ("unbounded", C.c_int32), ("conditioned_sigma", C.c_int32), ("max_action", C.c_float),
+         ("dropout_p", C.c_float), ("drop_env_base", C.c_int32), ("dropout_seed", C.c_uint64)]
+
+
 class VtbRolloutCfg(C.Structure):    # cirs_vtb_rollout_cfg
-    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "force_length", "dim_model", "nhead", "d_hid", "nlayers", "dim_state", "max_len",
-                                         "n_hidden")] + [("hidden", C.c_int32 * VTB_RO_MAX_HIDDEN)] + \
-        [(k, C.c_int32) for k in ("unbounded", "conditioned_sigma", "bound_method", "action_scaling")] + \
-        [("max_action", C.c_float), ("dropout_p", C.c_float), ("drop_env_base", C.c_int32), ("dropout_seed", C.c_uint64), ("env_seed", C.c_uint64)]
+    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "force_length", "bound_method", "action_scaling")] + \
+        [("model", VtbModelCfg), ("env_seed", C.c_uint64)]
 
 
 VTB_LAYER_FIELDS = ("in_w", "in_b", "out_w", "out_b", "lin1_w", "lin1_b", "lin2_w", "lin2_b", "norm1_w", "norm1_b", "norm2_w", "norm2_b")
@@ -158,9 +162,7 @@ class VtbTraj(C.Structure):          # cirs_vtb_traj
 
 
 class VtbLearnCfg(C.Structure):      # cirs_vtb_learn_cfg
-    _fields_ = [(k, C.c_int32) for k in ("n_env", "max_turn", "dim_model", "nhead", "d_hid", "nlayers", "dim_state", "max_len", "n_hidden")] + \
-        [("hidden", C.c_int32 * VTB_RO_MAX_HIDDEN), ("unbounded", C.c_int32), ("conditioned_sigma", C.c_int32), ("max_action", C.c_float),
-         ("dropout_p", C.c_float), ("drop_env_base", C.c_int32), ("dropout_seed", C.c_uint64)] + \
+    _fields_ = [("n_env", C.c_int32), ("max_turn", C.c_int32), ("model", VtbModelCfg)] + \
         [(k, C.c_int32) for k in ("n_rows", "n_seg", "scale_returns", "whiten_adv", "clip_value", "has_dual", "has_max_norm")] + \
         [(k, C.c_float) for k in ("clip", "dual", "c_value", "c_entropy", "max_norm")] + [(k, C.c_double) for k in ("discount", "lam", "floor")] + \
         [(k, C.c_float) for k in ("lr", "beta1", "beta2", "eps", "t_lr", "t_beta1", "t_beta2", "t_eps")]

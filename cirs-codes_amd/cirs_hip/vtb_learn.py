@@ -4,7 +4,7 @@ cirs_vtb_learn_prepare / cirs_vtb_learn_update.
 The torch modules and optimisers stay authoritative between updates.  An update packs the tracker and policy parameters and their Adam
 moments into flat fp32 images (torch's [out][in] layout, module registration order; one H2D copy), runs the whole update on the device
 with the host-drawn row permutations, and writes everything back in place (p.data.copy_, the optimisers' state entries, ret_rms)
-after one D2H copy.  Layout and refusals: `policy_params`, `tracker_params`, `check_optimisers` (pure host code, no library needed)."""
+after one D2H copy.  Layout and refusals: cirs_hip/vtb_model.py and `check_optimisers` (pure host code, no library needed)."""
 import ctypes as C
 from typing import Dict, List
 
@@ -12,55 +12,18 @@ import numpy as np
 import torch
 from torch import nn
 
-from .vtb_host import ACTION_DIM
+from .vtb_model import VtbModel, policy_tensors, stream, tracker_tensors, u64
 
 
 # ---- the parameter images (pure host code) ----------------------------------------------------------------------------------
-def _linears(mlp, what):
-    mods = list(mlp.model)
-    for m in mods:
-        if not isinstance(m, (nn.Linear, nn.ReLU)):
-            raise ValueError(f"{what}: only Linear + ReLU layers are supported by the device learner, found {type(m).__name__}")
-    return [m for m in mods if isinstance(m, nn.Linear)]
-
-
 def policy_params(actor, critic) -> List[nn.Parameter]:
-    """The policy image's parameters in order: trunk W b per layer | mu W b | sigma W b or sigma_param | critic W b.  The trunk
-    (shared Net) comes first; refuses shapes the device learner does not build."""
-    from tianshou.utils.net.continuous import ActorProb
-    if not isinstance(actor, ActorProb):
-        raise ValueError("learner='device' needs a continuous ActorProb actor (Independent(Normal) policy)")
-    if critic.preprocess is not actor.preprocess:
-        raise ValueError("learner='device' needs actor and critic over one shared Net trunk (CIRS-RL-taobao.py)")
-    trunk = _linears(actor.preprocess.model, "actor trunk")
-    mu = _linears(actor.mu, "actor mu head")
-    sig = _linears(actor.sigma, "actor sigma head") if actor._c_sigma else []
-    last = _linears(critic.last, "critic head")
-    if len(mu) != 1 or (actor._c_sigma and len(sig) != 1) or len(last) != 1:
-        raise ValueError("ActorProb / Critic heads with hidden layers are not supported by the device learner (hidden_sizes=() only)")
-    if int(actor.output_dim) != ACTION_DIM:
-        raise ValueError(f"the actor must output the {ACTION_DIM} VirtualTaobao action features")
-    if not 1 <= len(trunk) <= 3 or any(m.out_features > 128 for m in trunk) or trunk[0].in_features > 128:
-        raise ValueError("the trunk must be a Net of 1..3 hidden layers of width <= 128")
-    out = [p for m in trunk for p in (m.weight, m.bias)] + [mu[0].weight, mu[0].bias]
-    out += [sig[0].weight, sig[0].bias] if actor._c_sigma else [actor.sigma_param]
-    out += [last[0].weight, last[0].bias]
-    if any(p is None for p in out):
-        raise ValueError("every Linear of the device learner needs a bias")
-    return out
+    """The policy image's parameters in order (vtb_model.py policy_tensors); refuses shapes the device learner does not build."""
+    return [p for _, p in policy_tensors(actor, critic)]
 
 
 def tracker_params(tracker) -> List[nn.Parameter]:
-    """The tracker image's parameters in order (HostStateTracker registration order)."""
-    out = [tracker.ffn_user.weight, tracker.ffn_user.bias, tracker.fnn_gate.weight, tracker.fnn_gate.bias]
-    for ly in tracker.transformer_encoder.layers:
-        if getattr(ly, "norm_first", False) or getattr(ly.activation, "__name__", "relu") != "relu":
-            raise ValueError("the device learner builds post-norm ReLU TransformerEncoderLayers")
-        out += [ly.self_attn.in_proj_weight, ly.self_attn.in_proj_bias, ly.self_attn.out_proj.weight, ly.self_attn.out_proj.bias,
-                ly.linear1.weight, ly.linear1.bias, ly.linear2.weight, ly.linear2.bias, ly.norm1.weight, ly.norm1.bias, ly.norm2.weight,
-                ly.norm2.bias]
-    out += [tracker.decoder.weight, tracker.decoder.bias]
-    return out
+    """The tracker image's parameters in order (vtb_model.py tracker_tensors: HostStateTracker registration order)."""
+    return [p for _, p in tracker_tensors(tracker)]
 
 
 def check_optimisers(optim, ppar, tpar):
@@ -159,17 +122,11 @@ class DeviceVtbLearner:
     def __init__(self, tracker, actor, critic, n_env, max_turn, device):
         from . import abi
         self.tracker, self.actor, self.critic = tracker, actor, critic
-        self.ppar, self.tpar = policy_params(actor, critic), tracker_params(tracker)
+        self.model = VtbModel(tracker, actor, critic)
+        self.ppar, self.tpar = [p for _, p in self.model.policy_tensors()], [p for _, p in self.model.tracker_tensors()]
         self.n_env, self.max_turn, self.device = int(n_env), int(max_turn), torch.device(device)
         self._lib, self._abi = abi.lib(), abi
-        layers = tracker.transformer_encoder.layers
-        trunk = _linears(actor.preprocess.model, "actor trunk")
-        hidden = [int(m.out_features) for m in trunk] + [0] * (abi.VTB_RO_MAX_HIDDEN - len(trunk))
-        self.cfg = abi.VtbLearnCfg(n_env=self.n_env, max_turn=self.max_turn, dim_model=int(tracker.dim_model),
-                                   nhead=int(layers[0].self_attn.num_heads), d_hid=int(layers[0].linear1.out_features), nlayers=len(layers),
-                                   dim_state=int(tracker.dim_state), max_len=int(tracker.MAX_TURN), n_hidden=len(trunk),
-                                   hidden=(C.c_int32 * abi.VTB_RO_MAX_HIDDEN)(*hidden), unbounded=int(bool(actor._unbounded)),
-                                   conditioned_sigma=int(bool(actor._c_sigma)), max_action=float(actor._max))
+        self.cfg = abi.VtbLearnCfg(n_env=self.n_env, max_turn=self.max_turn, model=self.model.model_cfg())
         self._rows_cap = 0
         self.ws = None
         self.pe = tracker.pos_encoder.pe[:, 0, :].detach().float().contiguous().to(self.device)
@@ -180,9 +137,6 @@ class DeviceVtbLearner:
         out = (C.c_int64 * 5)()
         self._abi.check(self._lib.cirs_vtb_learn_sizes(C.byref(self.cfg), C.cast(out, C.c_void_p)), "cirs_vtb_learn_sizes")
         return [int(x) for x in out]
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     # ---- one update ---------------------------------------------------------------------------------------------------------
     def prepare(self, policy, rows_src, rows, buffer):
@@ -200,12 +154,12 @@ class DeviceVtbLearner:
         head_steps = {int(float(opt_p.state[p]["step"])) if "step" in opt_p.state.get(p, {}) else 0 for p in self.ppar[self.n_trunk:]}
         if len(head_steps) != 1 or len(tsteps) != 1 or trunk_steps != {2 * next(iter(head_steps))}:
             raise ValueError("learner='device' needs one Adam step count per optimiser (the shared trunk at twice the heads')")
-        assert pflat.numel() == n_pol and tflat.numel() == n_trk, "parameter image layout differs from csrc/vtb_learn.hip"
+        assert pflat.numel() == n_pol and tflat.numel() == n_trk, "parameter image size differs from csrc/vtb_learn.hip"
         self.p_step0, self.t_step0 = next(iter(head_steps)), next(iter(tsteps))
         host = torch.cat([tflat, tm, tv, pflat, pm, pv]).pin_memory()
         img = host.to(dev, non_blocking=True)
-        o = np.cumsum([0, n_trk, n_trk, n_trk, n_pol, n_pol, n_pol])
-        self.tflat, self.tm, self.tv, self.pflat, self.pm, self.pv = (img[o[i]:o[i + 1]] for i in range(6))
+        self._split = [n_trk] * 3 + [n_pol] * 3      # tracker image, m, v | policy image, m, v
+        self.tflat, self.tm, self.tv, self.pflat, self.pm, self.pv = img.split(self._split)
         self.img = img
         # sample tables
         size = buffer.size
@@ -232,9 +186,8 @@ class DeviceVtbLearner:
         c.discount, c.lam, c.floor = float(h.discount), float(h.lam), float(h.floor)
         c.lr, c.beta1, c.beta2, c.eps = _hyper(opt_p)
         c.t_lr, c.t_beta1, c.t_beta2, c.t_eps = _hyper(opt_t)
-        c.dropout_p = float(rows_src.dropout_p)
-        c.drop_env_base = int(rows_src.rollout.cfg.drop_env_base)
-        c.dropout_seed = int(rows_src.dropout_seed) & 0xFFFFFFFFFFFFFFFF
+        # the dropout key of the collect the rows come from: the forward pass regenerates that collect's masks
+        c.model.dropout_p, c.model.drop_env_base, c.model.dropout_seed = rows_src.dropout_p, rows_src.drop_env_base, u64(rows_src.dropout_seed)
         tr = rows_src.rollout.traj
         p = lambda x: x.data_ptr()      # noqa: E731
         base = self.ints.data_ptr()
@@ -243,11 +196,11 @@ class DeviceVtbLearner:
                                            done=p(tr["done"]), act=p(tr["act"]), len=p(tr["len"]), rows=base, boundary=p(self.bnd),
                                            seg_end=base + 4 * int(oi[1]), grad_rows=base + 4 * int(oi[2]), grad_start=base + 4 * int(oi[3]),
                                            rms=p(self.rms), ws=p(self.ws), losses=0)
-        self._abi.check(self._lib.cirs_vtb_learn_prepare(C.byref(c), C.byref(self.bufs), self._stream()), "cirs_vtb_learn_prepare")
+        self._abi.check(self._lib.cirs_vtb_learn_prepare(C.byref(c), C.byref(self.bufs), stream(self.device)), "cirs_vtb_learn_prepare")
 
     def states(self):
         """The learner's tracker states [max_turn + 1, n_env, dim_state] of the last prepare (device view)."""
-        o, T, B, S = self.states_off, self.max_turn, self.n_env, self.cfg.dim_state
+        o, T, B, S = self.states_off, self.max_turn, self.n_env, self.cfg.model.dim_state
         return self.ws[o:o + (T + 1) * B * S].view(T + 1, B, S)
 
     def row_block(self):
@@ -265,14 +218,12 @@ class DeviceVtbLearner:
         self.bufs.losses = losses.data_ptr()
         self._abi.check(self._lib.cirs_vtb_learn_update(C.byref(self.cfg), C.byref(self.bufs), perm_d.data_ptr(), int(repeat), int(batch_size),
                                                         int(bool(policy.hyper.refresh_adv)), int(self.p_step0), int(self.t_step0),
-                                                        self._stream()), "cirs_vtb_learn_update")
+                                                        stream(self.device)), "cirs_vtb_learn_update")
         back = torch.cat([self.img, losses.reshape(-1)]).cpu()
         rms = self.rms.cpu().numpy()
         n_img = self.img.numel()
         img, lo = back[:n_img], back[n_img:n_img + 4 * n_mb].view(n_mb, 4).numpy()
-        n_trk, n_pol = self.tflat.numel(), self.pflat.numel()
-        o = np.cumsum([0, n_trk, n_trk, n_trk, n_pol, n_pol, n_pol])
-        tflat, tm, tv, pflat, pm, pv = (img[o[i]:o[i + 1]] for i in range(6))
+        tflat, tm, tv, pflat, pm, pv = img.split(self._split)
         opt_p, opt_t = policy.optim
         k = n_mb
         unpack_image(self.tpar, opt_t, tflat, tm, tv, [self.t_step0 + 1] * len(self.tpar))

@@ -6,27 +6,44 @@ vector step and no host synchronisation until the collect ends.  The parameters 
 modules): before every collect they are packed into one flat fp32 buffer and sent up with one H2D copy.
 """
 import ctypes as C
+import operator
 
 import numpy as np
 import torch
-from torch import nn
 
 from . import abi
 from .vtb_host import ACTION_DIM, DROP_ATTN, DROP_FF, DROP_POS, DROP_RES1, DROP_RES2, USER_DIM
+from .vtb_model import VtbModel, stream, u64
 
 _BOUND = {"": 0, None: 0, "clip": 1, "tanh": 2}
 
 
-def _linears(mlp, what):
-    """The nn.Linear layers of a tianshou MLP; every hidden layer must be followed by a ReLU."""
-    mods = list(mlp.model)
-    lin = [m for m in mods if isinstance(m, nn.Linear)]
-    for i, m in enumerate(mods):
-        if isinstance(m, nn.Linear):
-            continue
-        if not isinstance(m, nn.ReLU):
-            raise ValueError(f"{what}: only Linear + ReLU layers are supported, found {type(m).__name__}")
-    return lin
+def image_parts(model, policy):
+    """The rollout's flat parameter image as (name, tensor, transposed, offset in floats) in order, and its total floats: the model's
+    tensors without the critic's, a matrix stored transposed ([out][in] -> [in][out]) and a vector flat, plus the rollout's own pe (after
+    the input slot's) and action box; every tensor 16-byte aligned."""
+    parts = [(name, p, p.dim() == 2) for name, p in model.tracker_tensors() + model.policy_tensors() if not name.startswith("critic")]
+    parts.insert(4, ("pe", model.tracker.pos_encoder.pe[:, 0, :], False))
+    if policy.action_scaling:
+        box = policy.action_space
+        parts += [(k, torch.as_tensor(np.asarray(v, np.float32)), False) for k, v in (("act_low", box.low), ("act_high", box.high))]
+    offs = np.concatenate([[0], np.cumsum([(p.numel() + 3) // 4 * 4 for _, p, _ in parts])])
+    return [part + (int(o),) for part, o in zip(parts, offs)], int(offs[-1])
+
+
+def fill_image(host, parts):
+    for _, p, transposed, o in parts:
+        src = p.detach().to(torch.float32)
+        host[o:o + p.numel()] = (src.t() if transposed else src).reshape(-1)
+
+
+def _weight_slots(w, nlayers, n_hidden):
+    """name of an image part -> (setter, holder, key): where its pointer goes in cirs_vtb_policy_weights."""
+    slots = {k: (setattr, w, k) for k in ("user_w", "user_b", "gate_w", "gate_b", "pe", "dec_w", "dec_b", "mu_w", "mu_b", "sigma_w", "sigma_b",
+                                          "sigma_param", "act_low", "act_high")}
+    slots.update({f"layer{l}.{k}": (setattr, w.layer[l], k) for l in range(nlayers) for k in abi.VTB_LAYER_FIELDS})
+    slots.update({f"trunk{i}_{k}": (operator.setitem, getattr(w, f"trunk_{k}"), i) for i in range(n_hidden) for k in "wb"})
+    return slots
 
 
 class DeviceVtbRollout:
@@ -34,87 +51,34 @@ class DeviceVtbRollout:
     HostPPOPolicy that maps its actions."""
 
     def __init__(self, vtb, tracker, actor, policy, force_length=0):
-        from tianshou.utils.net.continuous import ActorProb
-        if not isinstance(actor, ActorProb):
-            raise TypeError("the device VirtualTaobao rollout needs a continuous ActorProb actor (Independent(Normal) policy)")
+        self.model = VtbModel(tracker, actor)
         self.vtb, self.tracker, self.actor, self.policy = vtb, tracker, actor, policy
         self.device = vtb.device
         B, T = vtb.n_env, vtb.max_turn
-        layers = tracker.transformer_encoder.layers
-        D, S = int(tracker.dim_model), int(tracker.dim_state)
-        nhead = int(layers[0].self_attn.num_heads)
-        d_hid = int(layers[0].linear1.out_features)
-        trunk = _linears(actor.preprocess.model, "actor trunk")
-        mu = _linears(actor.mu, "actor mu head")
-        if len(mu) != 1:
-            raise ValueError("ActorProb heads with hidden layers are not supported by the device rollout (hidden_sizes=() only)")
-        sig = _linears(actor.sigma, "actor sigma head") if actor._c_sigma else []
-        if actor._c_sigma and len(sig) != 1:
-            raise ValueError("a conditioned sigma head with hidden layers is not supported by the device rollout")
-        if int(actor.output_dim) != ACTION_DIM:
-            raise ValueError(f"the actor must output the {ACTION_DIM} VirtualTaobao action features")
-        if not 1 <= len(trunk) <= 3 or trunk[0].in_features != S:
-            raise ValueError("the actor trunk must be a Net of 1..3 hidden layers over the tracker state")
         if policy.action_bound_method not in _BOUND:
             raise ValueError(f"unsupported action_bound_method {policy.action_bound_method!r}")
-        hidden = [int(m.out_features) for m in trunk] + [0] * (abi.VTB_RO_MAX_HIDDEN - len(trunk))
-        self.cfg = abi.VtbRolloutCfg(n_env=B, max_turn=T, force_length=int(force_length), dim_model=D, nhead=nhead, d_hid=d_hid,
-                                     nlayers=len(layers), dim_state=S, max_len=int(tracker.MAX_TURN), n_hidden=len(trunk),
-                                     hidden=(C.c_int32 * abi.VTB_RO_MAX_HIDDEN)(*hidden), unbounded=int(bool(actor._unbounded)),
-                                     conditioned_sigma=int(bool(actor._c_sigma)), bound_method=_BOUND[policy.action_bound_method],
-                                     action_scaling=int(bool(policy.action_scaling)), max_action=float(actor._max))
-        # the flat parameter image: (name, host fp32 tensor of the kernel's layout) in a fixed order
-        t_ = lambda w: w.detach().to(torch.float32).t()      # noqa: E731  [out, in] -> [in, out]
-        v_ = lambda w: w.detach().to(torch.float32).reshape(-1)   # noqa: E731
-        parts = [("user_w", lambda: t_(tracker.ffn_user.weight)), ("user_b", lambda: v_(tracker.ffn_user.bias)),
-                 ("gate_w", lambda: t_(tracker.fnn_gate.weight)), ("gate_b", lambda: v_(tracker.fnn_gate.bias)),
-                 ("pe", lambda: v_(tracker.pos_encoder.pe[:, 0, :]))]
-        for l, ly in enumerate(layers):
-            parts += [((l, "in_w"), lambda ly=ly: t_(ly.self_attn.in_proj_weight)), ((l, "in_b"), lambda ly=ly: v_(ly.self_attn.in_proj_bias)),
-                      ((l, "out_w"), lambda ly=ly: t_(ly.self_attn.out_proj.weight)), ((l, "out_b"), lambda ly=ly: v_(ly.self_attn.out_proj.bias)),
-                      ((l, "lin1_w"), lambda ly=ly: t_(ly.linear1.weight)), ((l, "lin1_b"), lambda ly=ly: v_(ly.linear1.bias)),
-                      ((l, "lin2_w"), lambda ly=ly: t_(ly.linear2.weight)), ((l, "lin2_b"), lambda ly=ly: v_(ly.linear2.bias)),
-                      ((l, "norm1_w"), lambda ly=ly: v_(ly.norm1.weight)), ((l, "norm1_b"), lambda ly=ly: v_(ly.norm1.bias)),
-                      ((l, "norm2_w"), lambda ly=ly: v_(ly.norm2.weight)), ((l, "norm2_b"), lambda ly=ly: v_(ly.norm2.bias))]
-        parts += [("dec_w", lambda: t_(tracker.decoder.weight)), ("dec_b", lambda: v_(tracker.decoder.bias))]
-        for i, m in enumerate(trunk):
-            parts += [(("trunk_w", i), lambda m=m: t_(m.weight)), (("trunk_b", i), lambda m=m: v_(m.bias))]
-        parts += [("mu_w", lambda: t_(mu[0].weight)), ("mu_b", lambda: v_(mu[0].bias))]
-        if actor._c_sigma:
-            parts += [("sigma_w", lambda: t_(sig[0].weight)), ("sigma_b", lambda: v_(sig[0].bias))]
-        else:
-            parts += [("sigma_param", lambda: v_(actor.sigma_param))]
-        if policy.action_scaling:
-            box = policy.action_space
-            low, high = torch.as_tensor(np.asarray(box.low, np.float32)), torch.as_tensor(np.asarray(box.high, np.float32))
-            parts += [("act_low", lambda: low.reshape(-1)), ("act_high", lambda: high.reshape(-1))]
-        self._parts = parts
-        sizes = [int(f().numel()) for _, f in parts]
-        offs = np.concatenate([[0], np.cumsum([(n + 3) // 4 * 4 for n in sizes])])      # 16-byte aligned tensors
-        self.flat = torch.zeros(int(offs[-1]), dtype=torch.float32, device=self.device)
-        self._host = torch.zeros(int(offs[-1]), dtype=torch.float32, pin_memory=True)
-        self._slices = [(int(o), n) for o, n in zip(offs[:-1], sizes)]
-        w = abi.VtbPolicyWeights()
-        base, fsz = self.flat.data_ptr(), 4
-        for (name, _), (o, _n) in zip(parts, self._slices):
-            p = base + fsz * o
-            if isinstance(name, tuple) and isinstance(name[0], int):
-                setattr(w.layer[name[0]], name[1], p)
-            elif isinstance(name, tuple):
-                getattr(w, name[0])[name[1]] = p
-            else:
-                setattr(w, name, p)
-        self._w = w
+        m = self.model.model_cfg()
+        self.cfg = abi.VtbRolloutCfg(n_env=B, max_turn=T, force_length=int(force_length), bound_method=_BOUND[policy.action_bound_method],
+                                     action_scaling=int(bool(policy.action_scaling)), model=m)
+        D, S, L, nlayers = m.dim_model, m.dim_state, m.max_len, m.nlayers
+        # the flat parameter image: one pinned staging buffer, one device buffer, the kernel's pointers into it
+        self._parts, total = image_parts(self.model, policy)
+        self.flat = torch.zeros(total, dtype=torch.float32, device=self.device)
+        self._host = torch.zeros(total, dtype=torch.float32, pin_memory=True)
+        self._w = abi.VtbPolicyWeights()
+        slots = _weight_slots(self._w, nlayers, m.n_hidden)
+        for name, _, _, o in self._parts:
+            put, holder, key = slots[name]
+            put(holder, key, self.flat.data_ptr() + 4 * o)
         # trajectory + scratch
         dev = self.device
         f32, f64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.float64, device=dev)
-        L = int(tracker.MAX_TURN)
         self.traj = dict(state=torch.zeros((T + 1, B, S), **f32), act=torch.zeros((T, B, ACTION_DIM), **f32),
                          act_mapped=torch.zeros((T, B, ACTION_DIM), **f32), obs0=torch.zeros((B, USER_DIM + 3), **f64),
                          obs=torch.zeros((T, B, ACTION_DIM + 3), **f64), rew=torch.zeros((T, B), **f64),
                          done=torch.zeros((T, B), dtype=torch.uint8, device=dev), ctr=torch.zeros((T, B), **f64),
                          len=torch.zeros(B, dtype=torch.int32, device=dev),
-                         kcache=torch.zeros((len(layers), B, L, D), **f32), vcache=torch.zeros((len(layers), B, L, D), **f32),
+                         kcache=torch.zeros((nlayers, B, L, D), **f32), vcache=torch.zeros((nlayers, B, L, D), **f32),
                          lists=torch.zeros((T + 1, B), dtype=torch.int32, device=dev), counts=torch.zeros(T + 1, dtype=torch.int32, device=dev),
                          act_buf=torch.zeros((B, ACTION_DIM), **f32), step_obs=torch.zeros((B, ACTION_DIM + 3), **f64),
                          step_rew=torch.zeros(B, **f64), step_ctr=torch.zeros(B, **f64),
@@ -122,31 +86,24 @@ class DeviceVtbRollout:
         self._tr = abi.VtbTraj(**{k: self.traj[k].data_ptr() for k in abi.VTB_TRAJ_FIELDS})
         self._lib = abi.lib()
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def pack(self):
         """The current host parameters -> the device image (one H2D copy)."""
-        for (_, f), (o, n) in zip(self._parts, self._slices):
-            self._host[o:o + n] = f().reshape(-1)
+        fill_image(self._host, self._parts)
         self.flat.copy_(self._host, non_blocking=True)
 
-    @property
-    def dropout_p(self):
-        """nn.Dropout is live while the tracker is in training mode (the reference never switches it off)."""
-        return float(self.tracker.pos_encoder.dropout.p) if self.tracker.training else 0.0
+    dropout_p = property(lambda self: self.model.dropout_p)
 
     def collect(self, seed, collect_id, dropout_seed=0, force_length=None):
         """One collect of every env; returns the episode lengths (numpy, the only synchronisation)."""
         if force_length is not None:
             self.cfg.force_length = int(force_length)
-        self.cfg.dropout_p = self.dropout_p
-        self.cfg.dropout_seed = int(dropout_seed) & 0xFFFFFFFFFFFFFFFF
-        self.cfg.env_seed = int(self.vtb._seed) & 0xFFFFFFFFFFFFFFFF
+        self.cfg.model.dropout_p = self.dropout_p
+        self.cfg.model.dropout_seed = u64(dropout_seed)
+        self.cfg.env_seed = u64(self.vtb._seed)
         self.pack()
         abi.check(self._lib.cirs_vtb_rollout_collect(C.byref(self.cfg), C.byref(self._w), C.byref(self.vtb.cfg), C.byref(self.vtb._wst),
-                                                     C.byref(self.vtb._st), C.byref(self._tr), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                                     int(collect_id) & 0xFFFFFFFF, self._stream()), "cirs_vtb_rollout_collect")
+                                                     C.byref(self.vtb._st), C.byref(self._tr), u64(seed), int(collect_id) & 0xFFFFFFFF,
+                                                     stream(self.device)), "cirs_vtb_rollout_collect")
         lens = self.traj["len"].cpu().numpy().astype(np.int64)
         self.vtb.host_turn[:] = lens          # the env's turns as the host tracks them (DeviceVirtualTB._check_turns)
         self.vtb._was_reset[:] = True
@@ -158,24 +115,25 @@ class DeviceVtbRollout:
         ids = torch.as_tensor(np.asarray(env_ids, np.int32).reshape(-1), device=self.device)
         tt = torch.as_tensor(np.asarray(ts, np.int32).reshape(-1), device=self.device)
         out = torch.empty((ids.numel(), dims), dtype=torch.float32, device=self.device)
-        abi.check(self._lib.cirs_vtb_rollout_noise(int(seed) & 0xFFFFFFFFFFFFFFFF, int(collect_id) & 0xFFFFFFFF, ids.data_ptr(), tt.data_ptr(),
-                                                   ids.numel(), dims, out.data_ptr(), self._stream()), "cirs_vtb_rollout_noise")
+        abi.check(self._lib.cirs_vtb_rollout_noise(u64(seed), int(collect_id) & 0xFFFFFFFF, ids.data_ptr(), tt.data_ptr(), ids.numel(), dims,
+                                                   out.data_ptr(), stream(self.device)), "cirs_vtb_rollout_noise")
         return out
 
     def masks(self, dropout_seed, n_pos, env0=0, n_env=None, p=None):
         """The scaled keep masks of positions 0..n_pos-1 in the layout vtb_host.states_from_slots takes (host fp32 tensors)."""
         lib, B = self._lib, self.vtb.n_env if n_env is None else n_env
         p = self.dropout_p if p is None else p
-        D, H, d_hid = self.cfg.dim_model, self.cfg.nhead, self.cfg.d_hid
+        mc = self.cfg.model
+        D, H, d_hid = mc.dim_model, mc.nhead, mc.d_hid
 
         def one(layer, site, n_elem):
             out = torch.empty((B, n_pos, n_elem), dtype=torch.float32, device=self.device)
-            abi.check(lib.cirs_vtb_rollout_masks(int(dropout_seed) & 0xFFFFFFFFFFFFFFFF, float(p), int(self.cfg.drop_env_base) + env0, B, 0, n_pos,
-                                                 layer, site, n_elem, out.data_ptr(), self._stream()), "cirs_vtb_rollout_masks")
+            abi.check(lib.cirs_vtb_rollout_masks(u64(dropout_seed), float(p), int(mc.drop_env_base) + env0, B, 0, n_pos, layer, site, n_elem,
+                                                 out.data_ptr(), stream(self.device)), "cirs_vtb_rollout_masks")
             return out.cpu()
 
         m = {"pos": one(0, DROP_POS, D)}
-        for l in range(self.cfg.nlayers):
+        for l in range(mc.nlayers):
             m[(l, DROP_ATTN)] = one(l, DROP_ATTN, n_pos * H)
             m[(l, DROP_RES1)] = one(l, DROP_RES1, D)
             m[(l, DROP_FF)] = one(l, DROP_FF, d_hid)

@@ -27,7 +27,6 @@ def _splitmix64(x: int) -> int:
 def check_device_vtb(policy, env, preprocess_fn):
     """Raise a clear error unless (device VirtualTB vector env, HostStateTracker.build_state, HostPPOPolicy over ActorProb)."""
     from core.host_rl import HostPPOPolicy, HostStateTracker
-    from tianshou.utils.net.continuous import ActorProb
     if not getattr(env, "host_mode", False):
         raise ValueError("rollout='device' runs the VirtualTaobao rollout; KuaishouEnv vector envs always collect on the device "
                          "(build the Collector without rollout=)")
@@ -38,9 +37,11 @@ def check_device_vtb(policy, env, preprocess_fn):
         raise ValueError("rollout='device' needs preprocess_fn=tracker.build_state of the VirtualTB-v0 StateTrackerTransformer")
     if not isinstance(policy, HostPPOPolicy):
         raise ValueError("rollout='device' needs the VirtualTB-v0 PPOPolicy (core.host_rl.HostPPOPolicy)")
-    if policy.action_type != "continuous" or not isinstance(policy.actor, ActorProb):
+    if policy.action_type != "continuous":
         raise ValueError("rollout='device' needs a continuous ActorProb actor with an Independent(Normal) policy; "
                          "discrete actors are collected by the host loop")
+    from cirs_hip.vtb_model import VtbModel
+    VtbModel(tracker, policy.actor)      # the actor's class and shape: refused here, before anything touches the GPU
     return tracker
 
 

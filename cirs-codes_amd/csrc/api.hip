@@ -51,4 +51,4 @@ extern "C" int cirs_prof_stop(double* total_seconds, int32_t* n_samples) {
 }
 
 extern "C" const char* cirs_last_error(void) { return cirs::g_last_error.c_str(); }
-extern "C" int cirs_version(void) { return 100; }
+extern "C" int cirs_version(void) { return 101; }

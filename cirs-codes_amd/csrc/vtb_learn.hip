@@ -19,6 +19,7 @@
 // the return statistics, the advantage moments and the gradient norm.  Parameter images are in torch's [out][in] layout.
 #include "common.h"
 #include "rng.h"
+#include "vtb_model.h"
 
 namespace cirs {
 namespace {
@@ -61,12 +62,12 @@ struct Lay {
 
 Lay make_layout(const cirs_vtb_learn_cfg& c) {
     Lay L{};
-    const long D = c.dim_model, F = c.d_hid, S = c.dim_state, H = c.nhead;
+    const long D = c.model.dim_model, F = c.model.d_hid, S = c.model.dim_state, H = c.model.nhead;
     long o = 0;
     auto take = [&o](long n) { const long r = o; o += n; return r; };
     L.t.user_w = take(D * kU); L.t.user_b = take(D);
     L.t.gate_w = take(D * (1 + kA)); L.t.gate_b = take(D);
-    for (int l = 0; l < c.nlayers; ++l) {
+    for (int l = 0; l < c.model.nlayers; ++l) {
         L.t.in_w[l] = take(3 * D * D); L.t.in_b[l] = take(3 * D);
         L.t.out_w[l] = take(D * D); L.t.out_b[l] = take(D);
         L.t.l1_w[l] = take(F * D); L.t.l1_b[l] = take(F);
@@ -79,16 +80,16 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
 
     o = 0;
     long in = S;
-    for (int i = 0; i < c.n_hidden; ++i) {
+    for (int i = 0; i < c.model.n_hidden; ++i) {
         L.p.tin[i] = in;
-        L.p.tw[i] = take((long)c.hidden[i] * in);
-        L.p.tb[i] = take(c.hidden[i]);
-        in = c.hidden[i];
+        L.p.tw[i] = take((long)c.model.hidden[i] * in);
+        L.p.tb[i] = take(c.model.hidden[i]);
+        in = c.model.hidden[i];
     }
     L.p.width = (int)in;
     L.p.trunk_end = o;
     L.p.mu_w = take(kA * in); L.p.mu_b = take(kA);
-    if (c.conditioned_sigma) {
+    if (c.model.conditioned_sigma) {
         L.p.sg_w = take(kA * in); L.p.sg_b = take(kA); L.p.sp = -1;
     } else {
         L.p.sg_w = L.p.sg_b = -1; L.p.sp = take(kA);
@@ -99,8 +100,8 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
     const long Lp = c.max_turn + 1;
     L.Lp = (int)Lp;
     o = 0;
-    L.e.X = take((c.nlayers + 1) * Lp * D);
-    for (int l = 0; l < c.nlayers; ++l) {
+    L.e.X = take((c.model.nlayers + 1) * Lp * D);
+    for (int l = 0; l < c.model.nlayers; ++l) {
         L.e.QKV[l] = take(Lp * 3 * D);
         L.e.P[l] = take(H * Lp * Lp);
         L.e.PM[l] = take(H * Lp * Lp);
@@ -116,7 +117,7 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
     L.e.total = (o + 3) / 4 * 4;
 
     long sumh = 0;
-    for (int i = 0; i < c.n_hidden; ++i) sumh += c.hidden[i];
+    for (int i = 0; i < c.model.n_hidden; ++i) sumh += c.model.hidden[i];
     const long n = c.n_rows, B = c.n_env;
     o = 0;
     L.w.states = take(Lp * B * S);
@@ -139,7 +140,7 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
 
 // keep decision of (position, layer, site, element) of this episode (csrc/rng.h; needs c, denv, thr in scope)
 #define LEARN_KEEP(P, LAYER, SITE, ELEM) \
-    dropout_keep(c.dropout_seed, denv, (uint32_t)(P), (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), thr)
+    dropout_keep(c.model.dropout_seed, denv, (uint32_t)(P), (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), thr)
 
 __device__ __forceinline__ float sigm(float g) { return 1.0f / (1.0f + expf(-g)); }
 
@@ -147,13 +148,14 @@ __device__ __forceinline__ float sigm(float g) { return 1.0f / (1.0f + expf(-g))
 template <bool DROP>
 __global__ __launch_bounds__(kT) void vtb_learn_forward_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
     const int e = blockIdx.x, tid = threadIdx.x;
-    const int B = c.n_env, D = c.dim_model, H = c.nhead, HD = D / H, F = c.d_hid, S = c.dim_state, NL = c.nlayers, Lp = L.Lp;
+    const int B = c.n_env, D = c.model.dim_model, H = c.model.nhead, HD = D / H, F = c.model.d_hid, S = c.model.dim_state;
+    const int NL = c.model.nlayers, Lp = L.Lp;
     const int np = b.len[e] + 1;          // positions 0..len (the last one is obs_next of the last row)
     float* w = b.ws + L.w.env + (long)e * L.e.total;
     const float* tp = b.tparams;
-    const uint32_t thr = DROP ? dropout_threshold(c.dropout_p) : 0u;
-    const float inv = DROP ? 1.0f / (1.0f - c.dropout_p) : 1.0f;
-    const uint32_t denv = (uint32_t)(c.drop_env_base + e);
+    const uint32_t thr = DROP ? dropout_threshold(c.model.dropout_p) : 0u;
+    const float inv = DROP ? 1.0f / (1.0f - c.model.dropout_p) : 1.0f;
+    const uint32_t denv = (uint32_t)(c.model.drop_env_base + e);
     const float sqd = sqrtf((float)D);
     float* X0 = w + L.e.X;
     for (int i = tid; i < np * D; i += kT) {
@@ -320,8 +322,8 @@ __device__ __forceinline__ const float* trunk_fwd(const cirs_vtb_learn_cfg& c, c
     float* in = buf0;
     float* out = buf1;
     long aoff = 0;
-    for (int li = 0; li < c.n_hidden; ++li) {
-        const int O = c.hidden[li], K = (int)L.p.tin[li];
+    for (int li = 0; li < c.model.n_hidden; ++li) {
+        const int O = c.model.hidden[li], K = (int)L.p.tin[li];
         for (int o = lane; o < O; o += 64) {
             const float* W = pp + L.p.tw[li] + (long)o * K;
             float acc = pp[L.p.tb[li] + o];
@@ -352,10 +354,10 @@ __device__ __forceinline__ RowOut heads(const cirs_vtb_learn_cfg& c, const Lay& 
         const float* Wm = pp + L.p.mu_w + (long)lane * W;
         float pre = pp[L.p.mu_b + lane];
         for (int k = 0; k < W; ++k) pre = __builtin_fmaf(Wm[k], h[k], pre);
-        const float mu = c.unbounded ? pre : c.max_action * tanhf(pre);
+        const float mu = c.model.unbounded ? pre : c.model.max_action * tanhf(pre);
         float sig;
         float hs = 0.f;
-        if (c.conditioned_sigma) {
+        if (c.model.conditioned_sigma) {
             const float* Ws = pp + L.p.sg_w + (long)lane * W;
             hs = pp[L.p.sg_b + lane];
             for (int k = 0; k < W; ++k) hs = __builtin_fmaf(Ws[k], h[k], hs);
@@ -385,7 +387,7 @@ __global__ __launch_bounds__(64 * kVW) void vtb_learn_values_kernel(cirs_vtb_lea
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r = blockIdx.x * kVW + wv;
     if (r >= c.n_rows) return;           // wave-uniform
-    const int B = c.n_env, S = c.dim_state;
+    const int B = c.n_env, S = c.model.dim_state;
     const int t = b.rows[r], e = b.rows[c.n_rows + r];
     const float* states = b.ws + L.w.states;
     const float* pp = b.pparams;
@@ -475,7 +477,7 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
     __shared__ float sm[kT / 64][4][kMaxW];
     __shared__ float stat[2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int B = c.n_env, S = c.dim_state, n = c.n_rows, W = L.p.width;
+    const int B = c.n_env, S = c.model.dim_state, n = c.n_rows, W = L.p.width;
     float* ws = b.ws;
     const float* pp = b.pparams;
     const int j0 = blockIdx.x * kRows, j1 = min(j0 + kRows, m);
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
         astd = stat[1];
     }
     long sumh = 0;
-    for (int i = 0; i < c.n_hidden; ++i) sumh += c.hidden[i];
+    for (int i = 0; i < c.model.n_hidden; ++i) sumh += c.model.hidden[i];
     const long RS = L.w.row_stride;
     const float inv_m = 1.0f / (float)m;
     for (int j = j0 + wv; j < j1; j += kT / 64) {
@@ -549,11 +551,11 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
         if (lane < kA) {
             const float var = hl.sig * hl.sig;
             const float dmu = dlogp * hl.diff / var;
-            const float dpre = c.unbounded ? dmu : dmu * c.max_action * (1.0f - tanhf(hl.pre) * tanhf(hl.pre));
+            const float dpre = c.model.unbounded ? dmu : dmu * c.model.max_action * (1.0f - tanhf(hl.pre) * tanhf(hl.pre));
             DPRE[lane] = dpre;
             sm[wv][2][lane] = dpre;
             float dsg;
-            if (c.conditioned_sigma) {
+            if (c.model.conditioned_sigma) {
                 const float dsig = dlogp * (hl.diff * hl.diff / (var * hl.sig) - 1.0f / hl.sig) + dent / hl.sig;
                 dsg = (hl.hs >= -20.f && hl.hs <= 2.f) ? dsig * hl.sig : 0.f;
             } else {
@@ -574,15 +576,15 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
         for (int k = lane; k < W; k += 64) {
             float acc = pp[L.p.c_w + k] * dv;
             for (int d = 0; d < kA; ++d) acc = __builtin_fmaf(pp[L.p.mu_w + (long)d * W + k], sm[wv][2][d], acc);
-            if (c.conditioned_sigma)
+            if (c.model.conditioned_sigma)
                 for (int d = 0; d < kA; ++d) acc = __builtin_fmaf(pp[L.p.sg_w + (long)d * W + k], sm[wv][3][d], acc);
             da[k] = acc;
         }
         __builtin_amdgcn_wave_barrier();
         // trunk backward
         long aoff = sumh;
-        for (int li = c.n_hidden - 1; li >= 0; --li) {
-            const int O = c.hidden[li], K = (int)L.p.tin[li];
+        for (int li = c.model.n_hidden - 1; li >= 0; --li) {
+            const int O = c.model.hidden[li], K = (int)L.p.tin[li];
             aoff -= O;
             for (int q = lane; q < O; q += 64) {
                 const float dz = rb[aoff + q] > 0.f ? da[q] : 0.f;
@@ -609,9 +611,9 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
         float acc = 0.f;
         if (q < L.p.trunk_end) {
             int li = 0;
-            while (li + 1 < c.n_hidden && q >= L.p.tw[li + 1]) ++li;
+            while (li + 1 < c.model.n_hidden && q >= L.p.tw[li + 1]) ++li;
             long aoff = 0;
-            for (int i = 0; i < li; ++i) aoff += c.hidden[i];
+            for (int i = 0; i < li; ++i) aoff += c.model.hidden[i];
             const int K = (int)L.p.tin[li];
             if (q < L.p.tb[li]) {
                 const long o = (q - L.p.tw[li]) / K, k = (q - L.p.tw[li]) % K;
@@ -637,11 +639,11 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
             const long d = q - L.p.mu_b;
             for (int j = j0; j < j1; ++j) acc += rb0[(long)j * RS + 2 * sumh + d];
         } else if (q < L.p.c_w) {   // sigma: head or free parameter
-            if (c.conditioned_sigma && q < L.p.sg_b) {
+            if (c.model.conditioned_sigma && q < L.p.sg_b) {
                 const long d = (q - L.p.sg_w) / W, k = (q - L.p.sg_w) % W;
                 for (int j = j0; j < j1; ++j) acc = __builtin_fmaf(rb0[(long)j * RS + 2 * sumh + kA + d], rb0[(long)j * RS + sumh - W + k], acc);
             } else {
-                const long d = q - (c.conditioned_sigma ? L.p.sg_b : L.p.sp);
+                const long d = q - (c.model.conditioned_sigma ? L.p.sg_b : L.p.sp);
                 for (int j = j0; j < j1; ++j) acc += rb0[(long)j * RS + 2 * sumh + kA + d];
             }
         } else if (q < L.p.c_b) {
@@ -768,14 +770,15 @@ __device__ __forceinline__ void ln_bwd(const float* dY, const float* XH, const f
 template <bool DROP>
 __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
     const int e = blockIdx.x, tid = threadIdx.x;
-    const int B = c.n_env, D = c.dim_model, H = c.nhead, HD = D / H, F = c.d_hid, S = c.dim_state, NL = c.nlayers, Lp = L.Lp, T = c.max_turn;
+    const int B = c.n_env, D = c.model.dim_model, H = c.model.nhead, HD = D / H, F = c.model.d_hid, S = c.model.dim_state;
+    const int NL = c.model.nlayers, Lp = L.Lp, T = c.max_turn;
     const int np = b.len[e];             // obs positions 0..len-1 carry gradient
     float* w = b.ws + L.w.env + (long)e * L.e.total;
     const float* tp = b.tparams;
     float* g = b.ws + L.w.tslab + (long)e * L.t.total;
-    const uint32_t thr = DROP ? dropout_threshold(c.dropout_p) : 0u;
-    const float inv = DROP ? 1.0f / (1.0f - c.dropout_p) : 1.0f;
-    const uint32_t denv = (uint32_t)(c.drop_env_base + e);
+    const uint32_t thr = DROP ? dropout_threshold(c.model.dropout_p) : 0u;
+    const float inv = DROP ? 1.0f / (1.0f - c.model.dropout_p) : 1.0f;
+    const uint32_t denv = (uint32_t)(c.model.drop_env_base + e);
     float* G = w + L.e.G;
     float* DU = w + L.e.DU;
     float* DH = w + L.e.DH;
@@ -1003,16 +1006,9 @@ __global__ __launch_bounds__(256) void vtb_learn_tracker_adam_kernel(cirs_vtb_le
 int validate(const cirs_vtb_learn_cfg* c) {
     CIRS_REQUIRE(c != nullptr, "null learn cfg");
     CIRS_REQUIRE(c->n_env >= 1 && c->max_turn >= 1, "n_env and max_turn must be >= 1");
-    CIRS_REQUIRE(c->dim_model == kA, "dim_model must be 27 (the VirtualTaobao action slot)");
-    CIRS_REQUIRE(c->nhead >= 1 && c->dim_model % c->nhead == 0, "dim_model must be a multiple of nhead");
-    CIRS_REQUIRE(c->d_hid >= 1 && c->d_hid <= 1024, "d_hid must lie in [1, 1024]");
-    CIRS_REQUIRE(c->nlayers >= 1 && c->nlayers <= CIRS_VTB_RO_MAX_LAYERS, "nlayers must lie in [1, 4]");
-    CIRS_REQUIRE(c->dim_state >= 1 && c->dim_state <= kMaxW, "dim_state must lie in [1, 128]");
-    CIRS_REQUIRE(c->max_len >= c->max_turn + 1, "max_turn exceeds the tracker's MAX_TURN - 1");
-    CIRS_REQUIRE(c->n_hidden >= 1 && c->n_hidden <= CIRS_VTB_RO_MAX_HIDDEN, "the trunk must have 1..3 hidden layers");
-    for (int i = 0; i < c->n_hidden; ++i) CIRS_REQUIRE(c->hidden[i] >= 1 && c->hidden[i] <= kMaxW, "trunk widths must lie in [1, 128]");
-    CIRS_REQUIRE(c->dropout_p >= 0.f && c->dropout_p < 1.f, "dropout_p must lie in [0, 1)");
-    CIRS_REQUIRE(c->drop_env_base >= 0, "drop_env_base must be >= 0");
+    if (int rc = vtb_validate_model(&c->model, c->max_turn)) return rc;
+    CIRS_REQUIRE(c->model.d_hid >= 1 && c->model.d_hid <= 1024, "d_hid must lie in [1, 1024]");
+    CIRS_REQUIRE(c->model.dim_state >= 1 && c->model.dim_state <= kMaxW, "dim_state must lie in [1, 128]");
     CIRS_REQUIRE(c->n_rows >= 1, "n_rows must be >= 1");
     CIRS_REQUIRE(c->n_seg >= 1 && c->n_seg <= c->n_rows, "n_seg must lie in [1, n_rows]");
     return CIRS_OK;
@@ -1060,7 +1056,7 @@ extern "C" int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_
     if (int rc = validate_bufs(b)) return rc;
     const hipStream_t s = (hipStream_t)stream;
     const Lay L = make_layout(*cfg);
-    if (cfg->dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_forward_kernel<true>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
+    if (cfg->model.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_forward_kernel<true>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
     else hipLaunchKernelGGL(vtb_learn_forward_kernel<false>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
     CIRS_CHECK_LAUNCH("vtb_learn_forward_kernel");
     return returns_stage(*cfg, *b, L, 1, s);
@@ -1097,7 +1093,7 @@ extern "C" int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_v
             CIRS_CHECK_LAUNCH("vtb_learn_adam_kernel");
         }
     }
-    if (c.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<true>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
+    if (c.model.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<true>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
     else hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<false>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
     CIRS_CHECK_LAUNCH("vtb_learn_tracker_bwd_kernel");
     const int g = cdiv(L.t.total, 256);

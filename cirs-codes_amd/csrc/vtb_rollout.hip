@@ -18,6 +18,7 @@
 // fp32 throughout; matrices are [in][out] so that the lanes of a mat-vec read consecutive floats; the weights stay in L2.
 #include "common.h"
 #include "rng.h"
+#include "vtb_model.h"
 
 #define CIRS_RNG_STREAM_GAUSS 0x47415553u /* 'GAUS' */
 
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
     if (j >= B) return;
     const int e = t == 0 ? j : tr.lists[(size_t)(t - 1) * B + j];
     if (e < 0 || e >= B) return;      // wave-uniform: past the end of the previous step's active list
-    const int D = cfg.dim_model, H = cfg.nhead, HD = D / H, S = cfg.dim_state, L = cfg.max_len;
+    const int D = cfg.model.dim_model, H = cfg.model.nhead, HD = D / H, S = cfg.model.dim_state, L = cfg.model.max_len;
     float* base = smem + (size_t)wv * (kFixed + H * L);
     float* xs = base;
     float* qs = base + kMaxD;
@@ -148,18 +149,18 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
 
     // ---- decode position t ---------------------------------------------------------------------------------------------
     const int pos = t;
-    const uint32_t d_thr = DROP ? dropout_threshold(cfg.dropout_p) : 0u;
-    const float d_inv = DROP ? 1.0f / (1.0f - cfg.dropout_p) : 1.0f;
-    const uint32_t d_env = (uint32_t)(cfg.drop_env_base + e);
+    const uint32_t d_thr = DROP ? dropout_threshold(cfg.model.dropout_p) : 0u;
+    const float d_inv = DROP ? 1.0f / (1.0f - cfg.model.dropout_p) : 1.0f;
+    const uint32_t d_env = (uint32_t)(cfg.model.drop_env_base + e);
 #define VTB_DROP(V, LAYER, SITE, ELEM) \
-    (dropout_keep(cfg.dropout_seed, d_env, (uint32_t)pos, (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), d_thr) ? (V) * d_inv : 0.f)
+    (dropout_keep(cfg.model.dropout_seed, d_env, (uint32_t)pos, (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), d_thr) ? (V) * d_inv : 0.f)
     float h = 0.f;
     if (lane < D) {
         h = x * sqrtf((float)D) + w.pe[(size_t)pos * D + lane];
         if (DROP) h = VTB_DROP(h, 0, CIRS_DROP_POS, lane);
     }
     const float qscale = 1.0f / sqrtf((float)HD);
-    for (int l = 0; l < cfg.nlayers; ++l) {
+    for (int l = 0; l < cfg.model.nlayers; ++l) {
         const cirs_vtb_policy_layer& ly = w.layer[l];
         if (lane < D) xs[lane] = h;
         wbar();
@@ -215,13 +216,13 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
         if (lane < D) h1s[lane] = h1;
         wbar();
         // feed-forward (ReLU) + residual + LayerNorm 2
-        for (int i = lane; i < cfg.d_hid; i += 64) {
-            float f = fmaxf(mv(ly.lin1_w, ly.lin1_b, h1s, D, cfg.d_hid, i), 0.f);
+        for (int i = lane; i < cfg.model.d_hid; i += 64) {
+            float f = fmaxf(mv(ly.lin1_w, ly.lin1_b, h1s, D, cfg.model.d_hid, i), 0.f);
             if (DROP) f = VTB_DROP(f, l, CIRS_DROP_FF, i);
             ffs[i] = f;
         }
         wbar();
-        float f2 = lane < D ? mv(ly.lin2_w, ly.lin2_b, ffs, cfg.d_hid, D, lane) : 0.f;
+        float f2 = lane < D ? mv(ly.lin2_w, ly.lin2_b, ffs, cfg.model.d_hid, D, lane) : 0.f;
         if (DROP && lane < D) f2 = VTB_DROP(f2, l, CIRS_DROP_RES2, lane);
         h = layer_norm(h1 + f2, lane, D, ly.norm2_w, ly.norm2_b);
         wbar();
@@ -242,8 +243,8 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
     float* in = hb;
     float* out = hc;
     int width = S;
-    for (int li = 0; li < cfg.n_hidden; ++li) {
-        const int O = cfg.hidden[li];
+    for (int li = 0; li < cfg.model.n_hidden; ++li) {
+        const int O = cfg.model.hidden[li];
         for (int o = lane; o < O; o += 64) out[o] = fmaxf(mv(w.trunk_w[li], w.trunk_b[li], in, width, O, o), 0.f);
         wbar();
         float* tmp = in;
@@ -253,9 +254,9 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
     }
     if (lane < kA) {
         const float pre = mv(w.mu_w, w.mu_b, in, width, kA, lane);
-        const float mu = cfg.unbounded ? pre : cfg.max_action * tanhf(pre);
+        const float mu = cfg.model.unbounded ? pre : cfg.model.max_action * tanhf(pre);
         float sigma;
-        if (cfg.conditioned_sigma) sigma = expf(fminf(fmaxf(mv(w.sigma_w, w.sigma_b, in, width, kA, lane), -20.f), 2.f));
+        if (cfg.model.conditioned_sigma) sigma = expf(fminf(fmaxf(mv(w.sigma_w, w.sigma_b, in, width, kA, lane), -20.f), 2.f));
         else sigma = expf(w.sigma_param[lane]);
         const float z = gauss_z(seed, collect_id, (uint32_t)e, (uint32_t)t, (uint32_t)lane);
         const float act = mu + sigma * z;
@@ -309,36 +310,29 @@ int grid_of(long total) {
 
 int validate_rollout(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* w, const cirs_vtb_cfg* vc, const cirs_vtb_traj* tr) {
     CIRS_REQUIRE(cfg && w && vc && tr, "null rollout argument");
+    const cirs_vtb_model_cfg* m = &cfg->model;
     CIRS_REQUIRE(cfg->n_env >= 1, "n_env must be >= 1");
     CIRS_REQUIRE(cfg->n_env == vc->n_env, "rollout n_env must equal the env's n_env");
     CIRS_REQUIRE(cfg->max_turn >= 1, "max_turn must be >= 1");
     CIRS_REQUIRE(!vc->simulated || cfg->max_turn == vc->max_turn, "rollout max_turn must equal the simulated env's max_turn");
     CIRS_REQUIRE(vc->simulated || cfg->max_turn >= vc->max_turn, "rollout max_turn must be >= the raw env's max_turn (it ends every episode there)");
-    CIRS_REQUIRE(cfg->max_len >= 2 && cfg->max_turn <= cfg->max_len - 1,
-                 "max_turn exceeds the tracker's MAX_TURN - 1 (positions 0..max_turn need pe / cache rows)");
     CIRS_REQUIRE(cfg->force_length >= 0 && cfg->force_length <= cfg->max_turn, "force_length must lie in [0, max_turn]");
-    CIRS_REQUIRE(cfg->dim_model >= 1 && cfg->dim_model <= kMaxD, "dim_model must lie in [1, 64]");
-    CIRS_REQUIRE(cfg->dim_model == kA, "dim_model must be 27: the input slot is sigmoid(fnn_gate([r, a])) * a with the 27 action features");
-    CIRS_REQUIRE(cfg->nhead >= 1 && cfg->dim_model % cfg->nhead == 0, "dim_model must be a multiple of nhead");
-    CIRS_REQUIRE((long)cfg->nhead * cfg->max_len <= kMaxAttn, "nhead * max_len must be <= 2048");
-    CIRS_REQUIRE(cfg->d_hid >= 1 && cfg->d_hid <= kMaxHid, "d_hid must lie in [1, 256]");
-    CIRS_REQUIRE(cfg->nlayers >= 1 && cfg->nlayers <= CIRS_VTB_RO_MAX_LAYERS, "nlayers must lie in [1, 4]");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= kMaxD, "dim_state must lie in [1, 64]");
-    CIRS_REQUIRE(cfg->n_hidden >= 1 && cfg->n_hidden <= CIRS_VTB_RO_MAX_HIDDEN, "the actor trunk must have 1..3 hidden layers");
-    for (int i = 0; i < cfg->n_hidden; ++i) CIRS_REQUIRE(cfg->hidden[i] >= 1 && cfg->hidden[i] <= kMaxW, "actor hidden widths must lie in [1, 128]");
     CIRS_REQUIRE(cfg->bound_method >= 0 && cfg->bound_method <= 2, "bound_method must be 0 (none), 1 (clip) or 2 (tanh)");
-    CIRS_REQUIRE(cfg->dropout_p >= 0.f && cfg->dropout_p < 1.f, "dropout_p must lie in [0, 1)");
-    CIRS_REQUIRE(cfg->drop_env_base >= 0, "drop_env_base must be >= 0");
+    if (int rc = vtb_validate_model(m, cfg->max_turn)) return rc;
+    CIRS_REQUIRE(m->dim_model <= kMaxD, "dim_model must lie in [1, 64]");      // this and the next three: what a wave holds in LDS
+    CIRS_REQUIRE((long)m->nhead * m->max_len <= kMaxAttn, "nhead * max_len must be <= 2048");
+    CIRS_REQUIRE(m->d_hid >= 1 && m->d_hid <= kMaxHid, "d_hid must lie in [1, 256]");
+    CIRS_REQUIRE(m->dim_state >= 1 && m->dim_state <= kMaxD, "dim_state must lie in [1, 64]");
     CIRS_REQUIRE(w->user_w && w->user_b && w->gate_w && w->gate_b && w->pe && w->dec_w && w->dec_b && w->mu_w && w->mu_b,
                  "tracker / actor weight is null");
-    for (int l = 0; l < cfg->nlayers; ++l) {
+    for (int l = 0; l < m->nlayers; ++l) {
         const cirs_vtb_policy_layer& y = w->layer[l];
         CIRS_REQUIRE(y.in_w && y.in_b && y.out_w && y.out_b && y.lin1_w && y.lin1_b && y.lin2_w && y.lin2_b && y.norm1_w && y.norm1_b &&
                          y.norm2_w && y.norm2_b,
                      "encoder layer weight is null");
     }
-    for (int i = 0; i < cfg->n_hidden; ++i) CIRS_REQUIRE(w->trunk_w[i] && w->trunk_b[i], "actor trunk weight is null");
-    CIRS_REQUIRE(cfg->conditioned_sigma ? (w->sigma_w && w->sigma_b) : (w->sigma_param != nullptr), "sigma weight is null");
+    for (int i = 0; i < m->n_hidden; ++i) CIRS_REQUIRE(w->trunk_w[i] && w->trunk_b[i], "actor trunk weight is null");
+    CIRS_REQUIRE(m->conditioned_sigma ? (w->sigma_w && w->sigma_b) : (w->sigma_param != nullptr), "sigma weight is null");
     CIRS_REQUIRE(!cfg->action_scaling || (w->act_low && w->act_high), "action box is null");
     CIRS_REQUIRE(tr->state && tr->act && tr->act_mapped && tr->obs0 && tr->obs && tr->rew && tr->done && tr->ctr && tr->len && tr->kcache &&
                      tr->vcache && tr->lists && tr->counts && tr->act_buf && tr->step_obs && tr->step_rew && tr->step_ctr && tr->step_done,
@@ -364,7 +358,7 @@ extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const c
     CIRS_HIP(hipMemsetAsync(tr.lists, 0xFF, (T + 1) * B * sizeof(int32_t), s));
     CIRS_HIP(hipMemsetAsync(tr.counts, 0, (T + 1) * sizeof(int32_t), s));
     CIRS_HIP(hipMemsetAsync(tr.len, 0, (size_t)B * sizeof(int32_t), s));
-    CIRS_HIP(hipMemsetAsync(tr.state, 0, (T + 1) * B * c.dim_state * sizeof(float), s));
+    CIRS_HIP(hipMemsetAsync(tr.state, 0, (T + 1) * B * c.model.dim_state * sizeof(float), s));
     CIRS_HIP(hipMemsetAsync(tr.act, 0, T * B * kA * sizeof(float), s));
     CIRS_HIP(hipMemsetAsync(tr.act_mapped, 0, T * B * kA * sizeof(float), s));
     CIRS_HIP(hipMemsetAsync(tr.obs, 0, T * B * kObs * sizeof(double), s));
@@ -372,9 +366,9 @@ extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const c
     CIRS_HIP(hipMemsetAsync(tr.ctr, 0, T * B * sizeof(double), s));
     CIRS_HIP(hipMemsetAsync(tr.done, 0, T * B, s));
     if (int rc = cirs_vtb_reset(vtb_cfg, vtb_w, vtb_st, c.env_seed, nullptr, B, tr.obs0, stream)) return rc;
-    const size_t shmem = (size_t)kWaves * (kFixed + (size_t)c.nhead * c.max_len) * sizeof(float);
+    const size_t shmem = (size_t)kWaves * (kFixed + (size_t)c.model.nhead * c.model.max_len) * sizeof(float);
     const dim3 grid(cdiv(B, kWaves)), block(64 * kWaves);
-    const bool drop = c.dropout_p > 0.f;
+    const bool drop = c.model.dropout_p > 0.f;
     for (int t = 0; t <= steps; ++t) {
         if (drop) hipLaunchKernelGGL(vtb_policy_step_kernel<true>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);
         else hipLaunchKernelGGL(vtb_policy_step_kernel<false>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);

@@ -784,11 +784,11 @@ int cirs_vtb_mmoe_forward(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, co
 #define CIRS_VTB_RO_MAX_LAYERS 4
 #define CIRS_VTB_RO_MAX_HIDDEN 3
 
-typedef struct cirs_vtb_rollout_cfg {
-    int32_t n_env;             /* == vtb_cfg->n_env                                                              */
-    int32_t max_turn;          /* vector steps of a collect; == vtb_cfg->max_turn and <= max_len - 1             */
-    int32_t force_length;      /* > 0: every episode ends after this many steps, overriding the env (<= max_turn) */
-    int32_t dim_model;         /* D <= 64, D % nhead == 0                                                        */
+/* The model both stages run: HostStateTracker + ActorProb over a Net trunk (CIRS-RL-taobao.py).  Declared once and embedded in
+ * cirs_vtb_rollout_cfg and cirs_vtb_learn_cfg; its rules are checked in one place (csrc/vtb_model.h).  The capacity limits noted
+ * per field are the rollout's; the learner's are wider (d_hid <= 1024, dim_state <= 128). */
+typedef struct cirs_vtb_model_cfg {
+    int32_t dim_model;         /* D == 27 (the action slot), D % nhead == 0                                      */
     int32_t nhead;
     int32_t d_hid;             /* <= 256                                                                         */
     int32_t nlayers;           /* 1..4                                                                           */
@@ -798,12 +798,19 @@ typedef struct cirs_vtb_rollout_cfg {
     int32_t hidden[CIRS_VTB_RO_MAX_HIDDEN]; /* trunk widths <= 128                                               */
     int32_t unbounded;         /* 1: mu = head output; 0: max_action * tanh(head output)                         */
     int32_t conditioned_sigma; /* 1: sigma = exp(clamp(sigma head, -20, 2)); 0: exp(sigma_param)                */
-    int32_t bound_method;      /* mapped action: 0 none, 1 clip to [-1, 1], 2 tanh                               */
-    int32_t action_scaling;    /* 1: [-1, 1] -> [act_low, act_high]                                              */
     float max_action;
-    float dropout_p;           /* 0 <= p < 1; 0 = no mask work                                                    */
+    float dropout_p;           /* 0 <= p < 1; 0 = no mask work.  With the next two: the position-keyed dropout key of one collect */
     int32_t drop_env_base;     /* dropout env id = drop_env_base + env                                           */
     uint64_t dropout_seed;     /* dropout key of this collect                                                    */
+} cirs_vtb_model_cfg;
+
+typedef struct cirs_vtb_rollout_cfg {
+    int32_t n_env;             /* == vtb_cfg->n_env                                                              */
+    int32_t max_turn;          /* vector steps of a collect; == vtb_cfg->max_turn and <= model.max_len - 1       */
+    int32_t force_length;      /* > 0: every episode ends after this many steps, overriding the env (<= max_turn) */
+    int32_t bound_method;      /* mapped action: 0 none, 1 clip to [-1, 1], 2 tanh                               */
+    int32_t action_scaling;    /* 1: [-1, 1] -> [act_low, act_high]                                              */
+    cirs_vtb_model_cfg model;
     uint64_t env_seed;         /* Philox key of the env (DeviceVirtualTB.seed)                                   */
 } cirs_vtb_rollout_cfg;
 
@@ -880,13 +887,7 @@ int cirs_vtb_rollout_masks(uint64_t dropout_seed, float p, int32_t env0, int32_t
  * Adam sub-steps per minibatch. */
 typedef struct cirs_vtb_learn_cfg {
     int32_t n_env, max_turn;                     /* the collect's shape (trajectory [max_turn][n_env])                      */
-    int32_t dim_model, nhead, d_hid, nlayers, dim_state, max_len;
-    int32_t n_hidden;
-    int32_t hidden[CIRS_VTB_RO_MAX_HIDDEN];
-    int32_t unbounded, conditioned_sigma;
-    float max_action, dropout_p;
-    int32_t drop_env_base;
-    uint64_t dropout_seed;
+    cirs_vtb_model_cfg model;                    /* with the dropout key of the collect the rows come from                  */
     int32_t n_rows, n_seg;                       /* sampled rows, GAE segments of the sample order                           */
     int32_t scale_returns, whiten_adv, clip_value, has_dual, has_max_norm;
     float clip, dual, c_value, c_entropy, max_norm;
