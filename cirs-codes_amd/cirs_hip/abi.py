@@ -204,6 +204,13 @@ SIGNATURES = {
     "cirs_vtb_learn_prepare": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P]),
     "cirs_vtb_learn_update": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
                                         C.c_int64, _P]),
+    "cirs_vtb_rollout_collect_redraw": (C.c_int, [C.POINTER(VtbRolloutCfg), C.POINTER(VtbPolicyWeights), C.POINTER(VtbCfg),
+                                                  C.POINTER(VtbWeights), C.POINTER(VtbState), C.POINTER(VtbTraj), _P, C.c_uint64, C.c_uint32,
+                                                  _P]),
+    "cirs_vtb_learn_redraw_sizes": (C.c_int, [C.POINTER(VtbLearnCfg), _P]),
+    "cirs_vtb_learn_prepare_redraw": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P]),
+    "cirs_vtb_learn_update_redraw": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int64, C.c_int64, _P]),
     "cirs_tracker_init": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,
                                     C.c_int32, _P, C.c_int64, _P]),
     "cirs_tracker_step": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P,

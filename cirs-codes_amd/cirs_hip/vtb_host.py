@@ -5,6 +5,8 @@ tracker_states    one teacher-forced causal pass of HostStateTracker (core/host_
                   reaches ffn_user and fnn_gate as well as the encoder.  A functional restatement of the post-norm
                   TransformerEncoderLayer that takes the rollout's dropout masks as given tensors (nn.Dropout cannot).  With
                   position-keyed masks one pass equals the T per-step calls of build_state.
+redraw_states     the same states under the exact-redraw dropout (dropout_redraw=True): one causal pass per call c with that call's masks
+                  over positions 0..c, position c kept, every call's graph retained -- what the reference's tracker in train() does.
 gauss_noise       the rollout's Gaussian draw z (Box-Muller on Philox), restated in numpy bit for bit.
 """
 import math
@@ -70,6 +72,32 @@ def states_from_slots(tracker, slots, masks=None):
 def tracker_states(tracker, user, rew, act, masks=None):
     """States [T+1, B, dim_state] of a recorded collect, with autograd: user [B, 88], rew [T, B], act [T, B, 27] (fp32)."""
     return states_from_slots(tracker, input_slots(tracker, user, rew, act), masks)
+
+
+def _pad_masks(masks, n):
+    """Masks of positions 0..c (states_from_slots' layout) as masks of n >= c + 1 positions: ones at the added positions and keys."""
+    out = {}
+    for key, m in masks.items():
+        B, c1, n_elem = m.shape
+        if key != "pos" and key[1] == DROP_ATTN:
+            nhead = n_elem // c1
+            full = torch.ones(B, n, n, nhead, dtype=m.dtype)
+            full[:, :c1, :c1] = m.reshape(B, c1, c1, nhead)
+            out[key] = full.reshape(B, n, n * nhead)
+        else:
+            out[key] = torch.cat((m, torch.ones(B, n - c1, n_elem, dtype=m.dtype)), 1)
+    return out
+
+
+def redraw_states(tracker, user, rew, act, masks_of_call=None):
+    """States [T+1, B, dim_state] where state c is position c of a causal pass of its own with the masks masks_of_call(c) (the layout
+    states_from_slots takes, positions 0..c; None = no dropout), with autograd through every call's pass.  Every pass runs over all
+    T + 1 slots: position c sees positions 0..c only, so that is call c's prefix pass, and passes of one length round alike (torch
+    blocks its sums by shape), which makes the result independent of the call when the masks are."""
+    slots = input_slots(tracker, user, rew, act)
+    n = slots.shape[0]
+    return torch.stack([states_from_slots(tracker, slots, None if masks_of_call is None else _pad_masks(masks_of_call(c), n))[c]
+                        for c in range(n)])
 
 
 # ---- Gaussian noise -----------------------------------------------------------------------------------------------------------

@@ -132,10 +132,11 @@ class DeviceVtbLearner:
         self.pe = tracker.pos_encoder.pe[:, 0, :].detach().float().contiguous().to(self.device)
         self.rms = torch.zeros(3, dtype=torch.float64, device=self.device)
 
-    def sizes(self, n_rows):
+    def sizes(self, n_rows, redraw=False):
         self.cfg.n_rows, self.cfg.n_seg = int(n_rows), 1
         out = (C.c_int64 * 5)()
-        self._abi.check(self._lib.cirs_vtb_learn_sizes(C.byref(self.cfg), C.cast(out, C.c_void_p)), "cirs_vtb_learn_sizes")
+        name = "cirs_vtb_learn_redraw_sizes" if redraw else "cirs_vtb_learn_sizes"
+        self._abi.check(getattr(self._lib, name)(C.byref(self.cfg), C.cast(out, C.c_void_p)), name)
         return [int(x) for x in out]
 
     # ---- one update ---------------------------------------------------------------------------------------------------------
@@ -145,7 +146,12 @@ class DeviceVtbLearner:
         opt_p, opt_t = policy.optim
         dev = self.device
         n = len(rows)
-        sizes = self.sizes(n)
+        # the dropout key of the collect the rows come from: the forward pass regenerates that collect's masks, per position or, for a
+        # dropout_redraw collect, per call (the workspace differs)
+        m = self.cfg.model
+        m.dropout_p, m.drop_env_base, m.dropout_seed = rows_src.dropout_p, rows_src.drop_env_base, u64(rows_src.dropout_seed)
+        self.redraw = bool(getattr(rows_src, "dropout_redraw", False))
+        sizes = self.sizes(n, self.redraw)
         n_trk, n_pol, n_ws = sizes[:3]
         self.n_trunk = check_optimisers(policy.optim, self.ppar, self.tpar)
         pflat, pm, pv, psteps = pack_image(self.ppar, opt_p)
@@ -186,8 +192,6 @@ class DeviceVtbLearner:
         c.discount, c.lam, c.floor = float(h.discount), float(h.lam), float(h.floor)
         c.lr, c.beta1, c.beta2, c.eps = _hyper(opt_p)
         c.t_lr, c.t_beta1, c.t_beta2, c.t_eps = _hyper(opt_t)
-        # the dropout key of the collect the rows come from: the forward pass regenerates that collect's masks
-        c.model.dropout_p, c.model.drop_env_base, c.model.dropout_seed = rows_src.dropout_p, rows_src.drop_env_base, u64(rows_src.dropout_seed)
         tr = rows_src.rollout.traj
         p = lambda x: x.data_ptr()      # noqa: E731
         base = self.ints.data_ptr()
@@ -196,7 +200,8 @@ class DeviceVtbLearner:
                                            done=p(tr["done"]), act=p(tr["act"]), len=p(tr["len"]), rows=base, boundary=p(self.bnd),
                                            seg_end=base + 4 * int(oi[1]), grad_rows=base + 4 * int(oi[2]), grad_start=base + 4 * int(oi[3]),
                                            rms=p(self.rms), ws=p(self.ws), losses=0)
-        self._abi.check(self._lib.cirs_vtb_learn_prepare(C.byref(c), C.byref(self.bufs), stream(self.device)), "cirs_vtb_learn_prepare")
+        name = "cirs_vtb_learn_prepare_redraw" if self.redraw else "cirs_vtb_learn_prepare"
+        self._abi.check(getattr(self._lib, name)(C.byref(c), C.byref(self.bufs), stream(self.device)), name)
 
     def states(self):
         """The learner's tracker states [max_turn + 1, n_env, dim_state] of the last prepare (device view)."""
@@ -216,9 +221,10 @@ class DeviceVtbLearner:
         perm_d = torch.as_tensor(np.stack(perms).astype(np.int32)).to(self.device)
         losses = torch.zeros((n_mb, 4), dtype=torch.float32, device=self.device)
         self.bufs.losses = losses.data_ptr()
-        self._abi.check(self._lib.cirs_vtb_learn_update(C.byref(self.cfg), C.byref(self.bufs), perm_d.data_ptr(), int(repeat), int(batch_size),
-                                                        int(bool(policy.hyper.refresh_adv)), int(self.p_step0), int(self.t_step0),
-                                                        stream(self.device)), "cirs_vtb_learn_update")
+        name = "cirs_vtb_learn_update_redraw" if self.redraw else "cirs_vtb_learn_update"
+        self._abi.check(getattr(self._lib, name)(C.byref(self.cfg), C.byref(self.bufs), perm_d.data_ptr(), int(repeat), int(batch_size),
+                                                 int(bool(policy.hyper.refresh_adv)), int(self.p_step0), int(self.t_step0),
+                                                 stream(self.device)), name)
         back = torch.cat([self.img, losses.reshape(-1)]).cpu()
         rms = self.rms.cpu().numpy()
         n_img = self.img.numel()

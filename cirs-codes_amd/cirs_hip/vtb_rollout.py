@@ -50,8 +50,9 @@ class DeviceVtbRollout:
     """n_env = the DeviceVirtualTB's env count; `tracker` a HostStateTracker, `actor` an ActorProb over a Net trunk, `policy` the
     HostPPOPolicy that maps its actions."""
 
-    def __init__(self, vtb, tracker, actor, policy, force_length=0):
+    def __init__(self, vtb, tracker, actor, policy, force_length=0, dropout_redraw=False):
         self.model = VtbModel(tracker, actor)
+        self.dropout_redraw = bool(dropout_redraw)
         self.vtb, self.tracker, self.actor, self.policy = vtb, tracker, actor, policy
         self.device = vtb.device
         B, T = vtb.n_env, vtb.max_turn
@@ -84,6 +85,8 @@ class DeviceVtbRollout:
                          step_rew=torch.zeros(B, **f64), step_ctr=torch.zeros(B, **f64),
                          step_done=torch.zeros(B, dtype=torch.uint8, device=dev))
         self._tr = abi.VtbTraj(**{k: self.traj[k].data_ptr() for k in abi.VTB_TRAJ_FIELDS})
+        # exact redraw: the kept slots and the lower layers' output rows of the prefix pass
+        self._redraw_ws = torch.zeros(L * B * D * nlayers, **f32) if self.dropout_redraw else None
         self._lib = abi.lib()
 
     def pack(self):
@@ -101,9 +104,12 @@ class DeviceVtbRollout:
         self.cfg.model.dropout_seed = u64(dropout_seed)
         self.cfg.env_seed = u64(self.vtb._seed)
         self.pack()
-        abi.check(self._lib.cirs_vtb_rollout_collect(C.byref(self.cfg), C.byref(self._w), C.byref(self.vtb.cfg), C.byref(self.vtb._wst),
-                                                     C.byref(self.vtb._st), C.byref(self._tr), u64(seed), int(collect_id) & 0xFFFFFFFF,
-                                                     stream(self.device)), "cirs_vtb_rollout_collect")
+        args = (C.byref(self.cfg), C.byref(self._w), C.byref(self.vtb.cfg), C.byref(self.vtb._wst), C.byref(self.vtb._st), C.byref(self._tr))
+        key = (u64(seed), int(collect_id) & 0xFFFFFFFF, stream(self.device))
+        if self.dropout_redraw:
+            abi.check(self._lib.cirs_vtb_rollout_collect_redraw(*args, self._redraw_ws.data_ptr(), *key), "cirs_vtb_rollout_collect_redraw")
+        else:
+            abi.check(self._lib.cirs_vtb_rollout_collect(*args, *key), "cirs_vtb_rollout_collect")
         lens = self.traj["len"].cpu().numpy().astype(np.int64)
         self.vtb.host_turn[:] = lens          # the env's turns as the host tracks them (DeviceVirtualTB._check_turns)
         self.vtb._was_reset[:] = True
@@ -139,3 +145,7 @@ class DeviceVtbRollout:
             m[(l, DROP_FF)] = one(l, DROP_FF, d_hid)
             m[(l, DROP_RES2)] = one(l, DROP_RES2, D)
         return m
+
+    def call_masks(self, dropout_seed, c):
+        """Exact redraw: the masks of call c (positions 0..c) of every env, those of dropout env ids drop_env_base + c * n_env + e."""
+        return self.masks(dropout_seed, c + 1, env0=c * self.vtb.n_env)

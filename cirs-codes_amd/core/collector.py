@@ -40,7 +40,14 @@ def result_from_trajectory(traj, lengths: np.ndarray, offsets: np.ndarray) -> Di
 class Collector:
     def __new__(cls, policy=None, env=None, *args, rollout=None, **kwargs):
         """Host vector envs (VirtualTB-v0: BASELINE configs[0], CPU plumbing) are collected by the per-step loop of core.host_rl;
-        rollout="device" collects a VirtualTB-v0 vector env built with device= on the GPU instead (core.vtb_collector)."""
+        rollout="device" collects a VirtualTB-v0 vector env built with device= on the GPU instead (core.vtb_collector), with
+        dropout_redraw=True under the reference's own dropout procedure (fresh masks over the whole prefix at every call)."""
+        redraw = kwargs.get("dropout_redraw", False)
+        if not isinstance(redraw, (bool, np.bool_)):
+            raise TypeError(f"dropout_redraw must be a bool, got {redraw!r}")
+        if cls is Collector and redraw and rollout is None:
+            raise ValueError("dropout_redraw=True is an option of rollout='device'; the host collector already redraws the tracker's "
+                             "dropout at every call (torch's generator), and the KuaishouEnv option is CirsEngine(dropout_redraw=True)")
         if cls is Collector and rollout is not None:
             if rollout != "device":
                 raise ValueError(f"rollout must be None or 'device', got {rollout!r}")
@@ -49,11 +56,12 @@ class Collector:
             return DeviceVtbCollector(policy, env, *args, **kwargs)
         if cls is Collector and getattr(env, "host_mode", False):
             from core.host_rl import HostCollector
-            return HostCollector(policy, env, *args, **kwargs)
+            return HostCollector(policy, env, *args, **{k: v for k, v in kwargs.items() if k != "dropout_redraw"})
         return super().__new__(cls)
 
     def __init__(self, policy, env, buffer: Optional[VectorReplayBuffer] = None, preprocess_fn: Optional[Callable[..., Any]] = None,
-                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0, rollout=None):
+                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0, rollout=None,
+                 dropout_redraw=False):
         assert hasattr(env, "__len__"), "pass a tianshou.env.DummyVectorEnv"
         assert preprocess_fn is not None and hasattr(preprocess_fn, "__self__"), \
             "preprocess_fn must be StateTrackerTransformer.build_state (CIRS-RL-kuaishou.py:291)"

@@ -5,7 +5,11 @@ cirs_vtb_rollout_collect call (cirs_hip/vtb_rollout.py): the tracker, the actor 
 With a buffer (training collector) the states the learner back-propagates through are rebuilt afterwards in ONE teacher-forced causal pass
 of the tracker in torch (cirs_hip/vtb_host.py) with the collect's own dropout masks, and the VectorReplayBuffer is filled in the per-env
 segment order HostCollector's per-step adds produce, so HostPPOPolicy.update and onpolicy_trainer run unchanged.  Without a buffer (test
-collector) nothing is rebuilt."""
+collector) nothing is rebuilt.
+
+dropout_redraw=True: the reference's own dropout procedure -- every build_state call runs the whole prefix again with fresh masks -- instead
+of one mask per position for the rest of the episode (cirs_vtb_rollout_collect_redraw); the rebuilt states are then one pass per call
+(vtb_host.redraw_states) and the device learner back-propagates through each call's own graph."""
 import time
 from typing import Any, Callable, Dict, List, Optional
 
@@ -47,8 +51,11 @@ def check_device_vtb(policy, env, preprocess_fn):
 
 class DeviceVtbCollector:
     def __init__(self, policy, env, buffer: Optional[VectorReplayBuffer] = None, preprocess_fn: Optional[Callable[..., Any]] = None,
-                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0):
+                 exploration_noise: bool = False, remove_recommended_ids=False, force_length=0, dropout_redraw=False):
         self.tracker = check_device_vtb(policy, env, preprocess_fn)
+        if not isinstance(dropout_redraw, (bool, np.bool_)):
+            raise TypeError(f"dropout_redraw must be a bool, got {dropout_redraw!r}")
+        self.dropout_redraw = bool(dropout_redraw)
         if remove_recommended_ids:
             raise ValueError("remove_recommended_ids is a discrete-catalogue feature (KuaishouEnv)")
         self.policy, self.env, self.preprocess_fn = policy, env, preprocess_fn
@@ -87,7 +94,7 @@ class DeviceVtbCollector:
         if self._rollout is None:
             from cirs_hip.vtb_rollout import DeviceVtbRollout
             self._rollout = DeviceVtbRollout(self.env.vtb_env(), self.tracker, self.policy.actor, self.policy,
-                                             force_length=self.options["horizon"])
+                                             force_length=self.options["horizon"], dropout_redraw=self.dropout_redraw)
         return self._rollout
 
     def keys(self, collect_id):
@@ -131,9 +138,11 @@ class DeviceVtbCollector:
         user = tr["obs0"][:, :-3].to(torch.float32)
         rew = tr["rew"][:Tm].to(torch.float32)                     # fp64 -> fp32 once, as torch.as_tensor(rew, float32)
         act = tr["obs"][:Tm, :, :-3].to(torch.float32)             # the action columns of obs_next
-        masks = ro.masks(dropout_seed, Tm + 1, n_env=B) if ro.dropout_p > 0 else None
-        from cirs_hip.vtb_host import tracker_states
+        from cirs_hip.vtb_host import redraw_states, tracker_states
         with torch.enable_grad():
+            if self.dropout_redraw and ro.dropout_p > 0:
+                return redraw_states(self.tracker, user, rew, act, lambda c: ro.call_masks(dropout_seed, c))
+            masks = ro.masks(dropout_seed, Tm + 1, n_env=B) if ro.dropout_p > 0 else None
             return tracker_states(self.tracker, user, rew, act, masks)
 
     def _transitions(self, tr, lens):

@@ -22,6 +22,7 @@ class VtbDeviceRows:
         self.collector, self.rollout, self.lens = collector, rollout, np.asarray(lens, dtype=np.int64)
         self.seed, self.collect_id, self.dropout_seed = keys
         self.dropout_p, self.drop_env_base = float(rollout.dropout_p), int(rollout.cfg.model.drop_env_base)     # with dropout_seed: the dropout key
+        self.dropout_redraw = bool(rollout.dropout_redraw)      # the learner follows the collect's dropout procedure
         self._host = host_traj
 
     def is_current(self):

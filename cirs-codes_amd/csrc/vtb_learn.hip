@@ -15,6 +15,9 @@
 //   vtb_learn_tracker_bwd_kernel  one workgroup per episode: dL/dstate of the obs rows back through decoder, both encoder layers, PE
 //                                 and the input slots into per-episode tracker gradient partials
 //   vtb_learn_tracker_adam_kernel fixed-order reduction over episodes, one Adam step of the tracker
+// Exact redraw (cirs_vtb_learn_*_redraw, the buffer of a dropout_redraw collect): the forward and the tracker backward run per CALL (c, e)
+// instead of per episode -- positions 0..c with the masks of dropout env id drop_env_base + c * n_env + e, state and gradient on the last
+// position -- in vtb_learn_forward_redraw_kernel / vtb_learn_tracker_redraw_kernel, built from the same two device functions.
 // No float atomics: every sum has a fixed order, so two runs from the same snapshot are bit-identical.  fp32 FMA, fp64 for GAE,
 // the return statistics, the advantage moments and the gradient norm.  Parameter images are in torch's [out][in] layout.
 #include "common.h"
@@ -58,9 +61,12 @@ struct Lay {
     ELay e;
     WLay w;
     int Lp;
+    int n_wg;      // tracker workgroups = episode workspaces = gradient slabs: n_env, or n_env * groups in the exact-redraw mode
+    int groups;    // exact-redraw mode: workgroups per env, group g runs the calls c = g, g + groups, ...
 };
 
-Lay make_layout(const cirs_vtb_learn_cfg& c) {
+// redraw: the exact-redraw layout (cirs_vtb_learn_*_redraw with dropout_p > 0)
+Lay make_layout(const cirs_vtb_learn_cfg& c, bool redraw = false) {
     Lay L{};
     const long D = c.model.dim_model, F = c.model.d_hid, S = c.model.dim_state, H = c.model.nhead;
     long o = 0;
@@ -119,11 +125,15 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
     long sumh = 0;
     for (int i = 0; i < c.model.n_hidden; ++i) sumh += c.model.hidden[i];
     const long n = c.n_rows, B = c.n_env;
+    // a pseudo-episode's activations live only from its forward to its backward inside one workgroup, so the workspace grows with the
+    // workgroups in flight, not with the sum of the prefix lengths: up to 8 per env while that keeps <= 1024 of them
+    L.groups = redraw ? (int)(1024 / B < 1 ? 1 : 1024 / B > 8 ? 8 : 1024 / B) : 1;
+    L.n_wg = (int)B * L.groups;
     o = 0;
     L.w.states = take(Lp * B * S);
     L.w.dsrow = take(n * S);
-    L.w.env = take(B * L.e.total);
-    L.w.tslab = take(B * L.t.total);
+    L.w.env = take(L.n_wg * L.e.total);
+    L.w.tslab = take(L.n_wg * L.t.total);
     L.w.vs = take(n); L.w.adv = take(n); L.w.ret = take(n); L.w.logp_old = take(n);   // the per-row block, in this order
     L.w.now = take(n); L.w.nxt = take(n);
     o = (o + 1) / 2 * 2;
@@ -144,18 +154,18 @@ Lay make_layout(const cirs_vtb_learn_cfg& c) {
 
 __device__ __forceinline__ float sigm(float g) { return 1.0f / (1.0f + expf(-g)); }
 
-// ---- tracker forward: one workgroup per episode -----------------------------------------------------------------------------
-template <bool DROP>
-__global__ __launch_bounds__(kT) void vtb_learn_forward_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
-    const int e = blockIdx.x, tid = threadIdx.x;
+// ---- tracker forward: one workgroup per (pseudo-)episode ------------------------------------------------------------------------
+// The teacher-forced causal pass over the slots 0..np-1 of env e with the masks of dropout env id denv; activations into the workspace w.
+// LAST: only the state of position np - 1 is handed out (the state of call np - 1 in the exact-redraw mode).
+template <bool DROP, bool LAST>
+__device__ __forceinline__ void tracker_forward(const cirs_vtb_learn_cfg& c, const cirs_vtb_learn_bufs& b, const Lay& L, int e, int np,
+                                                uint32_t denv, float* w) {
+    const int tid = threadIdx.x;
     const int B = c.n_env, D = c.model.dim_model, H = c.model.nhead, HD = D / H, F = c.model.d_hid, S = c.model.dim_state;
     const int NL = c.model.nlayers, Lp = L.Lp;
-    const int np = b.len[e] + 1;          // positions 0..len (the last one is obs_next of the last row)
-    float* w = b.ws + L.w.env + (long)e * L.e.total;
     const float* tp = b.tparams;
     const uint32_t thr = DROP ? dropout_threshold(c.model.dropout_p) : 0u;
     const float inv = DROP ? 1.0f / (1.0f - c.model.dropout_p) : 1.0f;
-    const uint32_t denv = (uint32_t)(c.model.drop_env_base + e);
     const float sqd = sqrtf((float)D);
     float* X0 = w + L.e.X;
     for (int i = tid; i < np * D; i += kT) {
@@ -302,12 +312,31 @@ __global__ __launch_bounds__(kT) void vtb_learn_forward_kernel(cirs_vtb_learn_cf
     }
     const float* XL = w + L.e.X + (long)NL * Lp * D;
     float* states = b.ws + L.w.states;
-    for (int i = tid; i < np * S; i += kT) {
+    for (int i = tid + (LAST ? (np - 1) * S : 0); i < np * S; i += kT) {
         const int p = i / S, s = i % S;
         const float* W = tp + L.t.dec_w + (long)s * D;
         float acc = tp[L.t.dec_b + s];
         for (int k = 0; k < D; ++k) acc = __builtin_fmaf(W[k], XL[(long)p * D + k], acc);
         states[((long)p * B + e) * S + s] = acc;
+    }
+}
+
+// position-keyed mode: one pass per episode over positions 0..len (the last one is obs_next of the last row)
+template <bool DROP>
+__global__ __launch_bounds__(kT) void vtb_learn_forward_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
+    const int e = blockIdx.x;
+    tracker_forward<DROP, false>(c, b, L, e, b.len[e] + 1, (uint32_t)(c.model.drop_env_base + e), b.ws + L.w.env + (long)e * L.e.total);
+}
+
+// exact-redraw mode: workgroup (e, g) runs the calls c = g, g + groups, ... <= len of env e, each a pass of its own over the slots 0..c
+// with the masks of dropout env id drop_env_base + c * n_env + e; only the states leave (the update runs the passes again)
+__global__ __launch_bounds__(kT) void vtb_learn_forward_redraw_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
+    const int e = blockIdx.x / L.groups, g = blockIdx.x % L.groups;
+    float* w = b.ws + L.w.env + (long)blockIdx.x * L.e.total;
+    const int len = b.len[e];
+    for (int call = g; call <= len; call += L.groups) {
+        tracker_forward<true, true>(c, b, L, e, call + 1, (uint32_t)(c.model.drop_env_base + call * c.n_env + e), w);
+        __syncthreads();
     }
 }
 
@@ -734,18 +763,25 @@ __global__ __launch_bounds__(kAdamT) void vtb_learn_adam_kernel(cirs_vtb_learn_c
 
 // ---- tracker backward: one workgroup per episode -----------------------------------------------------------------------------------
 // dW[o][k] += sum_p dY[p][o] X[p][k] and db[o] += sum_p dY[p][o] for a [O][K] linear over positions 0..np-1 (written, not added)
+// ADD (exact-redraw mode): the pseudo-episodes of a workgroup add into its slab one after the other
+template <bool ADD>
+__device__ __forceinline__ void put_grad(float* g, long i, float v) {
+    g[i] = ADD ? g[i] + v : v;
+}
+
+template <bool ADD>
 __device__ __forceinline__ void lin_grads(float* g, long ow, long ob, const float* dY, int ldy, const float* X, int ldx, int O, int K, int np,
                                           int tid) {
     for (int i = tid; i < O * K; i += kT) {
         const int o = i / K, k = i % K;
         float acc = 0.f;
         for (int p = 0; p < np; ++p) acc = __builtin_fmaf(dY[(long)p * ldy + o], X[(long)p * ldx + k], acc);
-        g[ow + i] = acc;
+        put_grad<ADD>(g, ow + i, acc);
     }
     for (int o = tid; o < O; o += kT) {
         float acc = 0.f;
         for (int p = 0; p < np; ++p) acc += dY[(long)p * ldy + o];
-        g[ob + o] = acc;
+        put_grad<ADD>(g, ob + o, acc);
     }
 }
 
@@ -767,18 +803,17 @@ __device__ __forceinline__ void ln_bwd(const float* dY, const float* XH, const f
     }
 }
 
-template <bool DROP>
-__global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
-    const int e = blockIdx.x, tid = threadIdx.x;
+// The backward of tracker_forward's pass over positions 0..np-1 (activations in w, masks regenerated) into the gradient slab g.
+// LAST (exact-redraw mode): the upstream gradient sits on position np - 1 only, the rows whose obs is call np - 1, and g is added to.
+template <bool DROP, bool LAST>
+__device__ __forceinline__ void tracker_backward(const cirs_vtb_learn_cfg& c, const cirs_vtb_learn_bufs& b, const Lay& L, int e, int np,
+                                                 uint32_t denv, float* w, float* g) {
+    const int tid = threadIdx.x;
     const int B = c.n_env, D = c.model.dim_model, H = c.model.nhead, HD = D / H, F = c.model.d_hid, S = c.model.dim_state;
     const int NL = c.model.nlayers, Lp = L.Lp, T = c.max_turn;
-    const int np = b.len[e];             // obs positions 0..len-1 carry gradient
-    float* w = b.ws + L.w.env + (long)e * L.e.total;
     const float* tp = b.tparams;
-    float* g = b.ws + L.w.tslab + (long)e * L.t.total;
     const uint32_t thr = DROP ? dropout_threshold(c.model.dropout_p) : 0u;
     const float inv = DROP ? 1.0f / (1.0f - c.model.dropout_p) : 1.0f;
-    const uint32_t denv = (uint32_t)(c.model.drop_env_base + e);
     float* G = w + L.e.G;
     float* DU = w + L.e.DU;
     float* DH = w + L.e.DH;
@@ -790,12 +825,13 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
         const int p = i / S, s = i % S;
         const long key = (long)e * T + p;
         float acc = 0.f;
-        for (int k = b.grad_start[key]; k < b.grad_start[key + 1]; ++k) acc += b.ws[L.w.dsrow + (long)b.grad_rows[k] * S + s];
+        if (!LAST || p == np - 1)
+            for (int k = b.grad_start[key]; k < b.grad_start[key + 1]; ++k) acc += b.ws[L.w.dsrow + (long)b.grad_rows[k] * S + s];
         DS[(long)p * S + s] = acc;
     }
     __syncthreads();
     const float* XL = w + L.e.X + (long)NL * Lp * D;
-    lin_grads(g, L.t.dec_w, L.t.dec_b, DS, S, XL, D, S, D, np, tid);
+    lin_grads<LAST>(g, L.t.dec_w, L.t.dec_b, DS, S, XL, D, S, D, np, tid);
     for (int i = tid; i < np * D; i += kT) {
         const int p = i / D, k = i % D;
         float acc = 0.f;
@@ -821,8 +857,8 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
                 a = __builtin_fmaf(G[(long)p * D + d], XH2[(long)p * D + d], a);
                 bb += G[(long)p * D + d];
             }
-            g[L.t.n2_w[l] + d] = a;
-            g[L.t.n2_b[l] + d] = bb;
+            put_grad<LAST>(g, L.t.n2_w[l] + d, a);
+            put_grad<LAST>(g, L.t.n2_b[l] + d, bb);
         }
         ln_bwd(G, XH2, w + L.e.RS2[l], tp + L.t.n2_w[l], DU, D, np, tid);
         __syncthreads();
@@ -850,15 +886,15 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
                 if (DROP) fv = LEARN_KEEP(p, l, CIRS_DROP_FF, f) ? fv * inv : 0.f;
                 acc = __builtin_fmaf(G[(long)p * D + o], fv, acc);
             }
-            g[L.t.l2_w[l] + i] = acc;
+            put_grad<LAST>(g, L.t.l2_w[l] + i, acc);
         }
         for (int o = tid; o < D; o += kT) {
             float acc = 0.f;
             for (int p = 0; p < np; ++p) acc += G[(long)p * D + o];
-            g[L.t.l2_b[l] + o] = acc;
+            put_grad<LAST>(g, L.t.l2_b[l] + o, acc);
         }
         __syncthreads();
-        lin_grads(g, L.t.l1_w[l], L.t.l1_b[l], DFF, F, H1, D, F, D, np, tid);
+        lin_grads<LAST>(g, L.t.l1_w[l], L.t.l1_b[l], DFF, F, H1, D, F, D, np, tid);
         // dH1 = du2 + W1^T dFF
         for (int i = tid; i < np * D; i += kT) {
             const int p = i / D, k = i % D;
@@ -874,8 +910,8 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
                 a = __builtin_fmaf(DH[(long)p * D + d], XH1[(long)p * D + d], a);
                 bb += DH[(long)p * D + d];
             }
-            g[L.t.n1_w[l] + d] = a;
-            g[L.t.n1_b[l] + d] = bb;
+            put_grad<LAST>(g, L.t.n1_w[l] + d, a);
+            put_grad<LAST>(g, L.t.n1_b[l] + d, bb);
         }
         ln_bwd(DH, XH1, w + L.e.RS1[l], tp + L.t.n1_w[l], DU, D, np, tid);
         __syncthreads();
@@ -887,7 +923,7 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
             G[i] = v;
         }
         __syncthreads();
-        lin_grads(g, L.t.out_w[l], L.t.out_b[l], G, D, ATT, D, D, D, np, tid);
+        lin_grads<LAST>(g, L.t.out_w[l], L.t.out_b[l], G, D, ATT, D, D, D, np, tid);
         // dATT -> DH
         for (int i = tid; i < np * D; i += kT) {
             const int p = i / D, k = i % D;
@@ -933,7 +969,7 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
             DQKV[(long)p * 3 * D + D + d] = ak * qscale;
         }
         __syncthreads();
-        lin_grads(g, L.t.in_w[l], L.t.in_b[l], DQKV, 3 * D, X, D, 3 * D, D, np, tid);
+        lin_grads<LAST>(g, L.t.in_w[l], L.t.in_b[l], DQKV, 3 * D, X, D, 3 * D, D, np, tid);
         // dX = du1 + W_in^T dQKV -> G (the next layer down's output gradient)
         for (int i = tid; i < np * D; i += kT) {
             const int p = i / D, k = i % D;
@@ -956,8 +992,8 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
     __syncthreads();
     // slot 0: ffn_user
     const double* o0 = b.obs0 + (long)e * kObs0;
-    for (int i = tid; i < D * kU; i += kT) g[L.t.user_w + i] = DH[i / kU] * (float)o0[i % kU];
-    for (int d = tid; d < D; d += kT) g[L.t.user_b + d] = DH[d];
+    for (int i = tid; i < D * kU; i += kT) put_grad<LAST>(g, L.t.user_w + i, DH[i / kU] * (float)o0[i % kU]);
+    for (int d = tid; d < D; d += kT) put_grad<LAST>(g, L.t.user_b + d, DH[d]);
     // slots 1..np-1: x = sigmoid(gate) * a; dgate = dx * a * s (1 - s) -> DU
     const float* SIG = w + L.e.SIG;
     for (int i = tid; i < np * D; i += kT) {
@@ -979,12 +1015,38 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_lear
             const float x = k == 0 ? (float)b.rew[row] : (float)b.obs[row * kObs + k - 1];
             acc = __builtin_fmaf(DU[(long)p * D + o], x, acc);
         }
-        g[L.t.gate_w + i] = acc;
+        put_grad<LAST>(g, L.t.gate_w + i, acc);
     }
     for (int o = tid; o < D; o += kT) {
         float acc = 0.f;
         for (int p = 1; p < np; ++p) acc += DU[(long)p * D + o];
-        g[L.t.gate_b + o] = acc;
+        put_grad<LAST>(g, L.t.gate_b + o, acc);
+    }
+}
+
+// position-keyed mode: one workgroup per episode; the obs positions 0..len-1 carry gradient
+template <bool DROP>
+__global__ __launch_bounds__(kT) void vtb_learn_tracker_bwd_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
+    const int e = blockIdx.x;
+    tracker_backward<DROP, false>(c, b, L, e, b.len[e], (uint32_t)(c.model.drop_env_base + e), b.ws + L.w.env + (long)e * L.e.total,
+                                  b.ws + L.w.tslab + (long)e * L.t.total);
+}
+
+// exact-redraw mode: workgroup (e, g) runs forward and backward of the calls c = g, g + groups, ... < len of env e that have sampled rows
+// (call len is only ever an obs_next), in this fixed order, adding into its own slab (zeroed by the caller)
+__global__ __launch_bounds__(kT) void vtb_learn_tracker_redraw_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
+    const int e = blockIdx.x / L.groups, g = blockIdx.x % L.groups;
+    float* w = b.ws + L.w.env + (long)blockIdx.x * L.e.total;
+    float* slab = b.ws + L.w.tslab + (long)blockIdx.x * L.t.total;
+    const int len = b.len[e];
+    for (int call = g; call < len; call += L.groups) {
+        const long key = (long)e * c.max_turn + call;
+        if (b.grad_start[key] == b.grad_start[key + 1]) continue;      // workgroup-uniform
+        const uint32_t denv = (uint32_t)(c.model.drop_env_base + call * c.n_env + e);
+        tracker_forward<true, true>(c, b, L, e, call + 1, denv, w);
+        __syncthreads();
+        tracker_backward<true, true>(c, b, L, e, call + 1, denv, w, slab);
+        __syncthreads();
     }
 }
 #undef LEARN_KEEP
@@ -994,7 +1056,7 @@ __global__ __launch_bounds__(256) void vtb_learn_tracker_adam_kernel(cirs_vtb_le
     const float* slab = b.ws + L.w.tslab;
     for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < P; q += (long)gridDim.x * blockDim.x) {
         float g = 0.f;
-        for (int e = 0; e < c.n_env; ++e) g += slab[(long)e * P + q];
+        for (int e = 0; e < L.n_wg; ++e) g += slab[(long)e * P + q];
         float p = b.tparams[q], m = b.t_m[q], v = b.t_v[q];
         adam_one(p, m, v, g, step, c.t_lr, c.t_beta1, c.t_beta2, c.t_eps);
         b.tparams[q] = p;
@@ -1033,14 +1095,17 @@ int returns_stage(const cirs_vtb_learn_cfg& c, const cirs_vtb_learn_bufs& b, con
     return CIRS_OK;
 }
 
-}  // namespace
-}  // namespace cirs
+// what the exact-redraw mode adds to validate
+int validate_redraw(const cirs_vtb_learn_cfg* c) {
+    CIRS_REQUIRE((long)c->model.drop_env_base + ((long)c->max_turn + 1) * c->n_env < (1L << 31),
+                 "dropout_redraw: drop_env_base + (max_turn + 1) * n_env must be < 2^31 (call c of env e draws dropout env id "
+                 "drop_env_base + c * n_env + e)");
+    return CIRS_OK;
+}
 
-extern "C" int cirs_vtb_learn_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out) {
-    using namespace cirs;
-    if (int rc = validate(cfg)) return rc;
+int sizes(const cirs_vtb_learn_cfg* cfg, bool redraw, int64_t* out) {
     CIRS_REQUIRE(out != nullptr, "null output");
-    const Lay L = make_layout(*cfg);
+    const Lay L = make_layout(*cfg, redraw);
     out[0] = L.t.total;
     out[1] = L.p.total;
     out[2] = L.w.total;
@@ -1049,32 +1114,22 @@ extern "C" int cirs_vtb_learn_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out)
     return CIRS_OK;
 }
 
-// replaces core/host_rl.py HostPPOPolicy._returns_stage + process_fn (:255-283) and the graph of vtb_host.tracker_states
-extern "C" int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, void* stream) {
-    using namespace cirs;
-    if (int rc = validate(cfg)) return rc;
-    if (int rc = validate_bufs(b)) return rc;
-    const hipStream_t s = (hipStream_t)stream;
-    const Lay L = make_layout(*cfg);
-    if (cfg->model.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_forward_kernel<true>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
+int prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, bool redraw, hipStream_t s) {
+    const Lay L = make_layout(*cfg, redraw);
+    if (redraw) hipLaunchKernelGGL(vtb_learn_forward_redraw_kernel, dim3(L.n_wg), dim3(kT), 0, s, *cfg, *b, L);
+    else if (cfg->model.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_forward_kernel<true>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
     else hipLaunchKernelGGL(vtb_learn_forward_kernel<false>, dim3(cfg->n_env), dim3(kT), 0, s, *cfg, *b, L);
     CIRS_CHECK_LAUNCH("vtb_learn_forward_kernel");
     return returns_stage(*cfg, *b, L, 1, s);
 }
 
-// replaces core/host_rl.py HostPPOPolicy.learn (:286-316): ppo_objective + backward + clip_grad_norm_ + optim_RL.step per minibatch,
-// optim_state.step once at the end on the last pass's tracker gradient
-extern "C" int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
-                                     int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream) {
-    using namespace cirs;
-    if (int rc = validate(cfg)) return rc;
-    if (int rc = validate_bufs(b)) return rc;
+int update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, bool redraw, const int32_t* perms, int32_t repeat, int32_t batch_size,
+           int32_t recompute_adv, int64_t p_step0, int64_t t_step0, hipStream_t s) {
     CIRS_REQUIRE(perms != nullptr && b->losses != nullptr, "null permutations / losses");
     CIRS_REQUIRE(repeat >= 1 && batch_size >= 1, "repeat and batch_size must be >= 1");
     CIRS_REQUIRE(p_step0 >= 0 && t_step0 >= 0, "step counts must be >= 0");
-    const hipStream_t s = (hipStream_t)stream;
     const cirs_vtb_learn_cfg c = *cfg;
-    const Lay L = make_layout(c);
+    const Lay L = make_layout(c, redraw);
     const int n = c.n_rows;
     // row_ranges(n, batch_size): a short tail joins the range before it
     const int full = n / batch_size;
@@ -1093,11 +1148,72 @@ extern "C" int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_v
             CIRS_CHECK_LAUNCH("vtb_learn_adam_kernel");
         }
     }
-    if (c.model.dropout_p > 0.f) hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<true>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
-    else hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<false>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
+    if (redraw) {
+        CIRS_HIP(hipMemsetAsync(b->ws + L.w.tslab, 0, (size_t)L.n_wg * L.t.total * sizeof(float), s));
+        hipLaunchKernelGGL(vtb_learn_tracker_redraw_kernel, dim3(L.n_wg), dim3(kT), 0, s, c, *b, L);
+    } else if (c.model.dropout_p > 0.f) {
+        hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<true>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
+    } else {
+        hipLaunchKernelGGL(vtb_learn_tracker_bwd_kernel<false>, dim3(c.n_env), dim3(kT), 0, s, c, *b, L);
+    }
     CIRS_CHECK_LAUNCH("vtb_learn_tracker_bwd_kernel");
     const int g = cdiv(L.t.total, 256);
     hipLaunchKernelGGL(vtb_learn_tracker_adam_kernel, dim3(g < 1024 ? g : 1024), dim3(256), 0, s, c, *b, L, (long)t_step0 + 1);
     CIRS_CHECK_LAUNCH("vtb_learn_tracker_adam_kernel");
     return CIRS_OK;
+}
+
+}  // namespace
+}  // namespace cirs
+
+extern "C" int cirs_vtb_learn_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    return sizes(cfg, false, out);
+}
+
+// replaces core/host_rl.py HostPPOPolicy._returns_stage + process_fn (:255-283) and the graph of vtb_host.tracker_states
+extern "C" int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, void* stream) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    if (int rc = validate_bufs(b)) return rc;
+    return prepare(cfg, b, false, (hipStream_t)stream);
+}
+
+// replaces core/host_rl.py HostPPOPolicy.learn (:286-316): ppo_objective + backward + clip_grad_norm_ + optim_RL.step per minibatch,
+// optim_state.step once at the end on the last pass's tracker gradient
+extern "C" int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
+                                     int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    if (int rc = validate_bufs(b)) return rc;
+    return update(cfg, b, false, perms, repeat, batch_size, recompute_adv, p_step0, t_step0, (hipStream_t)stream);
+}
+
+// ---- exact-redraw mode ---------------------------------------------------------------------------------------------------------
+// The three calls above for a buffer of cirs_vtb_rollout_collect_redraw: the state of row (t, e) is call t's, of its obs_next call
+// t + 1's, and the tracker gradient goes through each call's own graph (reference core/state_tracker.py:170-250: one build_state call,
+// one retained graph; vtb_host.redraw_states).  Without dropout the calls coincide with the single causal pass: that one runs.
+extern "C" int cirs_vtb_learn_redraw_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    if (int rc = validate_redraw(cfg)) return rc;
+    return sizes(cfg, cfg->model.dropout_p > 0.f, out);
+}
+
+extern "C" int cirs_vtb_learn_prepare_redraw(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, void* stream) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    if (int rc = validate_redraw(cfg)) return rc;
+    if (int rc = validate_bufs(b)) return rc;
+    return prepare(cfg, b, cfg->model.dropout_p > 0.f, (hipStream_t)stream);
+}
+
+extern "C" int cirs_vtb_learn_update_redraw(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
+                                            int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream) {
+    using namespace cirs;
+    if (int rc = validate(cfg)) return rc;
+    if (int rc = validate_redraw(cfg)) return rc;
+    if (int rc = validate_bufs(b)) return rc;
+    return update(cfg, b, cfg->model.dropout_p > 0.f, perms, repeat, batch_size, recompute_adv, p_step0, t_step0, (hipStream_t)stream);
 }

@@ -15,6 +15,8 @@
 //
 // Dropout (DROP): the production mode of csrc/rng.h, position-keyed masks at the five sites of tracker.hip with its element
 // convention (ATTN: key_pos * nhead + head); a cached position keeps its masks for the rest of the episode.
+// Exact redraw (cirs_vtb_rollout_collect_redraw): call t runs the prefix 0..t again with masks of its own, as the reference's tracker in
+// train() does; vtb_policy_step_redraw_kernel below, built from the same row functions, so call 0 equals the decode's bit for bit.
 // fp32 throughout; matrices are [in][out] so that the lanes of a mat-vec read consecutive floats; the weights stay in L2.
 #include "common.h"
 #include "rng.h"
@@ -90,32 +92,50 @@ __device__ __forceinline__ float layer_norm(float v, int lane, int D, const floa
 
 __device__ __forceinline__ void wbar() { __builtin_amdgcn_wave_barrier(); }
 
-template <bool DROP>
-__global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w, cirs_vtb_traj tr,
-                                                                       int t, int steps, uint64_t seed, uint32_t collect_id) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int j = blockIdx.x * kWaves + wv;
-    const int B = cfg.n_env;
-    if (j >= B) return;
-    const int e = t == 0 ? j : tr.lists[(size_t)(t - 1) * B + j];
-    if (e < 0 || e >= B) return;      // wave-uniform: past the end of the previous step's active list
-    const int D = cfg.model.dim_model, H = cfg.model.nhead, HD = D / H, S = cfg.model.dim_state, L = cfg.model.max_len;
+// the LDS of one wave
+struct WaveLds {
+    float *xs, *qs, *ks, *vs, *att, *h1s, *ffs, *hb, *hc, *hinv, *ps;
+};
+__device__ __forceinline__ WaveLds wave_lds(float* smem, int wv, int H, int L) {
     float* base = smem + (size_t)wv * (kFixed + H * L);
-    float* xs = base;
-    float* qs = base + kMaxD;
-    float* ks = base + 2 * kMaxD;
-    float* vs = base + 3 * kMaxD;
-    float* att = base + 4 * kMaxD;
-    float* h1s = base + 5 * kMaxD;
-    float* ffs = base + 6 * kMaxD;
-    float* hb = ffs + kMaxHid;
-    float* hc = hb + kMaxW;
-    float* hinv = hc + kMaxW;
-    float* ps = hinv + kMaxD;
+    WaveLds s;
+    s.xs = base;
+    s.qs = base + kMaxD;
+    s.ks = base + 2 * kMaxD;
+    s.vs = base + 3 * kMaxD;
+    s.att = base + 4 * kMaxD;
+    s.h1s = base + 5 * kMaxD;
+    s.ffs = base + 6 * kMaxD;
+    s.hb = s.ffs + kMaxHid;
+    s.hc = s.hb + kMaxW;
+    s.hinv = s.hc + kMaxW;
+    s.ps = s.hinv + kMaxD;
+    return s;
+}
 
-    // ---- record the env step t-1 and build the input slot ------------------------------------------------------------
-    bool finished = false;
+// the dropout key of one pass: the masks of (dropout env id, position, layer, site, element) under the collect's key
+struct DropKey {
+    uint64_t seed;
+    uint32_t env, thr;
+    float inv;
+};
+__device__ __forceinline__ DropKey drop_key(const cirs_vtb_model_cfg& m, uint32_t env, bool on) {
+    DropKey k;
+    k.seed = m.dropout_seed;
+    k.env = env;
+    k.thr = on ? dropout_threshold(m.dropout_p) : 0u;
+    k.inv = on ? 1.0f / (1.0f - m.dropout_p) : 1.0f;
+    return k;
+}
+#define VTB_DROP(V, LAYER, SITE, ELEM) \
+    (dropout_keep(dk.seed, dk.env, (uint32_t)pos, (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), dk.thr) ? (V) * dk.inv : 0.f)
+
+// ---- record the env step t-1 of env e (list position j) and build the input slot t (lanes < D) ---------------------------
+__device__ __forceinline__ float record_and_slot(const cirs_vtb_rollout_cfg& cfg, const cirs_vtb_policy_weights& w, const cirs_vtb_traj& tr,
+                                                 const WaveLds& s, int t, int steps, int j, int e, int lane, bool& finished) {
+    const int B = cfg.n_env, D = cfg.model.dim_model;
+    float* hc = s.hc;
+    finished = false;
     float x = 0.f;
     if (t == 0) {
         const double* o0 = tr.obs0 + (size_t)e * kObs0;
@@ -146,98 +166,114 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
         }
     }
     wbar();
+    return x;
+}
 
-    // ---- decode position t ---------------------------------------------------------------------------------------------
-    const int pos = t;
-    const uint32_t d_thr = DROP ? dropout_threshold(cfg.model.dropout_p) : 0u;
-    const float d_inv = DROP ? 1.0f / (1.0f - cfg.model.dropout_p) : 1.0f;
-    const uint32_t d_env = (uint32_t)(cfg.model.drop_env_base + e);
-#define VTB_DROP(V, LAYER, SITE, ELEM) \
-    (dropout_keep(cfg.model.dropout_seed, d_env, (uint32_t)pos, (uint32_t)(LAYER), (uint32_t)(SITE), (uint32_t)(ELEM), d_thr) ? (V) * d_inv : 0.f)
+// the encoder's input row at position pos from the slot x: x * sqrt(D) + pe[pos], PE-output dropout
+template <bool DROP>
+__device__ __forceinline__ float embed_row(const cirs_vtb_policy_weights& w, const DropKey& dk, float x, int pos, int D, int lane) {
     float h = 0.f;
     if (lane < D) {
         h = x * sqrtf((float)D) + w.pe[(size_t)pos * D + lane];
         if (DROP) h = VTB_DROP(h, 0, CIRS_DROP_POS, lane);
     }
+    return h;
+}
+
+// ---- one post-norm TransformerEncoderLayer for the row at position pos ----------------------------------------------------
+// h (lanes < D) in, the layer's output back.  Causal attention of pos over 0..pos: the row's own K/V from LDS, rows 0..pos-1 from
+// kc / vc [max_len][D]; STORE_KV also writes the row's K/V there (the decode's cache).
+template <bool DROP, bool STORE_KV>
+__device__ __forceinline__ float encoder_row(const cirs_vtb_model_cfg& m, const cirs_vtb_policy_layer& ly, const WaveLds& s, const DropKey& dk,
+                                             int l, int pos, float h, float* kc, float* vc, int lane) {
+    const int D = m.dim_model, H = m.nhead, HD = D / H, L = m.max_len;
+    float *xs = s.xs, *qs = s.qs, *ks = s.ks, *vs = s.vs, *att = s.att, *h1s = s.h1s, *ffs = s.ffs, *hinv = s.hinv, *ps = s.ps;
     const float qscale = 1.0f / sqrtf((float)HD);
-    for (int l = 0; l < cfg.model.nlayers; ++l) {
-        const cirs_vtb_policy_layer& ly = w.layer[l];
-        if (lane < D) xs[lane] = h;
-        wbar();
-        float* kc = tr.kcache + (((size_t)l * B + e) * L) * D;
-        float* vc = tr.vcache + (((size_t)l * B + e) * L) * D;
-        if (lane < D) {
-            const float q = mv(ly.in_w, ly.in_b, xs, D, 3 * D, lane);
-            const float k = mv(ly.in_w, ly.in_b, xs, D, 3 * D, D + lane);
-            const float v = mv(ly.in_w, ly.in_b, xs, D, 3 * D, 2 * D + lane);
-            qs[lane] = q * qscale;
-            ks[lane] = k;
-            vs[lane] = v;
+    if (lane < D) xs[lane] = h;
+    wbar();
+    if (lane < D) {
+        const float q = mv(ly.in_w, ly.in_b, xs, D, 3 * D, lane);
+        const float k = mv(ly.in_w, ly.in_b, xs, D, 3 * D, D + lane);
+        const float v = mv(ly.in_w, ly.in_b, xs, D, 3 * D, 2 * D + lane);
+        qs[lane] = q * qscale;
+        ks[lane] = k;
+        vs[lane] = v;
+        if (STORE_KV) {
             kc[(size_t)pos * D + lane] = k;
             vc[(size_t)pos * D + lane] = v;
         }
-        wbar();
-        // causal attention of position pos over 0..pos, one head after the other; lanes stride over the key positions
-        for (int hh = 0; hh < H; ++hh) {
-            float mx = -INFINITY;
-            for (int jp = lane; jp <= pos; jp += 64) {
-                const float* kr = jp == pos ? ks : kc + (size_t)jp * D;
-                float sc = 0.f;
-                for (int d = 0; d < HD; ++d) sc = __builtin_fmaf(qs[hh * HD + d], kr[hh * HD + d], sc);
-                ps[hh * L + jp] = sc;
-                mx = fmaxf(mx, sc);
-            }
-            mx = wave_max_f32(mx);
-            float sm = 0.f;
-            for (int jp = lane; jp <= pos; jp += 64) {
-                const float ex = expf(ps[hh * L + jp] - mx);
-                sm += ex;
-                // attention-probability dropout acts after the softmax: the normaliser sums the unmasked terms
-                ps[hh * L + jp] = DROP ? VTB_DROP(ex, l, CIRS_DROP_ATTN, jp * H + hh) : ex;
-            }
-            sm = wave_sum_f32(sm);
-            if (lane == 0) hinv[hh] = 1.0f / sm;
-        }
-        wbar();
-        if (lane < D) {
-            const int hh = lane / HD;
-            const float* pr = ps + hh * L;
-            float acc = 0.f;
-#pragma unroll 4
-            for (int jp = 0; jp < pos; ++jp) acc = __builtin_fmaf(pr[jp], vc[(size_t)jp * D + lane], acc);
-            acc = __builtin_fmaf(pr[pos], vs[lane], acc);
-            att[lane] = acc * hinv[hh];
-        }
-        wbar();
-        // out_proj + residual + LayerNorm 1
-        float sa = lane < D ? mv(ly.out_w, ly.out_b, att, D, D, lane) : 0.f;
-        if (DROP && lane < D) sa = VTB_DROP(sa, l, CIRS_DROP_RES1, lane);
-        const float h1 = layer_norm(h + sa, lane, D, ly.norm1_w, ly.norm1_b);
-        if (lane < D) h1s[lane] = h1;
-        wbar();
-        // feed-forward (ReLU) + residual + LayerNorm 2
-        for (int i = lane; i < cfg.model.d_hid; i += 64) {
-            float f = fmaxf(mv(ly.lin1_w, ly.lin1_b, h1s, D, cfg.model.d_hid, i), 0.f);
-            if (DROP) f = VTB_DROP(f, l, CIRS_DROP_FF, i);
-            ffs[i] = f;
-        }
-        wbar();
-        float f2 = lane < D ? mv(ly.lin2_w, ly.lin2_b, ffs, cfg.model.d_hid, D, lane) : 0.f;
-        if (DROP && lane < D) f2 = VTB_DROP(f2, l, CIRS_DROP_RES2, lane);
-        h = layer_norm(h1 + f2, lane, D, ly.norm2_w, ly.norm2_b);
-        wbar();
     }
+    wbar();
+    // causal attention of position pos over 0..pos, one head after the other; lanes stride over the key positions
+    for (int hh = 0; hh < H; ++hh) {
+        float mx = -INFINITY;
+        for (int jp = lane; jp <= pos; jp += 64) {
+            const float* kr = jp == pos ? ks : kc + (size_t)jp * D;
+            float sc = 0.f;
+            for (int d = 0; d < HD; ++d) sc = __builtin_fmaf(qs[hh * HD + d], kr[hh * HD + d], sc);
+            ps[hh * L + jp] = sc;
+            mx = fmaxf(mx, sc);
+        }
+        mx = wave_max_f32(mx);
+        float sm = 0.f;
+        for (int jp = lane; jp <= pos; jp += 64) {
+            const float ex = expf(ps[hh * L + jp] - mx);
+            sm += ex;
+            // attention-probability dropout acts after the softmax: the normaliser sums the unmasked terms
+            ps[hh * L + jp] = DROP ? VTB_DROP(ex, l, CIRS_DROP_ATTN, jp * H + hh) : ex;
+        }
+        sm = wave_sum_f32(sm);
+        if (lane == 0) hinv[hh] = 1.0f / sm;
+    }
+    wbar();
+    if (lane < D) {
+        const int hh = lane / HD;
+        const float* pr = ps + hh * L;
+        float acc = 0.f;
+#pragma unroll 4
+        for (int jp = 0; jp < pos; ++jp) acc = __builtin_fmaf(pr[jp], vc[(size_t)jp * D + lane], acc);
+        acc = __builtin_fmaf(pr[pos], vs[lane], acc);
+        att[lane] = acc * hinv[hh];
+    }
+    wbar();
+    // out_proj + residual + LayerNorm 1
+    float sa = lane < D ? mv(ly.out_w, ly.out_b, att, D, D, lane) : 0.f;
+    if (DROP && lane < D) sa = VTB_DROP(sa, l, CIRS_DROP_RES1, lane);
+    const float h1 = layer_norm(h + sa, lane, D, ly.norm1_w, ly.norm1_b);
+    if (lane < D) h1s[lane] = h1;
+    wbar();
+    // feed-forward (ReLU) + residual + LayerNorm 2
+    for (int i = lane; i < m.d_hid; i += 64) {
+        float f = fmaxf(mv(ly.lin1_w, ly.lin1_b, h1s, D, m.d_hid, i), 0.f);
+        if (DROP) f = VTB_DROP(f, l, CIRS_DROP_FF, i);
+        ffs[i] = f;
+    }
+    wbar();
+    float f2 = lane < D ? mv(ly.lin2_w, ly.lin2_b, ffs, m.d_hid, D, lane) : 0.f;
+    if (DROP && lane < D) f2 = VTB_DROP(f2, l, CIRS_DROP_RES2, lane);
+    const float out = layer_norm(h1 + f2, lane, D, ly.norm2_w, ly.norm2_b);
+    wbar();
+    return out;
+}
 #undef VTB_DROP
+
+// ---- decoder on the encoder's output row h of position t, then the actor ---------------------------------------------------
+// state s_t -> traj.state; unless the env has finished: Net trunk, mu / sigma, act = mu + sigma * z, the mapped action at a compacted
+// position of the next active list
+__device__ __forceinline__ void decode_and_act(const cirs_vtb_rollout_cfg& cfg, const cirs_vtb_policy_weights& w, const cirs_vtb_traj& tr,
+                                               const WaveLds& sl, float h, int t, int e, int lane, bool finished, uint64_t seed,
+                                               uint32_t collect_id) {
+    const int B = cfg.n_env, D = cfg.model.dim_model, S = cfg.model.dim_state;
+    float *xs = sl.xs, *hb = sl.hb, *hc = sl.hc;
     if (lane < D) xs[lane] = h;
     wbar();
     float s = 0.f;
     if (lane < S) {
         s = mv(w.dec_w, w.dec_b, xs, D, S, lane);
-        tr.state[((size_t)pos * B + e) * S + lane] = s;
+        tr.state[((size_t)t * B + e) * S + lane] = s;
     }
     if (finished) return;      // wave-uniform
 
-    // ---- actor --------------------------------------------------------------------------------------------------------
     if (lane < S) hb[lane] = s;
     wbar();
     float* in = hb;
@@ -279,6 +315,93 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
     wbar();
     if (lane < kA) tr.act_buf[(size_t)p * kA + lane] = xs[lane];
     if (lane == 0) tr.lists[(size_t)t * B + p] = e;
+}
+
+// ---- position-keyed mode: one wave per env, K/V-cached decode of position t ------------------------------------------------
+template <bool DROP>
+__global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w, cirs_vtb_traj tr,
+                                                                       int t, int steps, uint64_t seed, uint32_t collect_id) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j = blockIdx.x * kWaves + wv;
+    const int B = cfg.n_env;
+    if (j >= B) return;
+    const int e = t == 0 ? j : tr.lists[(size_t)(t - 1) * B + j];
+    if (e < 0 || e >= B) return;      // wave-uniform: past the end of the previous step's active list
+    const int D = cfg.model.dim_model, L = cfg.model.max_len;
+    const WaveLds s = wave_lds(smem, wv, cfg.model.nhead, L);
+    bool finished;
+    const float x = record_and_slot(cfg, w, tr, s, t, steps, j, e, lane, finished);
+    const DropKey dk = drop_key(cfg.model, (uint32_t)(cfg.model.drop_env_base + e), DROP);
+    float h = embed_row<DROP>(w, dk, x, t, D, lane);
+    for (int l = 0; l < cfg.model.nlayers; ++l) {
+        float* kc = tr.kcache + (((size_t)l * B + e) * L) * D;
+        float* vc = tr.vcache + (((size_t)l * B + e) * L) * D;
+        h = encoder_row<DROP, true>(cfg.model, w.layer[l], s, dk, l, t, h, kc, vc, lane);
+    }
+    decode_and_act(cfg, w, tr, s, h, t, e, lane, finished, seed, collect_id);
+}
+
+// ---- exact-redraw mode (dropout_redraw): one workgroup per env, the whole prefix 0..t again with the masks of call t ----------
+// Call t of env e draws the masks of dropout env id drop_env_base + t * n_env + e at every position 0..t, so nothing of an earlier call
+// can be kept: per layer, phase A writes the K/V of every row of the layer's input (rows dealt to the waves), phase B runs the layer's
+// rows -- all of them below the top layer, whose outputs are the next layer's input, the last row only in the top layer.  The slots
+// x_0..x_t are kept (they carry no mask).  ws: slots [max_len][n_env][D] | layer outputs [nlayers - 1][n_env][max_len][D].
+constexpr int kRedrawWaves = 8;
+__global__ __launch_bounds__(64 * kRedrawWaves) void vtb_policy_step_redraw_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w,
+                                                                                   cirs_vtb_traj tr, float* ws, int t, int steps, uint64_t seed,
+                                                                                   uint32_t collect_id) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int j = blockIdx.x;
+    const int B = cfg.n_env;
+    const int e = t == 0 ? j : tr.lists[(size_t)(t - 1) * B + j];
+    if (e < 0 || e >= B) return;      // workgroup-uniform: past the end of the previous step's active list
+    const int D = cfg.model.dim_model, L = cfg.model.max_len, NL = cfg.model.nlayers;
+    const WaveLds s = wave_lds(smem, wv, cfg.model.nhead, L);
+    float* slot = ws;
+    float* rows = ws + (size_t)L * B * D;
+    bool finished = false;
+    if (wv == 0) {
+        const float x = record_and_slot(cfg, w, tr, s, t, steps, j, e, lane, finished);
+        if (lane < D) slot[((size_t)t * B + e) * D + lane] = x;
+    }
+    __syncthreads();
+    const DropKey dk = drop_key(cfg.model, (uint32_t)(cfg.model.drop_env_base + t * B + e), true);
+    float h_top = 0.f;
+    for (int l = 0; l < NL; ++l) {
+        const cirs_vtb_policy_layer& ly = w.layer[l];
+        float* kc = tr.kcache + (((size_t)l * B + e) * L) * D;
+        float* vc = tr.vcache + (((size_t)l * B + e) * L) * D;
+        const float* in = l == 0 ? nullptr : rows + (((size_t)(l - 1) * B + e) * L) * D;
+        float* out = rows + (((size_t)l * B + e) * L) * D;      // not written by the top layer
+        const bool top = l == NL - 1;
+        auto row_in = [&](int p) {
+            if (l > 0) return lane < D ? in[(size_t)p * D + lane] : 0.f;
+            return embed_row<true>(w, dk, lane < D ? slot[((size_t)p * B + e) * D + lane] : 0.f, p, D, lane);
+        };
+        for (int p = wv; p <= t; p += kRedrawWaves) {      // phase A
+            const float h = row_in(p);
+            if (lane < D) s.xs[lane] = h;
+            wbar();
+            if (lane < D) {
+                kc[(size_t)p * D + lane] = mv(ly.in_w, ly.in_b, s.xs, D, 3 * D, D + lane);
+                vc[(size_t)p * D + lane] = mv(ly.in_w, ly.in_b, s.xs, D, 3 * D, 2 * D + lane);
+            }
+            wbar();
+        }
+        __syncthreads();
+        if (top) {                                           // phase B
+            if (wv == 0) h_top = encoder_row<true, false>(cfg.model, ly, s, dk, l, t, row_in(t), kc, vc, lane);
+        } else {
+            for (int p = wv; p <= t; p += kRedrawWaves) {
+                const float o = encoder_row<true, false>(cfg.model, ly, s, dk, l, p, row_in(p), kc, vc, lane);
+                if (lane < D) out[(size_t)p * D + lane] = o;
+            }
+        }
+        __syncthreads();
+    }
+    if (wv == 0) decode_and_act(cfg, w, tr, s, h_top, t, e, lane, finished, seed, collect_id);
 }
 
 __global__ __launch_bounds__(256) void vtb_gauss_kernel(uint64_t seed, uint32_t collect_id, const int32_t* __restrict__ ids,
@@ -343,12 +466,24 @@ int validate_rollout(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weig
 }  // namespace
 }  // namespace cirs
 
-extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
-                                        const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
-                                        uint32_t collect_id, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_rollout(cfg, pw, vtb_cfg, traj)) return rc;
-    CIRS_REQUIRE(vtb_w && vtb_st, "null env weights / state");
+namespace cirs {
+namespace {
+
+// what the exact-redraw mode adds to validate_rollout
+int validate_redraw(const cirs_vtb_rollout_cfg* cfg) {
+    CIRS_REQUIRE(cfg != nullptr, "null rollout argument");
+    const cirs_vtb_model_cfg* m = &cfg->model;
+    CIRS_REQUIRE((long)m->drop_env_base + ((long)cfg->max_turn + 1) * cfg->n_env < (1L << 31),
+                 "dropout_redraw: drop_env_base + (max_turn + 1) * n_env must be < 2^31 (call c of env e draws dropout env id "
+                 "drop_env_base + c * n_env + e)");
+    CIRS_REQUIRE((size_t)kRedrawWaves * (kFixed + (size_t)m->nhead * m->max_len) * sizeof(float) <= 65536,
+                 "dropout_redraw: nhead * max_len must be <= 1088 (8 waves per env in 64 KB of LDS)");
+    return CIRS_OK;
+}
+
+// redraw_ws == nullptr: the position-keyed mode
+int collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg, const cirs_vtb_weights* vtb_w,
+            cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws, uint64_t seed, uint32_t collect_id, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     const cirs_vtb_rollout_cfg c = *cfg;
     const cirs_vtb_traj tr = *traj;
@@ -366,13 +501,19 @@ extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const c
     CIRS_HIP(hipMemsetAsync(tr.ctr, 0, T * B * sizeof(double), s));
     CIRS_HIP(hipMemsetAsync(tr.done, 0, T * B, s));
     if (int rc = cirs_vtb_reset(vtb_cfg, vtb_w, vtb_st, c.env_seed, nullptr, B, tr.obs0, stream)) return rc;
-    const size_t shmem = (size_t)kWaves * (kFixed + (size_t)c.model.nhead * c.model.max_len) * sizeof(float);
+    const size_t wave_lds_bytes = (kFixed + (size_t)c.model.nhead * c.model.max_len) * sizeof(float);
     const dim3 grid(cdiv(B, kWaves)), block(64 * kWaves);
     const bool drop = c.model.dropout_p > 0.f;
     for (int t = 0; t <= steps; ++t) {
-        if (drop) hipLaunchKernelGGL(vtb_policy_step_kernel<true>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);
-        else hipLaunchKernelGGL(vtb_policy_step_kernel<false>, grid, block, shmem, s, c, *pw, tr, t, steps, seed, collect_id);
-        CIRS_CHECK_LAUNCH("vtb_policy_step_kernel");
+        if (redraw_ws) {
+            hipLaunchKernelGGL(vtb_policy_step_redraw_kernel, dim3(B), dim3(64 * kRedrawWaves), kRedrawWaves * wave_lds_bytes, s, c, *pw, tr,
+                               redraw_ws, t, steps, seed, collect_id);
+            CIRS_CHECK_LAUNCH("vtb_policy_step_redraw_kernel");
+        } else {
+            if (drop) hipLaunchKernelGGL(vtb_policy_step_kernel<true>, grid, block, kWaves * wave_lds_bytes, s, c, *pw, tr, t, steps, seed, collect_id);
+            else hipLaunchKernelGGL(vtb_policy_step_kernel<false>, grid, block, kWaves * wave_lds_bytes, s, c, *pw, tr, t, steps, seed, collect_id);
+            CIRS_CHECK_LAUNCH("vtb_policy_step_kernel");
+        }
         if (t == steps) break;
         // the env step of list t (ids past the active count are -1: empty slots)
         if (int rc = cirs_vtb_step(vtb_cfg, vtb_w, vtb_st, c.env_seed, tr.act_buf, tr.lists + (size_t)t * B, B, tr.step_obs, tr.step_rew,
@@ -380,6 +521,32 @@ extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const c
             return rc;
     }
     return CIRS_OK;
+}
+
+}  // namespace
+}  // namespace cirs
+
+extern "C" int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                        const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
+                                        uint32_t collect_id, void* stream) {
+    using namespace cirs;
+    if (int rc = validate_rollout(cfg, pw, vtb_cfg, traj)) return rc;
+    CIRS_REQUIRE(vtb_w && vtb_st, "null env weights / state");
+    return collect(cfg, pw, vtb_cfg, vtb_w, vtb_st, traj, nullptr, seed, collect_id, stream);
+}
+
+// replaces the per-call dropout of core/state_tracker.py:170-250 (the tracker stays in train(): build_state runs the whole prefix through
+// the encoder again and nn.Dropout draws fresh masks at every call)
+extern "C" int cirs_vtb_rollout_collect_redraw(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                               const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws,
+                                               uint64_t seed, uint32_t collect_id, void* stream) {
+    using namespace cirs;
+    if (int rc = validate_redraw(cfg)) return rc;
+    if (int rc = validate_rollout(cfg, pw, vtb_cfg, traj)) return rc;
+    CIRS_REQUIRE(vtb_w && vtb_st, "null env weights / state");
+    CIRS_REQUIRE(redraw_ws != nullptr, "dropout_redraw: null workspace (max_len * n_env * dim_model * nlayers floats)");
+    // without dropout every call's prefix pass equals the cached decode: run that
+    return collect(cfg, pw, vtb_cfg, vtb_w, vtb_st, traj, cfg->model.dropout_p > 0.f ? redraw_ws : nullptr, seed, collect_id, stream);
 }
 
 extern "C" int cirs_vtb_rollout_noise(uint64_t seed, uint32_t collect_id, const int32_t* env_ids, const int32_t* ts, int32_t n, int32_t dims,

@@ -864,6 +864,17 @@ typedef struct cirs_vtb_traj { /* device buffers owned by the caller; t = vector
 int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
                              const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
                              uint32_t collect_id, void* stream);
+/* cirs_vtb_rollout_collect with the reference's own dropout procedure (core/state_tracker.py:170-250: the tracker stays in train(), every
+ * build_state call runs the whole prefix through the encoder again and nn.Dropout draws fresh masks over it).  Call c of env e (c = 0 on
+ * the reset observation, c = len_e after the last step) is ONE causal pass over the input slots 0..c with masks of its own at all five
+ * sites, those of dropout env id drop_env_base + c * n_env + e (cirs_vtb_rollout_masks with env0 = c * n_env, n_pos = c + 1), and hands
+ * out the state of position c.  Call 0 has the position-keyed key: state[0] is the same in both modes, bit for bit.  One workgroup per
+ * env per vector step; K/V of the prefix are rebuilt at every call.  model.dropout_p == 0 runs cirs_vtb_rollout_collect's own launches.
+ * redraw_ws: max_len * n_env * dim_model * nlayers floats of scratch.  Refused: drop_env_base + (max_turn + 1) * n_env >= 2^31,
+ * nhead * max_len > 1088. */
+int cirs_vtb_rollout_collect_redraw(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                    const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws,
+                                    uint64_t seed, uint32_t collect_id, void* stream);
 /* the standard normals z the policy kernel draws for (env_ids[j], ts[j], dim 0..dims-1): out [n][dims] fp32, bit for bit.
  * Box-Muller on Philox (counter (dim / 4, env, t, collect_id), key seed ^ 'GAUS'): the words (w0, w1) give dims 4b, 4b+1, (w2, w3)
  * dims 4b+2, 4b+3; u = u01_from_bits(w); z = sqrt(-2 det_logf(u1)) * {cos, sin}(2 pi u2) with fixed polynomials. */
@@ -930,6 +941,18 @@ int cirs_vtb_learn_prepare(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_b
  * No host synchronisation. */
 int cirs_vtb_learn_update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
                           int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream);
+/* The same three calls over the buffer of a cirs_vtb_rollout_collect_redraw (reference core/state_tracker.py:170-250 with
+ * core/policy/ppo.py:96-246: every build_state call keeps a graph of its own).  Row (t, e) has obs = the state of call t and obs_next =
+ * the state of call t + 1; the tracker gradient is the sum over the sampled rows of dL/d obs pushed through that call's own pass
+ * (positions 0..t of env e, masks of dropout env id drop_env_base + t * n_env + e, gradient on the last position only).  Each tracker
+ * workgroup runs forward and backward of its calls one after the other in one episode workspace and adds into one gradient slab, in a
+ * fixed order; min(8, 1024 / n_env) (at least 1) workgroups per env, so the workspace (sizes out[2]) does not grow with the number of
+ * calls.  Everything else is cirs_vtb_learn_*'s.  model.dropout_p == 0 runs those calls' own launches.  Refused:
+ * drop_env_base + (max_turn + 1) * n_env >= 2^31. */
+int cirs_vtb_learn_redraw_sizes(const cirs_vtb_learn_cfg* cfg, int64_t* out);
+int cirs_vtb_learn_prepare_redraw(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, void* stream);
+int cirs_vtb_learn_update_redraw(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, const int32_t* perms, int32_t repeat,
+                                 int32_t batch_size, int32_t recompute_adv, int64_t p_step0, int64_t t_step0, void* stream);
 
 /* ---- VirtualTaobao user-model training (csrc/mmoe_train.hip) ---------------------------------------------------------------
  * One optimiser step of UserModel_MMOE.fit_data's inner loop (reference core/user_model.py:150-170, core/user_model_mmoe.py:144-233,
