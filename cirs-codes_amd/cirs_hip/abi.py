@@ -126,6 +126,33 @@ class VtbState(C.Structure):     # cirs_vtb_state
     _fields_ = [(k, C.c_void_p) for k in ("task_user", "sim_user", "turn", "event", "prev_reward", "cum_reward", "lst_action", "hist")]
 
 
+VTB_STATIC_STATE_DIM, VTB_STATIC_MAX_DNN, VTB_STATIC_NOISE_COLS = 91, 3, 265
+
+
+def vtb_static_metrics_bytes(n_traj):    # CIRS_VTB_STATIC_METRICS_BYTES
+    return 48 + 4 * int(n_traj)
+
+
+class VtbMmoeShape(C.Structure):     # cirs_vtb_mmoe_shape
+    _fields_ = [("d_in", C.c_int32), ("n_dnn", C.c_int32), ("hidden", C.c_int32 * VTB_STATIC_MAX_DNN), ("experts", C.c_int32),
+                ("expert_dim", C.c_int32), ("n_tasks", C.c_int32), ("task_dim", C.c_int32 * 2)]
+
+
+class VtbMmoeWeights(C.Structure):   # cirs_vtb_mmoe_weights
+    _fields_ = [("dnn_w", C.c_void_p * VTB_STATIC_MAX_DNN), ("dnn_b", C.c_void_p * VTB_STATIC_MAX_DNN), ("expert_w", C.c_void_p),
+                ("expert_b", C.c_void_p), ("gate_w", C.c_void_p * 2), ("tower_w", C.c_void_p * 2), ("lin_w", C.c_void_p),
+                ("bias", C.c_void_p * 2)]
+
+
+class VtbStaticCfg(C.Structure):     # cirs_vtb_static_cfg
+    _fields_ = [("n_traj", C.c_int32), ("max_turn", C.c_int32), ("num_leave_compute", C.c_int32), ("reserved", C.c_int32),
+                ("leave_threshold", C.c_double), ("epsilon", C.c_double), ("policy", VtbMmoeShape)]
+
+
+class VtbStaticOut(C.Structure):     # cirs_vtb_static_out
+    _fields_ = [(k, C.c_void_p) for k in ("user", "state", "action", "reward_pred", "reward", "done", "explore", "metrics")]
+
+
 VTB_RO_MAX_LAYERS, VTB_RO_MAX_HIDDEN = 4, 3
 
 
@@ -195,6 +222,10 @@ SIGNATURES = {
                                 _P, _P, _P, _P, _P, _P]),
     "cirs_vtb_noise": (C.c_int, [C.c_uint64, _P, _P, C.c_int32, _P, _P]),
     "cirs_vtb_mmoe_forward": (C.c_int, [C.POINTER(VtbCfg), C.POINTER(VtbWeights), _P, C.c_int32, _P, _P]),
+    "cirs_vtb_static_workspace_bytes": (C.c_int64, [C.POINTER(VtbStaticCfg)]),
+    "cirs_vtb_static_eval": (C.c_int, [C.POINTER(VtbStaticCfg), C.POINTER(VtbWeights), C.POINTER(VtbMmoeWeights), C.c_uint64,
+                                       C.POINTER(VtbStaticOut), _P, C.c_int64, _P]),
+    "cirs_vtb_static_noise": (C.c_int, [C.c_uint64, _P, _P, C.c_int32, _P, _P]),
     "cirs_vtb_rollout_collect": (C.c_int, [C.POINTER(VtbRolloutCfg), C.POINTER(VtbPolicyWeights), C.POINTER(VtbCfg), C.POINTER(VtbWeights),
                                            C.POINTER(VtbState), C.POINTER(VtbTraj), C.c_uint64, C.c_uint32, _P]),
     "cirs_vtb_rollout_noise": (C.c_int, [C.c_uint64, C.c_uint32, _P, _P, C.c_int32, C.c_int32, _P, _P]),

@@ -40,6 +40,17 @@ def _mmoe_shape(model):
                 mmoe_tasks=len(model.tower_network), mmoe_task_dim=int(model.tower_network[0].out_features))
 
 
+def env_weights(vtb_env, dev):
+    """The generator's and the action model's fields of cirs_vtb_weights as device tensors, read off a host VirtualTB."""
+    g, a = _linears(vtb_env.generator), _linears(vtb_env.action_model)
+    if [(m.in_features, m.out_features) for m in g] != [(128, 128), (128, USER_DIM)] or \
+            [(m.in_features, m.out_features) for m in a] != [(USER_DIM + 1 + ACTION_DIM, 128), (128, 256), (256, 21)]:
+        raise ValueError("unexpected VirtualTB generator / action-model shapes")
+    return dict(gen_w1=_t(g[0].weight, dev), gen_b1=_v(g[0].bias, dev), gen_w2=_t(g[1].weight, dev), gen_b2=_v(g[1].bias, dev),
+                act_w1=_t(a[0].weight, dev), act_b1=_v(a[0].bias, dev), act_w2=_t(a[1].weight, dev), act_b2=_v(a[1].bias, dev),
+                act_w3=_t(a[2].weight, dev), act_b3=_v(a[2].bias, dev))
+
+
 class DeviceVirtualTB:
     """n_env VirtualTaobao envs stepped by one kernel launch.  user_model=None: raw VirtualTB-v0 (reward = clicks); otherwise
     SimulatedEnv(VirtualTB-v0) with that UserModel_MMOE and the exposure effect."""
@@ -61,13 +72,7 @@ class DeviceVirtualTB:
                               simulated=int(self.simulated), version=int(ver), use_exposure=int(bool(use_exposure_intervention)),
                               leave_threshold=float(vtb_env.leave_threshold), tau=float(tau), gamma_exposure=float(gamma_exposure), **shape)
         dev = self.device
-        g, a = _linears(vtb_env.generator), _linears(vtb_env.action_model)
-        if [(m.in_features, m.out_features) for m in g] != [(128, 128), (128, USER_DIM)] or \
-                [(m.in_features, m.out_features) for m in a] != [(USER_DIM + 1 + ACTION_DIM, 128), (128, 256), (256, 21)]:
-            raise ValueError("unexpected VirtualTB generator / action-model shapes")
-        w = dict(gen_w1=_t(g[0].weight, dev), gen_b1=_v(g[0].bias, dev), gen_w2=_t(g[1].weight, dev), gen_b2=_v(g[1].bias, dev),
-                 act_w1=_t(a[0].weight, dev), act_b1=_v(a[0].bias, dev), act_w2=_t(a[1].weight, dev), act_b2=_v(a[1].bias, dev),
-                 act_w3=_t(a[2].weight, dev), act_b3=_v(a[2].bias, dev))
+        w = env_weights(vtb_env, dev)
         if self.simulated:
             m = user_model
             w.update(mm_w1=_t(m.dnn.linears[0].weight, dev), mm_b1=_v(m.dnn.linears[0].bias, dev),

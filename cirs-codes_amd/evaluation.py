@@ -2,6 +2,7 @@
 
   get_feat_dominate_dict   evaluation.py:10-77  ("ifeat_feat": share of recommendations carrying a dominating category)
   Callback_Coverage_Count  evaluation.py:286-371 (CV, CV_turn and ifeat_* for the FB / NX_0 / NX_k test collectors)
+  test_taobao              evaluation.py:238-282  (the VirtualTaobao static baselines: MLP-taobao.py, MLP-epsilonGreedy-taobao.py)
 
 The reference walks the replay buffers on the host (buffer.prev / buffer.next); here each collector's buffer carries the
 device trajectory of its fused rollout and the counts come from cirs_eval_coverage (integer kernel, bit-exact)."""
@@ -155,6 +156,45 @@ def test_static_model_in_RL_env(model, env, dataset_val, is_softmax=True, epsilo
 
 
 test_static_model_in_RL_env.__test__ = False  # not a pytest test
+
+
+def test_taobao(model, env, epsilon=0, *, device=None, num_trajectory=100, seed=0):
+    """reference evaluation.py:238-282: `model` (two-task UserModel_MMOE: static state 91 -> 27 item features + click prediction)
+    plays num_trajectory trajectories against `env`, a VirtualTB in static-state mode -> {"ctr", "click_loss", "len_tra", "R_tra"}.
+
+    device=None: the reference's procedure on the host, statement for statement, so torch's and numpy's global generators are consumed
+    as the reference consumes them (the epsilon draw only when epsilon > 0; the exploration action is np.random.random(27); the action is
+    the raw prediction, not clipped to the action box).  device="cuda": every trajectory in lock step inside one launch
+    (cirs_hip.vtb_static.DeviceVtbStaticEval; counter-based noise keyed by `seed`, env weights and exit-rule settings read off `env`)."""
+    if not getattr(env, "static", False):
+        raise ValueError("test_taobao plays the static baselines: the env must be in static-state mode (env.set_state_mode(True)); the "
+                         "policy's 91 inputs are the static state [user | last clicks, last second draw | turn]")
+    if device is not None:
+        from cirs_hip.vtb_static import DeviceVtbStaticEval
+        return DeviceVtbStaticEval(env, model, num_trajectory, seed=seed, device=device).run(epsilon)
+    cumulative_reward = 0
+    total_click_loss = 0
+    total_turns = 0
+    for i in range(num_trajectory):
+        features = env.reset()
+        done = False
+        while not done:
+            res = model(torch.FloatTensor(features).to(model.device).unsqueeze(0)).to("cpu").squeeze()
+            item_feat_predict = res[model.y_index["feat_item"][0]:model.y_index["feat_item"][1]]
+            action = item_feat_predict.detach().numpy()
+            if epsilon > 0 and np.random.random() < epsilon:
+                action = np.random.random(action.shape)
+            reward_pred = res[model.y_index["y"][0]:model.y_index["y"][1]]
+            features, reward, done, info = env.step(action)
+            total_turns += 1
+            cumulative_reward += reward
+            total_click_loss += np.absolute(float(reward_pred.detach().numpy().reshape(-1)[0]) - reward)
+    ctr = cumulative_reward / total_turns
+    click_loss = total_click_loss / total_turns
+    return {"ctr": ctr, "click_loss": click_loss, "len_tra": total_turns / num_trajectory, "R_tra": cumulative_reward / num_trajectory}
+
+
+test_taobao.__test__ = False  # not a pytest test
 
 
 class Callback_Coverage_Count:

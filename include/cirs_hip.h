@@ -777,6 +777,73 @@ int cirs_vtb_noise(uint64_t seed, const int32_t* env_ids, const uint32_t* events
 int cirs_vtb_mmoe_forward(const cirs_vtb_cfg* cfg, const cirs_vtb_weights* w, const float* x, int32_t n, float* y_out,
                           void* stream);
 
+/* ---- VirtualTaobao static baselines: a whole evaluation per launch (csrc/vtb_static.hip, csrc/vtb_mmoe.h) -------------------
+ * replaces  evaluation.py:238-282 (test_taobao: num_trajectory trajectories of a two-task UserModel_MMOE played against a
+ *           VirtualTB in static-state mode, one batch-1 forward and one host env step at a time; called at every epoch end by
+ *           MLP-taobao.py and MLP-epsilonGreedy-taobao.py) with core/user_model_mmoe.py:232-262 (the forward).
+ * Trajectory i is env id i of the Philox convention above: event 0 = its user draw (tag 1), event 1 + t = turn t (tag 0: the 21
+ * step Gumbels; tag 2: word 0 -> the epsilon uniform u01, words 1..27 -> the 27 exploration uniforms u01).  The user redrawn by
+ * VirtualTB.step on done is not drawn: test_taobao resets the env before it is ever seen. */
+#define CIRS_VTB_STATIC_STATE_DIM 91  /* [user one-hot 88 | last clicks, last second draw | turn] */
+#define CIRS_VTB_STATIC_MAX_DNN 3
+#define CIRS_VTB_STATIC_NOISE_COLS 265 /* cirs_vtb_noise's 237 | epsilon uniform | 27 exploration uniforms */
+/* bytes of cirs_vtb_static_out.metrics: double[4] | int64[2] | int32 len[n_traj] */
+#define CIRS_VTB_STATIC_METRICS_BYTES(n_traj) (48 + 4 * (int64_t)(n_traj))
+
+typedef struct cirs_vtb_mmoe_shape { /* all-dense UserModel_MMOE with two regression tasks (y_columns: feat_item, y) */
+    int32_t d_in;                             /* 91                                                       */
+    int32_t n_dnn;                            /* 1..CIRS_VTB_STATIC_MAX_DNN hidden layers (ReLU)          */
+    int32_t hidden[CIRS_VTB_STATIC_MAX_DNN];  /* each 1..256                                              */
+    int32_t experts, expert_dim;              /* experts * expert_dim <= 64                               */
+    int32_t n_tasks;                          /* 2                                                        */
+    int32_t task_dim[2];                      /* (27, 1)                                                  */
+} cirs_vtb_mmoe_shape;
+
+typedef struct cirs_vtb_mmoe_weights { /* fp32, TRANSPOSED ([in][out]) like cirs_vtb_weights */
+    const float* dnn_w[CIRS_VTB_STATIC_MAX_DNN];
+    const float* dnn_b[CIRS_VTB_STATIC_MAX_DNN];
+    const float *expert_w, *expert_b; /* h_last -> experts * expert_dim (column d * experts + e) */
+    const float* gate_w[2];           /* h_last -> experts, no bias, per task                    */
+    const float* tower_w[2];          /* [expert_dim][task_dim], no bias                         */
+    const float* lin_w;               /* linear_model_task of the dim-1 task [d_in]              */
+    const float* bias[2];             /* out.<task>.bias [task_dim]                              */
+} cirs_vtb_mmoe_weights;
+
+typedef struct cirs_vtb_static_cfg {
+    int32_t n_traj;            /* 1..1048576                                                                  */
+    int32_t max_turn;          /* VirtualTB.max_turn, 1..16383                                                */
+    int32_t num_leave_compute; /* N of the exit rule, as cirs_vtb_cfg                                         */
+    int32_t reserved;          /* 0                                                                           */
+    double leave_threshold;
+    double epsilon;            /* 0..1; 0: no exploration draw is compared (evaluation.py:253)                */
+    cirs_vtb_mmoe_shape policy;
+} cirs_vtb_static_cfg;
+
+typedef struct cirs_vtb_static_out { /* rows (trajectory i, turn t) at i * max_turn + t; turns >= len[i] are not written */
+    int32_t* user;      /* [n_traj,11]   one-hot positions of the trajectory's user                                 */
+    float* state;       /* [rows,91]     the policy's input                                                         */
+    float* action;      /* [rows,27]     the action played (raw prediction or the exploration uniforms); the kernel
+                                         reads the exit rule's window back from here                               */
+    float* reward_pred; /* [rows]        the dim-1 task's output                                                    */
+    int32_t* reward;    /* [rows]        clicks 0..10                                                               */
+    uint8_t* done;      /* [rows]                                                                                   */
+    uint8_t* explore;   /* [rows]        1: the epsilon branch fired                                                */
+    void* metrics;      /* CIRS_VTB_STATIC_METRICS_BYTES: {ctr, click_loss, len_tra, R_tra} double | {clicks, turns}
+                                         int64 | len[n_traj] int32                                                  */
+} cirs_vtb_static_out;
+
+/* bytes of cirs_vtb_static_eval's workspace (per-trajectory click counts and |reward_pred - reward| sums); -1 on a bad cfg */
+int64_t cirs_vtb_static_workspace_bytes(const cirs_vtb_static_cfg* cfg);
+/* Play n_traj trajectories from the user draw to the exit: ONE vtb_static_eval_kernel launch (4 trajectories per workgroup, the
+ * turn loop inside), then a one-workgroup reduction of the metrics in a fixed order: click_loss sums fp64 in turn order inside a
+ * trajectory, the trajectories' sums in trajectory order; clicks and turns are integers.  `w`: generator and action model only
+ * (the mm_* fields are not read). */
+int cirs_vtb_static_eval(const cirs_vtb_static_cfg* cfg, const cirs_vtb_weights* w, const cirs_vtb_mmoe_weights* pw, uint64_t seed,
+                         const cirs_vtb_static_out* out, void* workspace, int64_t workspace_bytes, void* stream);
+/* the noise cirs_vtb_static_eval draws for (trajectory traj_ids[j], turn turns[j]): out [n,265] fp32 = [21 step Gumbels of the
+ * turn | z (128) | 88 user Gumbels (the trajectory's, the same at every turn) | epsilon uniform | 27 exploration uniforms] */
+int cirs_vtb_static_noise(uint64_t seed, const int32_t* traj_ids, const int32_t* turns, int32_t n, float* out, void* stream);
+
 /* ---- VirtualTaobao PPO rollout on the device (csrc/vtb_rollout.hip) -------------------------------------------------------
  * The policy side of CIRS-RL-taobao.py's per-step loop: the dense-feature state tracker (HostStateTracker: ffn_user / fnn_gate
  * input slot, positional encoding, post-norm causal TransformerEncoder, decoder) as a K/V-cached decode step, and ActorProb over
