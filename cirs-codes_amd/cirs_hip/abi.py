@@ -208,6 +208,10 @@ class MmoeTrainCfg(C.Structure):    # cirs_mmoe_train_cfg
         [(k, C.c_float) for k in ("l2_linear", "l2_all", "lr", "beta1", "beta2", "eps")]
 
 
+class MlpTrainCfg(C.Structure):     # cirs_mlp_train_cfg
+    _fields_ = [("shape", VtbMmoeShape)] + [(k, C.c_float) for k in ("l2_linear", "l2_all", "lr", "beta1", "beta2", "eps")]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -324,6 +328,11 @@ SIGNATURES = {
     "cirs_mmoe_train_epoch": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32,
                                         _P, _P, C.c_int64, _P]),
     "cirs_vtb_exposure_history": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P, _P, _P]),
+    "cirs_mlp_train_param_count": (C.c_int64, [C.POINTER(MlpTrainCfg)]),
+    "cirs_mlp_train_workspace_bytes": (C.c_int64, [C.POINTER(MlpTrainCfg), C.c_int32]),
+    "cirs_mlp_train_step": (C.c_int, [C.POINTER(MlpTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_mlp_train_epoch": (C.c_int, [C.POINTER(MlpTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, C.c_int32,
+                                       _P, _P, C.c_int64, _P]),
     "cirs_exposure_history": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_double, _P, _P]),
     "cirs_find_negative": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int64, _P, _P]),
     "cirs_select_items": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_float, _P, C.c_uint64, C.c_uint32,

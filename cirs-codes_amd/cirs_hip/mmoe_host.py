@@ -5,6 +5,9 @@ torch_train              the optimiser steps of UserModel_MMOE.fit_data (referen
                          (autograd + torch.optim.Adam) over a state_dict under the reference's names: loss_taobao, the regulariser
                          over linear_model (l2_linear) and over EVERY parameter (l2_all).  The comparison object of the device step, in
                          tests and in tools/probe_mmoe_train.py.
+mlp_torch_train          the same for the two-task build of the static baselines (reference MLP-taobao.py: 91 static-state inputs ->
+                         feat_item (27) and y (1), its own loss_taobao, MLP-taobao.py:137-155), for run-time shapes: the comparison
+                         object of csrc/mlp_train.hip, in tests and in tools/probe_mlp_train.py.
 """
 import numpy as np
 import torch
@@ -76,6 +79,96 @@ def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_lin
     for st in range(steps):
         idx = order[st * batch_size:(st + 1) * batch_size]
         loss = loss_taobao(forward(p, X[idx]), Y[idx], E[idx])
+        opt.zero_grad()
+        reg = torch.zeros((1,), dtype=dtype, device=device)
+        w = p["linear_model.weight"]
+        reg = reg + torch.sum(l2_linear * w * w)
+        for k in names:
+            reg = reg + torch.sum(l2_all * p[k] * p[k])
+        (loss + reg.squeeze()).backward()
+        opt.step()
+        losses.append([float(loss.detach()), float(reg.detach())])
+        if st in keep:
+            kept[st] = {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
+    return np.array(losses), kept, {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
+
+
+# ---- the two-task build of the static baselines (MLP-taobao.py, MLP-epsilonGreedy-taobao.py) ------------------------------------------
+MLP_TASK_DIMS = (ACTION_COLS, 1)
+
+
+def mlp_shapes(hidden, experts=N_EXPERTS, expert_dim=EXPERT_DIM):
+    """(state_dict name, shape) of UserModel_MMOE's all-dense build with the tasks feat_item (27) and y (1), in state_dict order."""
+    dims = [USER_COLS] + list(hidden)
+    out = [("linear_model.weight", (USER_COLS, 1))]
+    for l, (a, b) in enumerate(zip(dims[:-1], dims[1:])):
+        out += [(f"dnn.linears.{l}.weight", (b, a)), (f"dnn.linears.{l}.bias", (b,))]
+    out += [("mmoe_layer.expert_network.weight", (experts * expert_dim, dims[-1])), ("mmoe_layer.expert_network.bias", (experts * expert_dim,)),
+            ("mmoe_layer.gating_networks.0.weight", (experts, dims[-1])), ("mmoe_layer.gating_networks.1.weight", (experts, dims[-1])),
+            ("tower_network.0.weight", (ACTION_COLS, expert_dim)), ("tower_network.1.weight", (1, expert_dim)),
+            ("out.0.bias", (1, ACTION_COLS)), ("out.1.bias", (1, 1)), ("linear_model_task.1.weight", (USER_COLS, 1))]
+    return out
+
+
+def mlp_shape_of(sd):
+    """(hidden, experts, expert_dim) read off a state_dict of the two-task build; ValueError when it is not one."""
+    try:
+        n = len([k for k in sd if k.startswith("dnn.linears.") and k.endswith(".weight")])
+        hidden = [int(sd[f"dnn.linears.{l}.weight"].shape[0]) for l in range(n)]
+        experts = int(sd["mmoe_layer.gating_networks.0.weight"].shape[0])
+        expert_dim = int(sd["mmoe_layer.expert_network.weight"].shape[0]) // max(experts, 1)
+        want = dict(mlp_shapes(hidden, experts, expert_dim))
+    except (KeyError, IndexError, AttributeError) as exc:
+        raise ValueError(f"not the two-task UserModel_MMOE of the static baselines ({exc})") from None
+    if n < 1 or set(sd) != set(want) or any(tuple(sd[k].shape) != want[k] for k in want):
+        diff = sorted(set(sd) ^ set(want)) or sorted(k for k in want if tuple(sd[k].shape) != want[k])
+        raise ValueError(f"unexpected parameters for the two-task UserModel_MMOE of the static baselines: {diff}")
+    return hidden, experts, expert_dim
+
+
+def mlp_forward(p, x):
+    """UserModel_MMOE.forward of the two-task build over the parameter dict p (reference names) -> [n, 28] = [feat_item | y]."""
+    h = x
+    l = 0
+    while f"dnn.linears.{l}.weight" in p:
+        h = torch.relu(h @ p[f"dnn.linears.{l}.weight"].t() + p[f"dnn.linears.{l}.bias"])
+        l += 1
+    n_exp = p["mmoe_layer.gating_networks.0.weight"].shape[0]
+    experts = (h @ p["mmoe_layer.expert_network.weight"].t() + p["mmoe_layer.expert_network.bias"]).reshape(len(x), -1, n_exp)
+    outs = []
+    for t in range(2):
+        gate = (h @ p[f"mmoe_layer.gating_networks.{t}.weight"].t()).softmax(1)
+        logit = torch.bmm(experts, gate.unsqueeze(-1)).squeeze(-1) @ p[f"tower_network.{t}.weight"].t()
+        if t == 1:               # linear_model_task exists on the dimension-1 task only
+            logit = x @ p["linear_model_task.1.weight"] + logit
+        outs.append(logit + p[f"out.{t}.bias"])
+    return torch.cat(outs, -1)
+
+
+def loss_taobao_mlp(y_pred, y):
+    """loss_taobao of MLP-taobao.py:137-155: the action task is masked by the click column (rows without a click teach no action),
+    the click task is a plain mse; y = [27 item features | click]."""
+    click = y[:, -1:]
+    mse = torch.nn.functional.mse_loss
+    return mse(click * y_pred[:, :ACTION_COLS], click * y[:, :ACTION_COLS]) + mse(y_pred[:, ACTION_COLS:], y[:, ACTION_COLS:])
+
+
+def mlp_torch_train(init, x, y, batch_size, steps=None, order=None, l2_linear=1e-5, l2_all=1e-2, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                    dtype=torch.float32, device="cpu", keep=()):
+    """x [N, 91], y [N, 28] -> (losses [steps, 2] = {loss, reg}, {step index: parameters after that step (numpy) for the indices in
+    `keep`}, final parameters): torch_train for the two-task build."""
+    p = {k: torch.nn.Parameter(torch.as_tensor(np.asarray(v)).to(device, dtype).clone()) for k, v in init.items()}
+    names = list(p)
+    opt = torch.optim.Adam([p[k] for k in names], lr=lr, betas=betas, eps=eps)
+    X = torch.as_tensor(np.asarray(x)).to(device, dtype)
+    Y = torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, ACTION_COLS + 1)
+    order = torch.arange(X.shape[0], device=device) if order is None else torch.as_tensor(order).to(device)
+    n_steps = (len(order) + batch_size - 1) // batch_size
+    steps = n_steps if steps is None else min(steps, n_steps)
+    losses, kept = [], {}
+    for st in range(steps):
+        idx = order[st * batch_size:(st + 1) * batch_size]
+        loss = loss_taobao_mlp(mlp_forward(p, X[idx]), Y[idx])
         opt.zero_grad()
         reg = torch.zeros((1,), dtype=dtype, device=device)
         w = p["linear_model.weight"]

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import abi
-from .mmoe_host import ACTION_COLS, D_IN, EXPERT_DIM, N_EXPERTS, shapes
+from .mmoe_host import ACTION_COLS, D_IN, EXPERT_DIM, N_EXPERTS, USER_COLS, mlp_shape_of, mlp_shapes, shapes
 
 # (state_dict name, stored transposed) in buffer order -- must match layout() in csrc/mmoe_train.hip
 _ORDER = [("dnn.linears.1.weight", False), ("mmoe_layer.expert_network.weight", False), ("mmoe_layer.gating_networks.0.weight", False),
@@ -117,6 +117,122 @@ class MMoETrainer:
                                                   self.adam_v.data_ptr(), self.step_count, x.data_ptr(), y.data_ptr(), e.data_ptr(), x.shape[0],
                                                   order.data_ptr(), n, bs, losses.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
                   "cirs_mmoe_train_epoch")
+        self.step_count += steps
+        return losses
+
+
+class MlpTrainer:
+    """The same surface for the two-task build of the static baselines (csrc/mlp_train.hip: cirs_mlp_train_step / _epoch; reference
+    MLP-taobao.py, MLP-epsilonGreedy-taobao.py): x [n, 91] static states, y [n, 28] = [27 item features | click].  The shape is read
+    off the state_dict: whatever cirs_hip.vtb_static evaluates can be trained."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], *, l2_linear=1e-5, l2_all=1e-2, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, device="cuda"):
+        self.device = torch.device(device)
+        sd = {k: torch.as_tensor(np.asarray(v) if not isinstance(v, torch.Tensor) else v) for k, v in state_dict.items()}
+        hidden, experts, expert_dim = mlp_shape_of(sd)
+        self.hidden, self.experts, self.expert_dim = tuple(hidden), experts, expert_dim
+        hid = list(hidden[:abi.VTB_STATIC_MAX_DNN]) + [0] * max(0, abi.VTB_STATIC_MAX_DNN - len(hidden))
+        shape = abi.VtbMmoeShape(d_in=USER_COLS, n_dnn=len(hidden), hidden=(C.c_int32 * abi.VTB_STATIC_MAX_DNN)(*hid), experts=experts,
+                                 expert_dim=expert_dim, n_tasks=2, task_dim=(C.c_int32 * 2)(ACTION_COLS, 1))
+        self.cfg = abi.MlpTrainCfg(shape=shape, l2_linear=float(l2_linear), l2_all=float(l2_all), lr=float(lr), beta1=float(betas[0]),
+                                   beta2=float(betas[1]), eps=float(eps))
+        self._lib = abi.lib()
+        total = self._lib.cirs_mlp_train_param_count(C.byref(self.cfg))
+        if total <= 0:
+            msg = self._lib.cirs_last_error()
+            raise ValueError(msg.decode() if msg else "unsupported MMoE shape")
+        self._shapes = mlp_shapes(hidden, experts, expert_dim)
+        want = dict(self._shapes)
+        L = len(hidden)
+        # (state_dict name, stored transposed) in buffer order -- must match layout() in csrc/mlp_train.hip
+        order = [(f"dnn.linears.{l}.weight", False) for l in range(1, L)] + \
+                [("mmoe_layer.expert_network.weight", False), ("mmoe_layer.gating_networks.0.weight", False),
+                 ("mmoe_layer.gating_networks.1.weight", False), ("dnn.linears.0.weight", True)] + \
+                [(f"dnn.linears.{l}.bias", False) for l in range(L)] + \
+                [("mmoe_layer.expert_network.bias", False), ("tower_network.0.weight", False), ("tower_network.1.weight", False),
+                 ("out.0.bias", False), ("out.1.bias", False), ("linear_model.weight", False), ("linear_model_task.1.weight", False)]
+        self.flat = torch.zeros(total, dtype=torch.float32, device=self.device)
+        self.grads = torch.zeros_like(self.flat)
+        self.adam_m = torch.zeros_like(self.flat)
+        self.adam_v = torch.zeros_like(self.flat)
+        self._slots = {}
+        off = 0
+        for name, transposed in order:
+            shape = want[name]
+            n = int(np.prod(shape))
+            self._slots[name] = (off, n, shape, transposed)
+            src = sd[name].to(self.device, torch.float32).reshape(shape)
+            self.flat[off:off + n].copy_((src.t() if transposed else src).reshape(-1))
+            off += n
+        assert off == total and set(self._slots) == set(want)
+        self.step_count = 0
+        self._ws = None
+        self.loss = torch.zeros(2, dtype=torch.float32, device=self.device)
+
+    def _named(self, flat):
+        out = {}
+        for name, _ in self._shapes:
+            off, n, shape, transposed = self._slots[name]
+            v = flat[off:off + n]
+            out[name] = v.view(shape[1], shape[0]).t().contiguous() if transposed else v.view(shape).clone()
+        return out
+
+    def state_dict(self):
+        """The parameters under the reference's state_dict names and shapes (copies)."""
+        return self._named(self.flat)
+
+    def moments(self):
+        return self._named(self.adam_m), self._named(self.adam_v)
+
+    def gradients(self):
+        """The gradients of loss + reg of the last step, under the same names."""
+        return self._named(self.grads)
+
+    def _workspace(self, n):
+        need = self._lib.cirs_mlp_train_workspace_bytes(C.byref(self.cfg), int(n))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _cols(self, x, y):
+        x = torch.as_tensor(x).to(self.device, torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != USER_COLS:
+            raise ValueError(f"x must be [n, {USER_COLS}]")
+        y = torch.as_tensor(y).to(self.device, torch.float32).contiguous()
+        if y.dim() != 2 or tuple(y.shape) != (x.shape[0], ACTION_COLS + 1):
+            raise ValueError(f"y must be [n, {ACTION_COLS + 1}] (27 item features | click) with one row per sample")
+        return x, y
+
+    def step(self, x, y):
+        """One optimiser step on the batch x [n, 91], y [n, 28] -> the device vector {loss, reg}."""
+        x, y = self._cols(x, y)
+        if x.shape[0] == 0:
+            raise ValueError("empty batch")
+        ws = self._workspace(x.shape[0])
+        abi.check(self._lib.cirs_mlp_train_step(C.byref(self.cfg), self.flat.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+                                                self.adam_v.data_ptr(), self.step_count, x.data_ptr(), y.data_ptr(), x.shape[0],
+                                                self.loss.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()), "cirs_mlp_train_step")
+        self.step_count += 1
+        return self.loss
+
+    def epoch(self, x, y, order, batch_size):
+        """All steps of one pass over the device-resident data set in the row order `order` (int64), the last batch short as in DataLoader
+        -> device tensor [steps, 2] of per-step {loss, reg}.  Nothing is synchronised: the launches are queued and the call returns."""
+        x, y = self._cols(x, y)
+        order = torch.as_tensor(order).to(self.device, torch.int64).contiguous()
+        n, bs = int(order.numel()), int(batch_size)
+        if n == 0 or bs <= 0 or x.shape[0] == 0:
+            raise ValueError("empty data set, index array or batch size")
+        steps = (n + bs - 1) // bs
+        losses = torch.zeros((steps, 2), dtype=torch.float32, device=self.device)
+        ws = self._workspace(min(bs, n))
+        abi.check(self._lib.cirs_mlp_train_epoch(C.byref(self.cfg), self.flat.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+                                                 self.adam_v.data_ptr(), self.step_count, x.data_ptr(), y.data_ptr(), x.shape[0],
+                                                 order.data_ptr(), n, bs, losses.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()),
+                  "cirs_mlp_train_epoch")
         self.step_count += steps
         return losses
 

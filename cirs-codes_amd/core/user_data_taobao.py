@@ -50,3 +50,16 @@ def load_dataset_virtualTaobao(tau, filename=FILENAME, feature_dim=10, exposure_
     dataset = StaticDataset(x_columns, y_columns, num_workers=4)
     dataset.compile_dataset(df_x, df_y, exposure_all)
     return dataset, x_columns, y_columns
+
+
+def load_dataset_mlp_taobao(filename=FILENAME, feature_dim=10):
+    """`load_dataset_virtualTaobao` of the static baselines (reference MLP-taobao.py:51-71, the same lines in
+    MLP-epsilonGreedy-taobao.py) over the same 91 + 27 + 1 column log: x = the 91-column static state, y = [27 item features | click];
+    there is no exposure column.  -> (StaticDataset with x_numpy [n, 91] and y_numpy [n, 28], x_columns, y_columns)."""
+    df = read_log(filename)
+    df_x, df_y = df[USER_FEATURES], df[ITEM_FEATURES + REWARD_FEATURES]
+    x_columns = [DenseFeat("feat_user", 91)]
+    y_columns = [DenseFeat("feat_item", 27)] + [DenseFeat("y", 1)]
+    dataset = StaticDataset(x_columns, y_columns, num_workers=4)
+    dataset.compile_dataset(df_x, df_y)
+    return dataset, x_columns, y_columns

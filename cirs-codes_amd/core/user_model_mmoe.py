@@ -2,7 +2,9 @@
 PredictionLayer): the user model of the VirtualTaobao experiments (CIRS-UserModel-taobao.py:100-148) -- BASELINE configs[0], CPU
 plumbing.  Parameters under the reference's state_dict names; `forward` is plain torch on whatever device the module lives on (this
 is not a hot path: one 1 x 118 row per env step); `compile` / `fit_data` train on the device (cirs_hip.mmoe_train.MMoETrainer:
-cirs_mmoe_train_epoch, two launches per optimiser step, loss_taobao inside the kernel).
+cirs_mmoe_train_epoch, two launches per optimiser step, loss_taobao inside the kernel).  The two-task build of the static baselines
+(MLP-taobao.py, MLP-epsilonGreedy-taobao.py: 91 static-state inputs -> feat_item (27) and y (1)) trains the same way behind the marker
+loss_taobao_mlp (cirs_hip.mmoe_train.MlpTrainer: cirs_mlp_train_epoch); `compile_RL_test` is the reference's per-epoch evaluation hook.
 
     y_task = PredictionLayer_task( Linear_task(X)  [+ FM over the sparse embeddings, none for the all-dense Taobao features]
                                    + tower_task( MMoE_task( DNN(X) ) ) )
@@ -23,6 +25,15 @@ def loss_taobao(y_predict=None, y_true=None, exposure=None, y_index=None):
 
 
 loss_taobao.device_loss = "taobao"
+
+
+def loss_taobao_mlp(y_predict=None, y_true=None, exposure=None, y_index=None):
+    """Marker of the static baselines' loss (MLP-taobao.py:137-155), mse(click * feat_item) + mse(y) with click = y_true[:, -1]: pass it
+    to UserModel_MMOE.compile of the two-task build; the loss itself runs inside cirs_mlp_train_step."""
+    raise RuntimeError("loss_taobao_mlp is evaluated on the device by cirs_mlp_train_step; it is a marker for UserModel_MMOE.compile")
+
+
+loss_taobao_mlp.device_loss = "taobao_mlp"
 
 
 class _Dense(nn.Module):
@@ -98,13 +109,21 @@ class UserModel_MMOE(UserModel):
         self._l2 = (1e-5, float(l2_reg_dnn))     # (linear_model: the base class's l2_reg_linear default, every parameter)
         self.optim = None
         self._trainer = None
+        self._kind = None                        # which device step compile() selected: "taobao" (one task) or "taobao_mlp" (two tasks)
+        self.RL_eval_fun = None
 
     # ---- training (reference core/user_model.py:74-170 with loss_taobao) ------------------------------------------------------
     def compile(self, optimizer, loss_dict=None, metrics=None, metric_fun=None, loss_func=None):
         if not (optimizer == "adam" or isinstance(optimizer, torch.optim.Adam)):
             raise ValueError("the device step implements torch.optim.Adam: pass optimizer=\"adam\" or a torch.optim.Adam instance")
+        if getattr(loss_func, "device_loss", None) == "taobao_mlp":
+            return self._compile_mlp(optimizer, loss_func, metrics, metric_fun)
         if getattr(loss_func, "device_loss", None) != "taobao":
             raise ValueError("pass core.user_model_mmoe.loss_taobao: the loss runs inside cirs_mmoe_train_step")
+        if len(self.tower_network) != 1:
+            raise ValueError("loss_taobao trains the build with one regression task; the two-task build of the static baselines "
+                             "(feat_item, y) compiles with core.user_model_mmoe.loss_taobao_mlp")
+        self._kind = "taobao"
         shape = [tuple(l.weight.shape) for l in self.dnn.linears]
         if len(shape) != 2 or shape[0][1] != 118 or any(s[0] not in (64, 128) for s in shape) or len(self.tower_network) != 1 or \
                 self.mmoe_layer.num_experts != 4 or self.mmoe_layer.out_dim != 8 or self.tower_network[0].out_features != 1:
@@ -117,37 +136,75 @@ class UserModel_MMOE(UserModel):
         self._adam = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"])
         self._trainer = None
 
+    def _compile_mlp(self, optimizer, loss_func, metrics, metric_fun):
+        """The static baselines' build (MLP-taobao.py:117-124): accepted where the device evaluation accepts it."""
+        from cirs_hip.vtb_static import policy_shape
+        if len(self.tower_network) != 2:
+            raise ValueError("loss_taobao_mlp trains the two-task build of the static baselines (feat_item, y); the build with one "
+                             "regression task compiles with core.user_model_mmoe.loss_taobao")
+        policy_shape(self)               # ValueError for a shape cirs_vtb_static_eval / cirs_mlp_train_step do not run
+        self._kind = "taobao_mlp"
+        self.metrics_names = ["loss"]
+        self.loss_func, self.metric_fun, self.metrics = loss_func, metric_fun, metrics
+        self.optim = "adam"
+        g = optimizer.param_groups[0] if isinstance(optimizer, torch.optim.Adam) else dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
+        self._adam = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"])
+        self._trainer = None
+
+    def compile_RL_test(self, RL_eval_fun):
+        """reference core/user_model.py:71-72: fit_data evaluates fn(self.eval()) before training and after every epoch."""
+        self.RL_eval_fun = RL_eval_fun
+
+    def _publish(self):
+        """The trained parameters into the module, under its state_dict names."""
+        with torch.no_grad():
+            mine = dict(self.named_parameters())
+            for k, v in self._trainer.state_dict().items():
+                mine[k].copy_(v.reshape(mine[k].shape).to(mine[k].device))
+
     def fit_data(self, dataset_train, dataset_val=None, batch_size=256, epochs=1, verbose=1, initial_epoch=0, callbacks=None, shuffle=True):
-        """One pass per epoch over (x, y, exposure) minibatches, the last one short; an epoch is one cirs_mmoe_train_epoch call on the
-        device-resident data set.  Returns [{"loss": summed total loss / sample count}, ...] like UserModel.fit_data."""
-        from cirs_hip.mmoe_train import MMoETrainer
+        """One pass per epoch over (x, y, exposure) minibatches, the last one short; an epoch is one cirs_mmoe_train_epoch (two-task
+        build: cirs_mlp_train_epoch, y [n, 28], no exposure) call on the device-resident data set.  With compile_RL_test set, the
+        evaluation's results join the epoch's logs.  Returns [{"loss": summed total loss / sample count, ...}, ...] like UserModel.fit_data."""
+        from cirs_hip.mmoe_train import MlpTrainer, MMoETrainer
         assert self.optim is not None, "call compile() first"
+        mlp = self._kind == "taobao_mlp"
         if self._trainer is None:
-            self._trainer = MMoETrainer(self.state_dict(), l2_linear=self._l2[0], l2_all=self._l2[1], **self._adam)
+            self._trainer = (MlpTrainer if mlp else MMoETrainer)(self.state_dict(), l2_linear=self._l2[0], l2_all=self._l2[1], **self._adam)
         tr = self._trainer
         x = torch.as_tensor(dataset_train.x_numpy).to(tr.device, torch.float32).contiguous()
-        y = torch.as_tensor(dataset_train.y_numpy).to(tr.device, torch.float32).reshape(-1).contiguous()
-        score = torch.as_tensor(dataset_train.score).to(tr.device, torch.float32).reshape(-1).contiguous()
+        if mlp:      # y = [27 item features | click]; the score column is not used (MLP-taobao.py:137-155)
+            y = torch.as_tensor(dataset_train.y_numpy).to(tr.device, torch.float32).reshape(x.shape[0], -1).contiguous()
+            cols = (x, y)
+        else:
+            y = torch.as_tensor(dataset_train.y_numpy).to(tr.device, torch.float32).reshape(-1).contiguous()
+            cols = (x, y, torch.as_tensor(dataset_train.score).to(tr.device, torch.float32).reshape(-1).contiguous())
         n_all = x.shape[0]
         callbacks = callbacks or []
         for cb in callbacks:
             cb.on_train_begin()
+        if self.RL_eval_fun:             # core/user_model.py:129-135: the untrained model's evaluation, reported as epoch -1
+            logs = {}
+            logs.update(self.RL_eval_fun(self.eval()))
+            for cb in callbacks:
+                cb.on_epoch_end(-1, logs)
         history = []
         for epoch in range(initial_epoch, epochs):
             for cb in callbacks:
                 cb.on_epoch_begin(epoch)
             order = torch.randperm(n_all, device=tr.device) if shuffle else torch.arange(n_all, device=tr.device)
-            losses = tr.epoch(x, y, score, order, batch_size)
+            losses = tr.epoch(*cols, order, batch_size)
             logs = {"loss": float(losses.sum(dtype=torch.float64)) / n_all}       # total_loss_epoch / sample_num (core/user_model.py:205)
+            if self.RL_eval_fun:         # core/user_model.py:215-219
+                self._publish()
+                for name, result in self.RL_eval_fun(self.eval()).items():
+                    logs[name] = result
             history.append(logs)
             for cb in callbacks:
                 cb.on_epoch_end(epoch, logs)
         for cb in callbacks:
             cb.on_train_end()
-        with torch.no_grad():      # publish the trained parameters under the module's state_dict names
-            mine = dict(self.named_parameters())
-            for k, v in tr.state_dict().items():
-                mine[k].copy_(v.reshape(mine[k].shape).to(mine[k].device))
+        self._publish()
         return history
 
     def load_state_dict(self, state_dict, strict=True):

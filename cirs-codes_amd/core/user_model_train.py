@@ -89,3 +89,48 @@ def train_user_model_taobao(dataset_path, save_root=".", callbacks=None, exposur
         pickle.dump(params, fh)
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, paths.state_dict)
     return SimpleNamespace(model=model, history=history, paths=paths, dataset=dataset)
+
+
+MLP_TAOBAO_DEFAULTS = dict(env="VirtualTB-v0", model_name="MLP", message="MLP", feature_dim=4, dnn=(256, 256), batch_size=100, epoch=100,
+                           leave_threshold=1.0, num_leave_compute=5, max_turn=50, seed=2022, num_trajectory=100)
+
+
+def train_mlp_taobao(dataset_path, save_root=".", callbacks=None, epsilon=0, shuffle=True, vtb_env=None, **overrides):
+    """The static baselines' run (MLP-taobao.py:74-132, `main`; epsilon > 0: MLP-epsilonGreedy-taobao.py) step for step, training and
+    the per-epoch evaluation on the device: create the directories, a VirtualTB in static-state mode, the 91 + 27 + 1 column log ->
+    data set, the two-task UserModel_MMOE, compile("adam", loss_taobao_mlp), compile_RL_test(test_taobao on the device), fit_data with
+    LoggerCallback_Update.  `vtb_env`: a VirtualTB to use instead of a fresh one (it is put into static-state mode).
+    Returns SimpleNamespace(model, history, env, dataset, logger_path)."""
+    import collections
+    import datetime
+    import functools
+    import time
+    from core.user_data_taobao import load_dataset_mlp_taobao
+    from core.user_model_mmoe import UserModel_MMOE, loss_taobao_mlp
+    from deepctr_torch.inputs import DenseFeat
+    from evaluation import test_taobao
+    from util.utils import LoggerCallback_Update, create_dir
+    a = SimpleNamespace(**{**MLP_TAOBAO_DEFAULTS, **overrides})
+    # 1. Create dirs
+    model_dir = os.path.join(save_root, "saved_models", a.env, a.model_name)
+    create_dir([os.path.join(save_root, "saved_models"), os.path.join(save_root, "saved_models", a.env), model_dir, os.path.join(model_dir, "logs")])
+    nowtime = datetime.datetime.fromtimestamp(time.time()).strftime("%Y_%m_%d-%H_%M_%S")
+    logger_path = os.path.join(model_dir, "logs", "[{}]_{}.log".format(a.message, nowtime))
+    # 2. Prepare Envs
+    env = vtb_env
+    if env is None:
+        from environments.VirtualTaobao.virtualTB.envs.virtualTB import VirtualTB
+        env = VirtualTB(num_leave_compute=a.num_leave_compute, leave_threshold=a.leave_threshold, max_turn=a.max_turn)
+    env.set_state_mode(True)             # return the states as user initial profile vectors
+    # 3. Prepare dataset
+    dataset, x_columns, y_columns = load_dataset_mlp_taobao(dataset_path, feature_dim=a.feature_dim)
+    # 4. Setup model
+    tasks = collections.OrderedDict({feat.name: "regression" for feat in y_columns})
+    task_logit_dim = {feat.name: feat.dimension if isinstance(feat, DenseFeat) else feat.embedding_dim for feat in y_columns}
+    model = UserModel_MMOE(x_columns, y_columns, len(tasks), tasks, task_logit_dim, dnn_hidden_units=tuple(a.dnn), seed=a.seed, device="cpu")
+    model.compile(optimizer="adam", loss_func=loss_taobao_mlp, metrics=None)
+    model.compile_RL_test(functools.partial(test_taobao, env=env, epsilon=epsilon, device="cuda", num_trajectory=a.num_trajectory))
+    # 5. Learn model
+    history = model.fit_data(dataset, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [LoggerCallback_Update(logger_path)],
+                             shuffle=shuffle)
+    return SimpleNamespace(model=model, history=history, env=env, dataset=dataset, logger_path=logger_path)

@@ -1065,6 +1065,47 @@ int cirs_mmoe_train_epoch(const cirs_mmoe_train_cfg* cfg, float* params, float* 
 int cirs_vtb_exposure_history(const int32_t* timestamp_host, const double* action, int64_t n_rows, double tau,
                               int64_t* start_scratch, double* exposure_out, void* stream);
 
+/* ---- VirtualTaobao static baselines: training (csrc/mlp_train.hip) ----------------------------------------------------------
+ * One optimiser step of UserModel_MMOE.fit_data's inner loop (reference core/user_model.py:150-170, core/user_model_mmoe.py:144-233,
+ * loss_taobao of MLP-taobao.py:137-155; the same lines serve MLP-epsilonGreedy-taobao.py) for the all-dense build with the two
+ * regression tasks feat_item (27) and y (1) -- the model cirs_vtb_static_eval plays, any shape cirs_vtb_mmoe_shape describes:
+ *   h = relu(W_l h + b_l), l < n_dnn; experts = (We h + be) as [expert_dim, experts]; gate_t = softmax(Wg_t h)
+ *   pred[:, :27] = tower_0 (experts @ gate_0) + out_0;  pred[:, 27] = (x . w_lin_task + tower_1 (experts @ gate_1)) + out_1
+ *   click = y[:, 27];  loss = mean over n * 27 of (click (pred[:, :27] - y[:, :27]))^2 + mean over n of (pred[:, 27] - click)^2
+ *   reg  = l2_linear |linear_model.weight|^2 + l2_all sum over EVERY parameter of |p|^2  (biases, both gates and the unused
+ *          duplicate linear_model.weight included)
+ *   (loss + reg).backward(); torch.optim.Adam step (no weight decay, no amsgrad).
+ * Shapes: d_in 91, 1..3 hidden layers of 1..256, experts * expert_dim <= 64, tasks (27, 1); anything else: CIRS_E_UNSUPPORTED.
+ * Parameters, gradients and both Adam moments are flat fp32 buffers of cirs_mlp_train_param_count(cfg) floats (16-byte aligned) in
+ * the order (H_l = hidden[l], L = n_dnn, E = experts, D = expert_dim; torch layouts unless said otherwise)
+ *     dnn.linears.l.weight [H_l,H_(l-1)] for l = 1 .. L-1
+ *   | expert_network.weight [E D,H_(L-1)] | gating_networks.0.weight [E,H_(L-1)] | gating_networks.1.weight [E,H_(L-1)]
+ *   | dnn.linears.0.weight TRANSPOSED [91,H_0] | dnn.linears.l.bias [H_l] for l = 0 .. L-1 | expert_network.bias [E D]
+ *   | tower_network.0.weight [27,D] | tower_network.1.weight [1,D] | out.0.bias [27] | out.1.bias [1]
+ *   | linear_model.weight [91] | linear_model_task.1.weight [91].
+ * Two launches per step, every sum in a fixed order (no float atomics): two runs from one state give identical bits. */
+typedef struct cirs_mlp_train_cfg {
+    cirs_vtb_mmoe_shape shape;
+    float l2_linear, l2_all;      /* the two regularisation lists of the reference (linear_model, all parameters)  */
+    float lr, beta1, beta2, eps;  /* torch.optim.Adam                                                              */
+} cirs_mlp_train_cfg;
+int64_t cirs_mlp_train_param_count(const cirs_mlp_train_cfg* cfg);               /* 0 for an unsupported shape */
+int64_t cirs_mlp_train_workspace_bytes(const cirs_mlp_train_cfg* cfg, int32_t n); /* n = rows of the largest batch */
+/* one step on the batch x [n,91], y [n,28] = [27 item features | click] (fp32, device); step_before = optimiser steps taken so
+ * far; loss_out[2] = {loss, reg} (device). */
+int cirs_mlp_train_step(const cirs_mlp_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                        int64_t step_before, const float* x, const float* y, int32_t n, float* loss_out, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+/* all steps of one pass: the data set x [n_rows,91], y [n_rows,28] stays on the device, batch b is the rows
+ * order[b * batch_size .. min(n_order, (b + 1) * batch_size)) (int64, device, every entry in [0, n_rows); the last batch may be
+ * short, as in DataLoader).  losses_out [ceil(n_order / batch_size)][2] = per-step {loss, reg} (device).  The launches are queued
+ * back to back: no host synchronisation between steps.  Bit-identical to the same steps issued through cirs_mlp_train_step.
+ * workspace: cirs_mlp_train_workspace_bytes(cfg, min(batch_size, n_order)). */
+int cirs_mlp_train_epoch(const cirs_mlp_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                         int64_t step_before, const float* x, const float* y, int64_t n_rows, const int64_t* order,
+                         int64_t n_order, int32_t batch_size, float* losses_out, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif
