@@ -63,22 +63,19 @@ def loss_taobao(y_pred, y, exposure):
     return (((1 / (1 + exposure) * y_pred - y) ** 2) * (y + 1)).mean()
 
 
-def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_linear=1e-5, l2_all=1e-2, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
-                dtype=torch.float32, device="cpu", keep=()):
-    """-> (losses [steps, 2] = {loss, reg}, {step index: parameters after that step (numpy) for the indices in `keep`}, final parameters)."""
+def _torch_train(forward_loss, init, cols, batch_size, steps, order, l2_linear, l2_all, lr, betas, eps, dtype, device, keep):
+    """The optimiser loop of torch_train / mlp_torch_train: forward_loss(p, *batch columns) -> the data loss; cols: the columns as 2-d
+    tensors, x first."""
     p = {k: torch.nn.Parameter(torch.as_tensor(np.asarray(v)).to(device, dtype).clone()) for k, v in init.items()}
     names = list(p)      # state_dict order = the reference's parameter order
     opt = torch.optim.Adam([p[k] for k in names], lr=lr, betas=betas, eps=eps)
-    X = torch.as_tensor(np.asarray(x)).to(device, dtype)
-    Y = torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, 1)
-    E = torch.as_tensor(np.asarray(exposure)).to(device, dtype).reshape(-1, 1)
-    order = torch.arange(X.shape[0], device=device) if order is None else torch.as_tensor(order).to(device)
+    order = torch.arange(cols[0].shape[0], device=device) if order is None else torch.as_tensor(order).to(device)
     n_steps = (len(order) + batch_size - 1) // batch_size
     steps = n_steps if steps is None else min(steps, n_steps)
     losses, kept = [], {}
     for st in range(steps):
         idx = order[st * batch_size:(st + 1) * batch_size]
-        loss = loss_taobao(forward(p, X[idx]), Y[idx], E[idx])
+        loss = forward_loss(p, *(c[idx] for c in cols))
         opt.zero_grad()
         reg = torch.zeros((1,), dtype=dtype, device=device)
         w = p["linear_model.weight"]
@@ -91,6 +88,14 @@ def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_lin
         if st in keep:
             kept[st] = {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
     return np.array(losses), kept, {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
+
+
+def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_linear=1e-5, l2_all=1e-2, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                dtype=torch.float32, device="cpu", keep=()):
+    """-> (losses [steps, 2] = {loss, reg}, {step index: parameters after that step (numpy) for the indices in `keep`}, final parameters)."""
+    cols = [torch.as_tensor(np.asarray(x)).to(device, dtype)] + [torch.as_tensor(np.asarray(c)).to(device, dtype).reshape(-1, 1) for c in (y, exposure)]
+    return _torch_train(lambda p, xb, yb, eb: loss_taobao(forward(p, xb), yb, eb), init, cols, batch_size, steps, order, l2_linear, l2_all, lr,
+                        betas, eps, dtype, device, keep)
 
 
 # ---- the two-task build of the static baselines (MLP-taobao.py, MLP-epsilonGreedy-taobao.py) ------------------------------------------
@@ -157,27 +162,6 @@ def mlp_torch_train(init, x, y, batch_size, steps=None, order=None, l2_linear=1e
                     dtype=torch.float32, device="cpu", keep=()):
     """x [N, 91], y [N, 28] -> (losses [steps, 2] = {loss, reg}, {step index: parameters after that step (numpy) for the indices in
     `keep`}, final parameters): torch_train for the two-task build."""
-    p = {k: torch.nn.Parameter(torch.as_tensor(np.asarray(v)).to(device, dtype).clone()) for k, v in init.items()}
-    names = list(p)
-    opt = torch.optim.Adam([p[k] for k in names], lr=lr, betas=betas, eps=eps)
-    X = torch.as_tensor(np.asarray(x)).to(device, dtype)
-    Y = torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, ACTION_COLS + 1)
-    order = torch.arange(X.shape[0], device=device) if order is None else torch.as_tensor(order).to(device)
-    n_steps = (len(order) + batch_size - 1) // batch_size
-    steps = n_steps if steps is None else min(steps, n_steps)
-    losses, kept = [], {}
-    for st in range(steps):
-        idx = order[st * batch_size:(st + 1) * batch_size]
-        loss = loss_taobao_mlp(mlp_forward(p, X[idx]), Y[idx])
-        opt.zero_grad()
-        reg = torch.zeros((1,), dtype=dtype, device=device)
-        w = p["linear_model.weight"]
-        reg = reg + torch.sum(l2_linear * w * w)
-        for k in names:
-            reg = reg + torch.sum(l2_all * p[k] * p[k])
-        (loss + reg.squeeze()).backward()
-        opt.step()
-        losses.append([float(loss.detach()), float(reg.detach())])
-        if st in keep:
-            kept[st] = {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
-    return np.array(losses), kept, {k: v.detach().cpu().numpy().copy() for k, v in p.items()}
+    cols = [torch.as_tensor(np.asarray(x)).to(device, dtype), torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, ACTION_COLS + 1)]
+    return _torch_train(lambda p, xb, yb: loss_taobao_mlp(mlp_forward(p, xb), yb), init, cols, batch_size, steps, order, l2_linear, l2_all, lr,
+                        betas, eps, dtype, device, keep)

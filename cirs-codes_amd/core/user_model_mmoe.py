@@ -123,12 +123,16 @@ class UserModel_MMOE(UserModel):
         if len(self.tower_network) != 1:
             raise ValueError("loss_taobao trains the build with one regression task; the two-task build of the static baselines "
                              "(feat_item, y) compiles with core.user_model_mmoe.loss_taobao_mlp")
-        self._kind = "taobao"
         shape = [tuple(l.weight.shape) for l in self.dnn.linears]
         if len(shape) != 2 or shape[0][1] != 118 or any(s[0] not in (64, 128) for s in shape) or len(self.tower_network) != 1 or \
                 self.mmoe_layer.num_experts != 4 or self.mmoe_layer.out_dim != 8 or self.tower_network[0].out_features != 1:
             raise ValueError("the device step trains the VirtualTaobao build only: 118 dense inputs, two hidden layers with widths from "
                              "{64, 128}, 4 experts of dim 8, one regression task of logit dim 1")
+        self._compiled("taobao", optimizer, loss_func, metrics, metric_fun)
+
+    def _compiled(self, kind, optimizer, loss_func, metrics, metric_fun):
+        """The end of compile() for either build, after its refusals: `kind` selects the device step."""
+        self._kind = kind
         self.metrics_names = ["loss"]
         self.loss_func, self.metric_fun, self.metrics = loss_func, metric_fun, metrics
         self.optim = "adam"
@@ -143,13 +147,7 @@ class UserModel_MMOE(UserModel):
             raise ValueError("loss_taobao_mlp trains the two-task build of the static baselines (feat_item, y); the build with one "
                              "regression task compiles with core.user_model_mmoe.loss_taobao")
         policy_shape(self)               # ValueError for a shape cirs_vtb_static_eval / cirs_mlp_train_step do not run
-        self._kind = "taobao_mlp"
-        self.metrics_names = ["loss"]
-        self.loss_func, self.metric_fun, self.metrics = loss_func, metric_fun, metrics
-        self.optim = "adam"
-        g = optimizer.param_groups[0] if isinstance(optimizer, torch.optim.Adam) else dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8)
-        self._adam = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"])
-        self._trainer = None
+        self._compiled("taobao_mlp", optimizer, loss_func, metrics, metric_fun)
 
     def compile_RL_test(self, RL_eval_fun):
         """reference core/user_model.py:71-72: fit_data evaluates fn(self.eval()) before training and after every epoch."""

@@ -13,24 +13,23 @@
 //                          weight loads are predicated on the matrix's own bounds.  Soft-max, mix and the loss are per-row VALU code.
 //                          Per-row operands of the weight gradients go to the workspace, the tile's two loss sums (fp64) to a partial.
 //                          Eight more workgroups compute the regulariser of the CURRENT parameters as 64 fixed chunks (fp64).
-//   mlp_grad_adam_kernel   the scheme of mmoe_grad_adam_kernel over a run-time job table: one workgroup per 32 x 32 tile of a weight
-//                          matrix, dW = dZ^T A on v_mfma_f32_32x32x2_f32, four row slabs added as (s0 + s1) + (s2 + s3), bias
-//                          gradients as column sums, then g += 2 l2 p and torch.optim.Adam on the tile's own parameters.  The last
-//                          workgroup decays the unused duplicate `linear_model.weight` and sums the loss / regulariser partials.
+//   grad_adam_kernel       (train_step.h, shared with mmoe_train.hip) dW = dZ^T A of the run-time job table built in launch_step on
+//                          the matrix cores, bias gradients, g += 2 l2 p and torch.optim.Adam; its last workgroup decays the unused
+//                          duplicate `linear_model.weight` and sums the two loss partials (A / 27 n + B / n) and the regulariser's.
 // Every sum has a fixed order and there are no float atomics: two runs from one state give identical bits, and an epoch (the same two
 // launches per step, queued back to back without host synchronisation) equals the step-by-step loop bit for bit.
 #include "common.h"
+#include "train_step.h"
 
 namespace cirs {
 namespace mlt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kIn = CIRS_VTB_STATIC_STATE_DIM, kAct = 27, kOut = 28, kMaxL = CIRS_VTB_STATIC_MAX_DNN, kMaxH = 256, kMaxED = 64;
 constexpr int kTile = 16, kThreads = 256;
+static_assert(kThreads == tstep::kThreads, "reg_chunks runs in the row kernel's workgroups");
 constexpr int kLdX = 100, kLdH = kMaxH + 4, kLdE = 3 * kMaxED + 4, kLdM = 2 * kMaxED + 4, kLdP = 36;   // LDS row strides (floats, multiples of 4)
-constexpr int kRegChunks = 64, kRegBlocks = 8;
 
 struct Layout {  // offsets (floats) into the flat parameter / gradient / moment buffers
     int w[kMaxL], weg, b[kMaxL], be, wt, ob, lin_model, lin_task, total;
@@ -54,7 +53,7 @@ static Layout layout(const cirs_vtb_mmoe_shape& s) {
 
 struct Rows {  // per-row outputs of mlp_rows_kernel
     float *X, *H[kMaxL], *DZ[kMaxL], *DEG, *MIX, *DP;   // [n,91] [n,H_l] [n,H_l] [n,ED+2E] [n,2D] [n,28]
-    double *loss_part, *reg_part;                       // [tiles][2] [kRegChunks]
+    double *loss_part, *reg_part;                       // [tiles][2] [tstep::kRegChunks]
 };
 
 struct RowsArgs {
@@ -167,19 +166,6 @@ __device__ __forceinline__ void tile_mm(const float* A, int lda, int K, int O, L
     __syncthreads();
 }
 
-// sum of 256 per-thread doubles in a fixed tree; result valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 struct alignas(16) RowsSmem {
     float x[kTile * kLdX];
     float h[kMaxL][kTile * kLdH];               // layer outputs; overwritten in place by the pre-activation gradients on the way back
@@ -198,20 +184,8 @@ __global__ __launch_bounds__(kThreads) void mlp_rows_kernel(RowsArgs a) {
     const int tid = threadIdx.x;
     const float* __restrict__ P = a.P;
     const Layout& L = a.L;
-    if ((int)blockIdx.x >= a.n_tiles) {   // regulariser of the current parameters: chunk c covers [c * cs, (c + 1) * cs)
-        double* red = reinterpret_cast<double*>(smem_raw);
-        const int cs = (L.total + kRegChunks - 1) / kRegChunks;
-        for (int c = blockIdx.x - a.n_tiles; c < kRegChunks; c += kRegBlocks) {
-            const int lo = c * cs, hi = min(L.total, lo + cs);
-            double acc = 0.0;
-            for (int i = lo + tid; i < hi; i += kThreads) {
-                const double p = (double)P[i];
-                const double coef = (double)a.l2_all + (i >= L.lin_model && i < L.lin_task ? (double)a.l2_linear : 0.0);   // linear_model.weight is in both lists
-                acc = fma(coef * p, p, acc);
-            }
-            const double t = block_sum_f64(acc, red);
-            if (tid == 0) a.out.reg_part[c] = t;
-        }
+    if ((int)blockIdx.x >= a.n_tiles) {
+        tstep::reg_chunks(P, L.total, L.lin_model, L.lin_task, a.l2_linear, a.l2_all, a.n_tiles, reinterpret_cast<double*>(smem_raw), a.out.reg_part);
         return;
     }
     const cirs_vtb_mmoe_shape& sh = a.sh;
@@ -364,108 +338,6 @@ __global__ __launch_bounds__(kThreads) void mlp_rows_kernel(RowsArgs a) {
     }
 }
 
-// one weight-gradient problem: G[i][j] = sum_r Lm[r][i] Rm[r][j], i < O, j < K; parameter of (i, j) at p_off + i * si + j * sj;
-// b_off >= 0: parameter b_off + i, i < b_n, takes sum_r Lm[r][i] (bias)
-struct Job {
-    const float *Lm, *Rm;
-    int ldl, ldr, O, K, p_off, si, sj, b_off, b_n, tile0, k_tiles;
-};
-constexpr int kJobs = kMaxL + 4;   // hidden layers, experts | gates, two towers, linear_model_task
-struct Jobs {
-    Job j[kJobs];
-    int n_jobs, n_tiles;
-};
-struct AdamArgs {
-    float beta1, beta2, eps, step_size, bc2s, l2_linear, l2_all;
-};
-
-__device__ __forceinline__ void adam_one(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int i,
-                                         float data_grad, float c2, const AdamArgs& a) {
-    const float pi = p[i];
-    const float gi = __builtin_fmaf(c2, pi, data_grad);   // d/dp of l2 * p^2 joins the data gradient
-    const float mi = m[i] + (1.0f - a.beta1) * (gi - m[i]);
-    const float vi = v[i] * a.beta2 + (1.0f - a.beta2) * gi * gi;
-    g[i] = gi; m[i] = mi; v[i] = vi;
-    p[i] = pi - a.step_size * (mi / (sqrtf(vi) / a.bc2s + a.eps));
-}
-
-__global__ __launch_bounds__(kThreads) void mlp_grad_adam_kernel(float* __restrict__ P, float* __restrict__ G, float* __restrict__ M,
-                                                                 float* __restrict__ V, Jobs jobs, int n, AdamArgs a, int lin_model, int n_row_tiles,
-                                                                 const double* __restrict__ loss_part, const double* __restrict__ reg_part,
-                                                                 float* __restrict__ loss_out) {
-    __shared__ float part[3][17][64];
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x == jobs.n_tiles) {
-        // linear_model.weight: decayed by both regulariser lists, no data gradient (UserModel_MMOE's forward never reads it)
-        if (tid < kIn) {
-            const float pi = P[lin_model + tid];
-            adam_one(P, G, M, V, lin_model + tid, 2.0f * a.l2_linear * pi, 2.0f * a.l2_all, a);
-        }
-        if (tid == 128) {
-            double ta = 0.0, tb = 0.0;
-            for (int q = 0; q < n_row_tiles; ++q) { ta += loss_part[2 * q]; tb += loss_part[2 * q + 1]; }
-            loss_out[0] = (float)(ta / ((double)n * kAct) + tb / (double)n);
-        }
-        if (tid == 192) {
-            double t = 0.0;
-            for (int q = 0; q < kRegChunks; ++q) t += reg_part[q];
-            loss_out[1] = (float)t;
-        }
-        return;
-    }
-    int ji = 0;
-#pragma unroll
-    for (int q = 1; q < kJobs; ++q)
-        if (q < jobs.n_jobs && (int)blockIdx.x >= jobs.j[q].tile0) ji = q;
-    const Job& J = jobs.j[ji];
-    const int t = blockIdx.x - J.tile0;
-    const int o0 = (t / J.k_tiles) * 32, k0 = (t % J.k_tiles) * 32;
-    const int wave = tid >> 6, lane = tid & 63, hi = lane >> 5, lo = lane & 31;
-    const int rps = (((n + 3) / 4) + 1) & ~1;     // rows per slab (even): wave w owns rows [w * rps, min(n, (w + 1) * rps))
-    const int r_beg = wave * rps, r_end = min(n, r_beg + rps);
-    const int o = o0 + lo, k = k0 + lo;
-    const bool o_ok = o < J.O, k_ok = k < J.K;
-    f32x16 acc;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc[s] = 0.f;
-    float bsum = 0.f;
-    for (int r = r_beg; r < r_end; r += 32) {   // 16 MFMA steps (32 rows) per batch: the loads go out first, row order unchanged
-        float av[16], bv[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int rr = r + 2 * j + hi;
-            const bool r_ok = rr < r_end;
-            av[j] = (r_ok && o_ok) ? J.Lm[(size_t)rr * J.ldl + o] : 0.f;
-            bv[j] = (r_ok && k_ok) ? J.Rm[(size_t)rr * J.ldr + k] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            bsum += av[j];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-        }
-    }
-    bsum += __shfl_xor(bsum, 32, CIRS_WAVE);
-    if (wave > 0) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) part[wave - 1][s][lane] = acc[s];
-        part[wave - 1][16][lane] = bsum;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc[s] = (acc[s] + part[0][s][lane]) + (part[1][s][lane] + part[2][s][lane]);
-    bsum = (bsum + part[0][16][lane]) + (part[1][16][lane] + part[2][16][lane]);
-    const float c2 = 2.0f * a.l2_all;
-    if (k_ok) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int oo = o0 + (s & 3) + 8 * (s >> 2) + 4 * hi;
-            if (oo < J.O) adam_one(P, G, M, V, J.p_off + oo * J.si + k * J.sj, acc[s], c2, a);
-        }
-    }
-    if (k0 == 0 && J.b_off >= 0 && hi == 0 && o < J.b_n) adam_one(P, G, M, V, J.b_off + o, bsum, c2, a);
-}
-
 static int check_cfg(const cirs_mlp_train_cfg* cfg) {
     CIRS_REQUIRE(cfg, "null cfg");
     const cirs_vtb_mmoe_shape& s = cfg->shape;
@@ -486,7 +358,7 @@ static size_t ws_floats(const cirs_vtb_mmoe_shape& s, long n) {
     size_t t = pad4((size_t)n * kIn);
     for (int l = 0; l < s.n_dnn; ++l) t += 2 * pad4((size_t)n * s.hidden[l]);
     t += pad4((size_t)n * (s.experts * s.expert_dim + 2 * s.experts)) + pad4((size_t)n * 2 * s.expert_dim) + pad4((size_t)n * kOut);
-    return t + pad4(4 * (size_t)tiles) + 2 * kRegChunks + 64;
+    return t + pad4(4 * (size_t)tiles) + 2 * tstep::kRegChunks + 64;
 }
 
 // the two launches of one step on batch rows r0 .. r0 + n - 1 of the index array (or of the data when idx is null)
@@ -510,36 +382,23 @@ static int launch_step(const cirs_mlp_train_cfg* cfg, float* params, float* grad
     o.X = take((size_t)n * kIn);
     for (int l = 0; l < nL; ++l) { o.H[l] = take((size_t)n * sh.hidden[l]); o.DZ[l] = take((size_t)n * sh.hidden[l]); }
     o.DEG = take((size_t)n * EG); o.MIX = take((size_t)n * 2 * D); o.DP = take((size_t)n * kOut);
-    o.loss_part = (double*)take(4 * (size_t)tiles); o.reg_part = (double*)take(2 * kRegChunks);
+    o.loss_part = (double*)take(4 * (size_t)tiles); o.reg_part = (double*)take(2 * tstep::kRegChunks);
     ra.P = params; ra.sh = sh; ra.L = L; ra.x = x; ra.y = y; ra.idx = idx; ra.r0 = r0; ra.N = N; ra.n = n; ra.n_tiles = tiles;
     ra.l2_linear = cfg->l2_linear; ra.l2_all = cfg->l2_all;
-    hipLaunchKernelGGL(mlp_rows_kernel, dim3(tiles + kRegBlocks), dim3(kThreads), sizeof(RowsSmem), s, ra);
+    hipLaunchKernelGGL(mlp_rows_kernel, dim3(tiles + tstep::kRegBlocks), dim3(kThreads), sizeof(RowsSmem), s, ra);
     CIRS_CHECK_LAUNCH("mlp_rows_kernel");
-    Jobs jobs{};
-    int t0 = 0, q = 0;
-    auto job = [&](const float* Lm, int ldl, int O, const float* Rm, int ldr, int K, int p_off, int si, int sj, int b_off, int b_n) {
-        Job& J = jobs.j[q++];
-        J.Lm = Lm; J.ldl = ldl; J.O = O; J.Rm = Rm; J.ldr = ldr; J.K = K; J.p_off = p_off; J.si = si; J.sj = sj; J.b_off = b_off; J.b_n = b_n;
-        J.tile0 = t0; J.k_tiles = (K + 31) / 32;
-        t0 += ((O + 31) / 32) * J.k_tiles;
-    };
+    tstep::Jobs jobs{};
     const int H0 = sh.hidden[0];
-    job(o.DZ[0], H0, H0, o.X, kIn, kIn, L.w[0], 1, H0, L.b[0], H0);          // layer 0 is stored transposed: (o, k) at k * H_0 + o
-    for (int l = 1; l < nL; ++l) job(o.DZ[l], sh.hidden[l], sh.hidden[l], o.H[l - 1], sh.hidden[l - 1], sh.hidden[l - 1], L.w[l], sh.hidden[l - 1], 1, L.b[l], sh.hidden[l]);
-    job(o.DEG, EG, EG, o.H[nL - 1], HL, HL, L.weg, HL, 1, L.be, ED);         // experts | gate 0 | gate 1; only the experts have a bias
-    job(o.DP, kOut, kAct, o.MIX, 2 * D, D, L.wt, D, 1, L.ob, kAct);          // tower 0 and out.0.bias
-    job(o.DP + kAct, kOut, 1, o.MIX + D, 2 * D, D, L.wt + kAct * D, D, 1, L.ob + kAct, 1);   // tower 1 and out.1.bias
-    job(o.DP + kAct, kOut, 1, o.X, kIn, kIn, L.lin_task, 0, 1, -1, 0);       // linear_model_task of the dim-1 task
-    jobs.n_jobs = q; jobs.n_tiles = t0;
-    const double t = (double)(step_before + 1);
-    AdamArgs a;
-    a.beta1 = cfg->beta1; a.beta2 = cfg->beta2; a.eps = cfg->eps; a.l2_linear = cfg->l2_linear; a.l2_all = cfg->l2_all;
-    a.step_size = (float)((double)cfg->lr / (1.0 - pow((double)cfg->beta1, t)));
-    a.bc2s = (float)sqrt(1.0 - pow((double)cfg->beta2, t));
-    hipLaunchKernelGGL(mlp_grad_adam_kernel, dim3(jobs.n_tiles + 1), dim3(kThreads), 0, s, params, grads, adam_m, adam_v, jobs, n, a, L.lin_model, tiles,
-                       (const double*)o.loss_part, (const double*)o.reg_part, loss_out);
-    CIRS_CHECK_LAUNCH("mlp_grad_adam_kernel");
-    return CIRS_OK;
+    tstep::add_job(jobs, o.DZ[0], H0, H0, o.X, kIn, kIn, L.w[0], 1, H0, L.b[0], H0);          // layer 0 is stored transposed: (o, k) at k * H_0 + o
+    for (int l = 1; l < nL; ++l)
+        tstep::add_job(jobs, o.DZ[l], sh.hidden[l], sh.hidden[l], o.H[l - 1], sh.hidden[l - 1], sh.hidden[l - 1], L.w[l], sh.hidden[l - 1], 1, L.b[l], sh.hidden[l]);
+    tstep::add_job(jobs, o.DEG, EG, EG, o.H[nL - 1], HL, HL, L.weg, HL, 1, L.be, ED);         // experts | gate 0 | gate 1; only the experts have a bias
+    tstep::add_job(jobs, o.DP, kOut, kAct, o.MIX, 2 * D, D, L.wt, D, 1, L.ob, kAct);          // tower 0 and out.0.bias
+    tstep::add_job(jobs, o.DP + kAct, kOut, 1, o.MIX + D, 2 * D, D, L.wt + kAct * D, D, 1, L.ob + kAct, 1);   // tower 1 and out.1.bias
+    tstep::add_job(jobs, o.DP + kAct, kOut, 1, o.X, kIn, kIn, L.lin_task, 0, 1, -1, 0);       // linear_model_task of the dim-1 task
+    const tstep::Tail tail{L.lin_model, kIn, tiles, 2, {(double)n * kAct, (double)n}, o.loss_part, o.reg_part, loss_out};
+    return tstep::launch_grad_adam(params, grads, adam_m, adam_v, jobs, n,
+                                   tstep::adam_args(cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->l2_linear, cfg->l2_all, step_before), tail, s);
 }
 
 }  // namespace mlt
@@ -560,13 +419,11 @@ extern "C" int cirs_mlp_train_step(const cirs_mlp_train_cfg* cfg, float* params,
                                    int64_t workspace_bytes, void* stream) {
     using namespace cirs;
     if (int rc = mlt::check_cfg(cfg)) return rc;
-    CIRS_REQUIRE(params && grads && adam_m && adam_v && loss_out && workspace, "null argument");
-    CIRS_REQUIRE(x && y, "null batch column");
-    CIRS_REQUIRE(n >= 1, "empty batch");
-    CIRS_REQUIRE(step_before >= 0, "negative step count");
-    CIRS_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "params and workspace must be 16-byte aligned");
-    CIRS_REQUIRE(workspace_bytes >= cirs_mlp_train_workspace_bytes(cfg, n), "workspace too small");
-    return mlt::launch_step(cfg, params, grads, adam_m, adam_v, step_before, x, y, nullptr, 0, n, n, loss_out, workspace, (hipStream_t)stream);
+    return tstep::run_steps(params, grads, adam_m, adam_v, loss_out, workspace, x && y, "null batch column", n >= 1, "empty batch", step_before,
+                            workspace_bytes, cirs_mlp_train_workspace_bytes(cfg, n), n, n, [&](int64_t, int64_t, int nb) {
+                                return mlt::launch_step(cfg, params, grads, adam_m, adam_v, step_before, x, y, nullptr, 0, nb, nb, loss_out, workspace,
+                                                        (hipStream_t)stream);
+                            });
 }
 
 extern "C" int cirs_mlp_train_epoch(const cirs_mlp_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
@@ -575,19 +432,11 @@ extern "C" int cirs_mlp_train_epoch(const cirs_mlp_train_cfg* cfg, float* params
                                     void* stream) {
     using namespace cirs;
     if (int rc = mlt::check_cfg(cfg)) return rc;
-    CIRS_REQUIRE(params && grads && adam_m && adam_v && losses_out && workspace, "null argument");
-    CIRS_REQUIRE(x && y && order, "null data column or index array");
-    CIRS_REQUIRE(n_rows >= 1 && n_order >= 1 && batch_size >= 1, "empty data set, index array or batch");
-    CIRS_REQUIRE(step_before >= 0, "negative step count");
-    CIRS_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "params and workspace must be 16-byte aligned");
     const int64_t bmax = batch_size < n_order ? batch_size : n_order;
-    CIRS_REQUIRE(workspace_bytes >= cirs_mlp_train_workspace_bytes(cfg, (int32_t)bmax), "workspace too small");
-    int64_t st = 0;
-    for (int64_t r0 = 0; r0 < n_order; r0 += batch_size, ++st) {   // queued back to back: the host never waits for the device
-        const int n = (int)(n_order - r0 < batch_size ? n_order - r0 : batch_size);
-        if (int rc = mlt::launch_step(cfg, params, grads, adam_m, adam_v, step_before + st, x, y, order, r0, n_rows, n, losses_out + 2 * st,
-                                      workspace, (hipStream_t)stream))
-            return rc;
-    }
-    return CIRS_OK;
+    return tstep::run_steps(params, grads, adam_m, adam_v, losses_out, workspace, x && y && order, "null data column or index array",
+                            n_rows >= 1 && n_order >= 1 && batch_size >= 1, "empty data set, index array or batch", step_before, workspace_bytes,
+                            cirs_mlp_train_workspace_bytes(cfg, (int32_t)bmax), n_order, batch_size, [&](int64_t st, int64_t r0, int nb) {
+                                return mlt::launch_step(cfg, params, grads, adam_m, adam_v, step_before + st, x, y, order, r0, n_rows, nb,
+                                                        losses_out + 2 * st, workspace, (hipStream_t)stream);
+                            });
 }

@@ -10,26 +10,22 @@
 //                          operands of the weight gradients (x, h1, h2, mixture, dz1, dz2, d experts | d gate, dy) go to the
 //                          workspace; the tile's loss sum (fp64) to a partial.  Eight more workgroups compute the
 //                          regulariser of the CURRENT parameters as 64 fixed chunks (fp64 partials).
-//   mmoe_grad_adam_kernel  one workgroup per 32 x 32 tile of a weight matrix: dW = dZ^T A over the batch rows on the fp32 matrix
-//                          cores (v_mfma_f32_32x32x2_f32, operand layout of small_gemm.h), the rows split into four contiguous
-//                          slabs (one wavefront each) whose accumulators are added as (s0 + s1) + (s2 + s3); bias gradients as
-//                          column sums in the same waves; then g += 2 l2 p and torch.optim.Adam on the tile's own parameters.
-//                          The last workgroup decays the unused duplicate `linear_model.weight` (no data gradient) and
-//                          sums the loss / regulariser partials in index order into loss_out.
+//   grad_adam_kernel       (train_step.h, shared with mlp_train.hip) dW = dZ^T A of the six jobs listed in launch_step on the matrix
+//                          cores, bias gradients, g += 2 l2 p and torch.optim.Adam; its last workgroup decays the unused duplicate
+//                          `linear_model.weight` and sums the loss / regulariser partials in index order into loss_out.
 // Every sum has a fixed order and there are no float atomics: two runs from one state give identical bits, and an epoch
 // (the same two launches per step, queued back to back without any host synchronisation) equals the step-by-step loop bit for bit.
 #include <vector>
 
 #include "common.h"
+#include "train_step.h"
 
 namespace cirs {
 namespace mmt {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kIn = 118, kExperts = 4, kExpertDim = 8, kEx = kExperts * kExpertDim, kEg = kEx + kExperts;
 constexpr int kTile = 16, kThreads = 256, kLd = 132, kLdE = 40;
-constexpr int kRegChunks = 64, kRegBlocks = 8;
+static_assert(kThreads == tstep::kThreads, "reg_chunks runs in the row kernel's workgroups");
 
 struct Layout {  // offsets (floats) into the flat parameter / gradient / moment buffers
     int w2, we, wg, w1t, b1, b2, be, wt, lin_model, lin_task, out_bias, total;
@@ -52,7 +48,7 @@ __host__ __device__ inline Layout layout(int H1, int H2) {   // the matrices rea
 
 struct Rows {  // per-row outputs of mmoe_rows_kernel
     float *X, *H1, *H2, *M, *DZ1, *DZ2, *DEG, *DY;  // [n,118] [n,H1] [n,H2] [n,8] [n,H1] [n,H2] [n,36] [n]
-    double *loss_part, *reg_part;                   // [tiles] [kRegChunks]
+    double *loss_part, *reg_part;                   // [tiles] [tstep::kRegChunks]
 };
 
 // Y[s][o] = relu(b[o] + sum_k X[s][k] Wt[k][o]): weights stored [K][O], lanes o read consecutive dwords
@@ -130,19 +126,6 @@ __device__ __forceinline__ void bwd_n(const float* __restrict__ W, const float* 
     __syncthreads();
 }
 
-// sum of 256 per-thread doubles in a fixed tree; result valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 struct alignas(16) RowsSmem {
     float x[kTile * kLd], h1[kTile * kLd], h2[kTile * kLd], dz2[kTile * kLd], dz1[kTile * kLd];
     float eg[kTile * kLdE], deg[kTile * kLdE];   // experts (column d * 4 + e) | gate logits;  their gradients
@@ -158,19 +141,8 @@ __global__ __launch_bounds__(kThreads) void mmoe_rows_kernel(const float* __rest
     __shared__ double red[kThreads];
     const Layout L = layout(H1, H2);
     const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= n_tiles) {   // regulariser of the current parameters: chunk c covers [c * cs, (c + 1) * cs)
-        const int cs = (L.total + kRegChunks - 1) / kRegChunks;
-        for (int c = blockIdx.x - n_tiles; c < kRegChunks; c += kRegBlocks) {
-            const int lo = c * cs, hi = min(L.total, lo + cs);
-            double acc = 0.0;
-            for (int i = lo + tid; i < hi; i += kThreads) {
-                const double p = (double)P[i];
-                const double coef = (double)l2_all + (i >= L.lin_model && i < L.lin_task ? (double)l2_linear : 0.0);   // linear_model.weight is in both lists
-                acc = fma(coef * p, p, acc);
-            }
-            const double t = block_sum_f64(acc, red);
-            if (tid == 0) out.reg_part[c] = t;
-        }
+    if ((int)blockIdx.x >= n_tiles) {
+        tstep::reg_chunks(P, L.total, L.lin_model, L.lin_task, l2_linear, l2_all, n_tiles, red, out.reg_part);
         return;
     }
     const int row0 = blockIdx.x * kTile;
@@ -297,108 +269,6 @@ __global__ __launch_bounds__(kThreads) void mmoe_rows_kernel(const float* __rest
     }
 }
 
-// one weight-gradient problem: G[i][j] = sum_r Lm[r][i] Rm[r][j], i < O, j < K; parameter of (i, j) at p_off + i * si + j * sj;
-// b_off >= 0: parameter b_off + i takes sum_r Lm[r][i] (bias)
-struct Job {
-    const float *Lm, *Rm;
-    int ldl, ldr, O, K, p_off, si, sj, b_off, tile0, k_tiles;
-};
-constexpr int kJobs = 6;
-struct Jobs {
-    Job j[kJobs];
-    int n_tiles;
-};
-struct AdamArgs {
-    float beta1, beta2, eps, step_size, bc2s, l2_linear, l2_all;
-};
-
-__device__ __forceinline__ void adam_one(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int i,
-                                         float data_grad, float c2, const AdamArgs& a) {
-    const float pi = p[i];
-    const float gi = __builtin_fmaf(c2, pi, data_grad);   // d/dp of l2 * p^2 joins the data gradient
-    const float mi = m[i] + (1.0f - a.beta1) * (gi - m[i]);
-    const float vi = v[i] * a.beta2 + (1.0f - a.beta2) * gi * gi;
-    g[i] = gi; m[i] = mi; v[i] = vi;
-    p[i] = pi - a.step_size * (mi / (sqrtf(vi) / a.bc2s + a.eps));
-}
-
-__global__ __launch_bounds__(kThreads) void mmoe_grad_adam_kernel(float* __restrict__ P, float* __restrict__ G, float* __restrict__ M,
-                                                                  float* __restrict__ V, Jobs jobs, int n, AdamArgs a, int lin_model, int n_row_tiles,
-                                                                  const double* __restrict__ loss_part, const double* __restrict__ reg_part,
-                                                                  float* __restrict__ loss_out) {
-    __shared__ float part[3][17][64];
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x == jobs.n_tiles) {
-        // linear_model.weight: decayed by both regulariser lists, no data gradient (UserModel_MMOE's forward never reads it)
-        if (tid < kIn) {
-            const float pi = P[lin_model + tid];
-            adam_one(P, G, M, V, lin_model + tid, 2.0f * a.l2_linear * pi, 2.0f * a.l2_all, a);
-        }
-        if (tid == 64) {
-            double t = 0.0;
-            for (int q = 0; q < n_row_tiles; ++q) t += loss_part[q];
-            loss_out[0] = (float)(t / (double)n);
-        }
-        if (tid == 128) {
-            double t = 0.0;
-            for (int q = 0; q < kRegChunks; ++q) t += reg_part[q];
-            loss_out[1] = (float)t;
-        }
-        return;
-    }
-    int ji = 0;
-#pragma unroll
-    for (int q = 1; q < kJobs; ++q)
-        if ((int)blockIdx.x >= jobs.j[q].tile0) ji = q;
-    const Job& J = jobs.j[ji];
-    const int t = blockIdx.x - J.tile0;
-    const int o0 = (t / J.k_tiles) * 32, k0 = (t % J.k_tiles) * 32;
-    const int wave = tid >> 6, lane = tid & 63, hi = lane >> 5, lo = lane & 31;
-    const int rps = (((n + 3) / 4) + 1) & ~1;     // rows per slab (even): wave w owns rows [w * rps, min(n, (w + 1) * rps))
-    const int r_beg = wave * rps, r_end = min(n, r_beg + rps);
-    const int o = o0 + lo, k = k0 + lo;
-    const bool o_ok = o < J.O, k_ok = k < J.K;
-    f32x16 acc;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc[s] = 0.f;
-    float bsum = 0.f;
-    for (int r = r_beg; r < r_end; r += 32) {   // 16 MFMA steps (32 rows) per batch: the loads go out first, row order unchanged
-        float av[16], bv[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const int rr = r + 2 * j + hi;
-            const bool r_ok = rr < r_end;
-            av[j] = (r_ok && o_ok) ? J.Lm[(size_t)rr * J.ldl + o] : 0.f;
-            bv[j] = (r_ok && k_ok) ? J.Rm[(size_t)rr * J.ldr + k] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            bsum += av[j];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-        }
-    }
-    bsum += __shfl_xor(bsum, 32, CIRS_WAVE);
-    if (wave > 0) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) part[wave - 1][s][lane] = acc[s];
-        part[wave - 1][16][lane] = bsum;
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) acc[s] = (acc[s] + part[0][s][lane]) + (part[1][s][lane] + part[2][s][lane]);
-    bsum = (bsum + part[0][16][lane]) + (part[1][16][lane] + part[2][16][lane]);
-    const float c2 = 2.0f * a.l2_all;
-    if (k_ok) {
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int oo = o0 + (s & 3) + 8 * (s >> 2) + 4 * hi;
-            if (oo < J.O) adam_one(P, G, M, V, J.p_off + oo * J.si + k * J.sj, acc[s], c2, a);
-        }
-    }
-    if (k0 == 0 && J.b_off >= 0 && hi == 0 && o_ok) adam_one(P, G, M, V, J.b_off + o, bsum, c2, a);
-}
-
 // compute_exposure_effect_virtualTaobao: one wavefront per row, lanes stride the session's earlier rows
 __global__ __launch_bounds__(256) void vtb_exposure_kernel(const int64_t* __restrict__ start, const double* __restrict__ action, long n_rows,
                                                            double tau, double* __restrict__ out) {
@@ -437,7 +307,7 @@ static size_t ws_floats(const cirs_mmoe_train_cfg* cfg, long n) {
     auto pad = [](size_t c) { return (c + 3) & ~(size_t)3; };
     const long tiles = (n + kTile - 1) / kTile;
     return pad((size_t)n * kIn) + 2 * pad((size_t)n * cfg->h1) + 2 * pad((size_t)n * cfg->h2) + pad((size_t)n * kExpertDim) + pad((size_t)n * kEg) +
-           pad((size_t)n) + 2 * pad((size_t)tiles) + 2 * kRegChunks + 64;
+           pad((size_t)n) + 2 * pad((size_t)tiles) + 2 * tstep::kRegChunks + 64;
 }
 
 // the two launches of one step on batch rows r0 .. r0 + n - 1 of the index array (or of the data when idx is null)
@@ -452,34 +322,20 @@ static int launch_step(const cirs_mmoe_train_cfg* cfg, float* params, float* gra
     Rows o;
     o.X = take((size_t)n * kIn); o.H1 = take((size_t)n * H1); o.DZ1 = take((size_t)n * H1); o.H2 = take((size_t)n * H2); o.DZ2 = take((size_t)n * H2);
     o.M = take((size_t)n * kExpertDim); o.DEG = take((size_t)n * kEg); o.DY = take(n);
-    o.loss_part = (double*)take(2 * (size_t)tiles); o.reg_part = (double*)take(2 * kRegChunks);
-    hipLaunchKernelGGL(mmoe_rows_kernel, dim3(tiles + kRegBlocks), dim3(kThreads), 0, s, (const float*)params, H1, H2, x, y, exposure, idx, r0, N, n,
+    o.loss_part = (double*)take(2 * (size_t)tiles); o.reg_part = (double*)take(2 * tstep::kRegChunks);
+    hipLaunchKernelGGL(mmoe_rows_kernel, dim3(tiles + tstep::kRegBlocks), dim3(kThreads), 0, s, (const float*)params, H1, H2, x, y, exposure, idx, r0, N, n,
                        tiles, cfg->l2_linear, cfg->l2_all, o);
     CIRS_CHECK_LAUNCH("mmoe_rows_kernel");
-    Jobs jobs;
-    int t0 = 0;
-    auto job = [&](int q, const float* Lm, int ldl, int O, const float* Rm, int ldr, int K, int p_off, int si, int sj, int b_off) {
-        Job& J = jobs.j[q];
-        J.Lm = Lm; J.ldl = ldl; J.O = O; J.Rm = Rm; J.ldr = ldr; J.K = K; J.p_off = p_off; J.si = si; J.sj = sj; J.b_off = b_off;
-        J.tile0 = t0; J.k_tiles = (K + 31) / 32;
-        t0 += ((O + 31) / 32) * J.k_tiles;
-    };
-    job(0, o.DZ1, H1, H1, o.X, kIn, kIn, L.w1t, 1, H1, L.b1);          // w1 is stored transposed: (o, k) at k * H1 + o
-    job(1, o.DZ2, H2, H2, o.H1, H1, H1, L.w2, H1, 1, L.b2);
-    job(2, o.DEG, kEg, kEx, o.H2, H2, H2, L.we, H2, 1, L.be);
-    job(3, o.DEG + kEx, kEg, kExperts, o.H2, H2, H2, L.wg, H2, 1, -1);
-    job(4, o.DY, 1, 1, o.X, kIn, kIn, L.lin_task, 0, 1, L.out_bias);
-    job(5, o.DY, 1, 1, o.M, kExpertDim, kExpertDim, L.wt, 0, 1, -1);
-    jobs.n_tiles = t0;
-    const double t = (double)(step_before + 1);
-    AdamArgs a;
-    a.beta1 = cfg->beta1; a.beta2 = cfg->beta2; a.eps = cfg->eps; a.l2_linear = cfg->l2_linear; a.l2_all = cfg->l2_all;
-    a.step_size = (float)((double)cfg->lr / (1.0 - pow((double)cfg->beta1, t)));
-    a.bc2s = (float)sqrt(1.0 - pow((double)cfg->beta2, t));
-    hipLaunchKernelGGL(mmoe_grad_adam_kernel, dim3(jobs.n_tiles + 1), dim3(kThreads), 0, s, params, grads, adam_m, adam_v, jobs, n, a, L.lin_model, tiles,
-                       (const double*)o.loss_part, (const double*)o.reg_part, loss_out);
-    CIRS_CHECK_LAUNCH("mmoe_grad_adam_kernel");
-    return CIRS_OK;
+    tstep::Jobs jobs{};   // a job with a bias passes b_n = O
+    tstep::add_job(jobs, o.DZ1, H1, H1, o.X, kIn, kIn, L.w1t, 1, H1, L.b1, H1);          // w1 is stored transposed: (o, k) at k * H1 + o
+    tstep::add_job(jobs, o.DZ2, H2, H2, o.H1, H1, H1, L.w2, H1, 1, L.b2, H2);
+    tstep::add_job(jobs, o.DEG, kEg, kEx, o.H2, H2, H2, L.we, H2, 1, L.be, kEx);
+    tstep::add_job(jobs, o.DEG + kEx, kEg, kExperts, o.H2, H2, H2, L.wg, H2, 1, -1, 0);
+    tstep::add_job(jobs, o.DY, 1, 1, o.X, kIn, kIn, L.lin_task, 0, 1, L.out_bias, 1);
+    tstep::add_job(jobs, o.DY, 1, 1, o.M, kExpertDim, kExpertDim, L.wt, 0, 1, -1, 0);
+    const tstep::Tail tail{L.lin_model, kIn, tiles, 1, {(double)n, 0.0}, o.loss_part, o.reg_part, loss_out};
+    return tstep::launch_grad_adam(params, grads, adam_m, adam_v, jobs, n,
+                                   tstep::adam_args(cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->l2_linear, cfg->l2_all, step_before), tail, s);
 }
 
 }  // namespace mmt
@@ -500,14 +356,11 @@ extern "C" int cirs_mmoe_train_step(const cirs_mmoe_train_cfg* cfg, float* param
                                     void* workspace, int64_t workspace_bytes, void* stream) {
     using namespace cirs;
     if (int rc = mmt::check_cfg(cfg)) return rc;
-    CIRS_REQUIRE(params && grads && adam_m && adam_v && loss_out && workspace, "null argument");
-    CIRS_REQUIRE(x && y && exposure, "null batch column");
-    CIRS_REQUIRE(n >= 1, "empty batch");
-    CIRS_REQUIRE(step_before >= 0, "negative step count");
-    CIRS_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "params and workspace must be 16-byte aligned");
-    CIRS_REQUIRE(workspace_bytes >= cirs_mmoe_train_workspace_bytes(cfg, n), "workspace too small");
-    return mmt::launch_step(cfg, params, grads, adam_m, adam_v, step_before, x, y, exposure, nullptr, 0, n, n, loss_out, workspace,
-                            (hipStream_t)stream);
+    return tstep::run_steps(params, grads, adam_m, adam_v, loss_out, workspace, x && y && exposure, "null batch column", n >= 1, "empty batch",
+                            step_before, workspace_bytes, cirs_mmoe_train_workspace_bytes(cfg, n), n, n, [&](int64_t, int64_t, int nb) {
+                                return mmt::launch_step(cfg, params, grads, adam_m, adam_v, step_before, x, y, exposure, nullptr, 0, nb, nb, loss_out,
+                                                        workspace, (hipStream_t)stream);
+                            });
 }
 
 extern "C" int cirs_mmoe_train_epoch(const cirs_mmoe_train_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
@@ -516,21 +369,13 @@ extern "C" int cirs_mmoe_train_epoch(const cirs_mmoe_train_cfg* cfg, float* para
                                      int64_t workspace_bytes, void* stream) {
     using namespace cirs;
     if (int rc = mmt::check_cfg(cfg)) return rc;
-    CIRS_REQUIRE(params && grads && adam_m && adam_v && losses_out && workspace, "null argument");
-    CIRS_REQUIRE(x && y && exposure && order, "null data column or index array");
-    CIRS_REQUIRE(n_rows >= 1 && n_order >= 1 && batch_size >= 1, "empty data set, index array or batch");
-    CIRS_REQUIRE(step_before >= 0, "negative step count");
-    CIRS_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)workspace & 15) == 0, "params and workspace must be 16-byte aligned");
     const int64_t bmax = batch_size < n_order ? batch_size : n_order;
-    CIRS_REQUIRE(workspace_bytes >= cirs_mmoe_train_workspace_bytes(cfg, (int32_t)bmax), "workspace too small");
-    int64_t st = 0;
-    for (int64_t r0 = 0; r0 < n_order; r0 += batch_size, ++st) {   // queued back to back: the host never waits for the device
-        const int n = (int)(n_order - r0 < batch_size ? n_order - r0 : batch_size);
-        if (int rc = mmt::launch_step(cfg, params, grads, adam_m, adam_v, step_before + st, x, y, exposure, order, r0, n_rows, n,
-                                      losses_out + 2 * st, workspace, (hipStream_t)stream))
-            return rc;
-    }
-    return CIRS_OK;
+    return tstep::run_steps(params, grads, adam_m, adam_v, losses_out, workspace, x && y && exposure && order, "null data column or index array",
+                            n_rows >= 1 && n_order >= 1 && batch_size >= 1, "empty data set, index array or batch", step_before, workspace_bytes,
+                            cirs_mmoe_train_workspace_bytes(cfg, (int32_t)bmax), n_order, batch_size, [&](int64_t st, int64_t r0, int nb) {
+                                return mmt::launch_step(cfg, params, grads, adam_m, adam_v, step_before + st, x, y, exposure, order, r0, n_rows, nb,
+                                                        losses_out + 2 * st, workspace, (hipStream_t)stream);
+                            });
 }
 
 extern "C" int cirs_vtb_exposure_history(const int32_t* timestamp_host, const double* action, int64_t n_rows, double tau,

@@ -3,6 +3,7 @@ UserModel_MMOE.fit_data, against THE SAME STEP IN PLAIN TORCH (cirs_hip.mmoe_hos
 and cirs_vtb_exposure_history against the numpy loop.  Warm-up, median of repeats, device events around the epoch call.
 
     python tools/probe_mmoe_train.py                  -> one JSON line
+    python tools/probe_mmoe_train.py --mode device    cirs_mmoe_train_epoch alone (epoch_ms_per_step per shape and batch), for A/B runs
     python tools/probe_mmoe_train.py --kernels-only   a few epochs and one exposure call, for a kernel trace
                                                       (rocprofv3 --kernel-trace --stats -- python tools/probe_mmoe_train.py --kernels-only)"""
 import json
@@ -23,6 +24,7 @@ from cirs_hip.mmoe_train import MMoETrainer, vtb_exposure_history
 
 N = 16384
 KERNELS_ONLY = "--kernels-only" in sys.argv
+DEVICE_ONLY = sys.argv[1:] == ["--mode", "device"]
 
 
 def epoch_ms(dnn, bs, repeats=7):
@@ -108,12 +110,18 @@ def main():
             if KERNELS_ONLY:
                 continue
             r = dict(epoch_ms_per_step=ms, epoch_rows_per_s=bs / ms * 1e3)
+            if DEVICE_ONLY:
+                out[key] = r
+                continue
             f = fit_ms(dnn, bs)
             r.update(fit_data_ms_per_step=f, fit_data_rows_per_s=bs / f * 1e3)
             tg = torch_ms(dnn, bs, "cuda", 40)
             tc = torch_ms(dnn, bs, "cpu", 20)
             r.update(torch_gpu_ms_per_step=tg, torch_cpu16_ms_per_step=tc, speedup_vs_torch_gpu=tg / ms, speedup_vs_torch_cpu16=tc / ms)
             out[key] = r
+    if DEVICE_ONLY:
+        print(json.dumps(out))
+        return
     e = exposure(1000000)
     if not KERNELS_ONLY:
         out["exposure"] = e
