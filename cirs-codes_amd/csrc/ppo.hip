@@ -235,6 +235,14 @@ constexpr float kScWa = 256.f, kScH2 = 64.f;
 #define hmfma_pair mfma_f16x3_pair
 constexpr float kScZ = kScWa * kScH2, kScZi = 1.0f / kScZ;      // scale of the logits accumulators (bias pre-scaled at staging) and its inverse
 constexpr int kPlaneTileU4 = 1536;  // uint4 per item tile of the fp16 planes of Wa (wa_planes_kernel)
+// Logit slab: head_stats_kernel leaves the 32 x 32 logits of every (item tile, row tile) for head_bwd_fused_kernel, which then forms neither the
+// R-plane operands nor the 24 MFMAs of the tile a second time.  Tile (ti, tr) is 4 KB at index ti * (n_pad / 32) + tr -- ABSOLUTE tile numbers: the two
+// kernels chunk the catalogue differently -- laid out [q = 0..3][lane] float4 = accumulator registers 4 q .. 4 q + 3 of the lane, the register layout both
+// kernels share: a wave-wide store / load instruction covers 1 KB of consecutive memory, the 4 row tiles of a workgroup 16 KB.  The value is the
+// accumulator sum acc + (acc1 + acc2) BEFORE the kScZi scaling: the bits the backward formed itself.  C3 at 1024 rows: 44 MB per step, written and read
+// back one launch later (beyond the L2, well inside the 256 MB of MALL).
+constexpr int kZTileF4 = 256;       // float4 per (item tile, row tile)
+__host__ inline size_t zslab_floats(int n_pad, int I) { return (size_t)cdiv(I, kTileN) * (n_pad / kTileM) * (kZTileF4 * 4); }
 struct MbView {  // contiguous minibatch arrays carved from the workspace (n_pad rows)
     float *obs, *adv, *ret, *v_s, *logp_old;  // gathered
     int32_t* act;
@@ -255,6 +263,7 @@ struct MbView {  // contiguous minibatch arrays carved from the workspace (n_pad
     uint4 *h2z, *h2b;                         // fp16 planes of H2 in the head kernels' register order (written by trunk_adv_kernel):
                                               // [32-row tile][12][lane] uint4, unit q of a lane = its q-th operand register quad
     int *sync;                                // [kSyncInts] arrival flags (see kSyncInts)
+    float4 *zslab;                            // logits of head_stats_kernel handed to the head backward (see kZTileF4)
     void* head_ws;                            // workspace of the head kernel (h2 copy + partials)
 };
 
@@ -327,6 +336,7 @@ __host__ inline size_t mb_ws_floats(int n_pad, int I, int S) {
     f += dwp_floats(n_pad, S);                         // dW row slabs (one per 32 rows: trunk_bwd_kernel; one per 8 rows in flat order: trunk_rows_kernel)
     f += (size_t)cdiv(I, kTileN) * kPlaneTileU4 * 4;   // wa_planes
     f += 2 * (size_t)n_pad * 96;                       // h2z, h2b: 24 uint4 per row each
+    f += zslab_floats(n_pad, I);                       // zslab
     f += (size_t)n_pad * kH + 4 * nch * (size_t)n_pad; // head workspace
     return f;
 }
@@ -352,6 +362,7 @@ __host__ inline MbView carve(void* ws, int n_pad, int I, int S) {
     v.dwp = take(dwp_floats(n_pad, S));
     v.wa_planes = (uint4*)take((size_t)cdiv(I, kTileN) * kPlaneTileU4 * 4);
     v.h2z = (uint4*)take((size_t)n_pad * 96); v.h2b = (uint4*)take((size_t)n_pad * 96);
+    v.zslab = (float4*)take(zslab_floats(n_pad, I));
     v.head_ws = (void*)p;
     return v;
 }
@@ -708,10 +719,15 @@ __device__ unsigned long long g_head_prof[64];
 #define CIRS_TSTAMP(B, K) do { } while (0)
 #define CIRS_SSTAMP(K) do { } while (0)
 #endif
+// kZout: the accumulator sums of every tile go to the logit slab (kZTileF4) for head_bwd_fused_kernel<.., kZin = true>.  EVERY row tile below n_pad
+// is then written (today's callers pass n_pad = n_pad_of(mb), where that is every tile anyway), so the backward, which walks all of them, never
+// reads a tile nobody wrote; rows at or beyond mb inside a tile carry the logits of an all-zero H2 row (finite).
+template <bool kZout>
 __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n_pad, int tiles_per_chunk,
                                                             const uint4* __restrict__ planes, const float* __restrict__ ba,
                                                             const uint4* __restrict__ h2z, ActorPartialView pv,
-                                                            const int32_t* __restrict__ act_rows, float* __restrict__ za_out) {
+                                                            const int32_t* __restrict__ act_rows, float* __restrict__ za_out,
+                                                            float4* __restrict__ zslab) {
     __shared__ __attribute__((aligned(16))) unsigned char sW[2][3 * kRPlaneB];
     __shared__ __attribute__((aligned(16))) float sB[2][kTileN];   // 16-byte aligned: the accumulator init reads 4 consecutive biases as one ds_read_b128
     const int tid = threadIdx.x;
@@ -721,7 +737,7 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
     const int row0 = (blockIdx.y * 4 + wv) * kTileM;
     const int chunk = blockIdx.x;
     const int jr = row0 + lo;
-    const bool wave_ok = row0 < n_pad && row0 < mb;   // some row of this tile belongs to the minibatch
+    const bool wave_ok = row0 < n_pad && (kZout || row0 < mb);   // some row of this tile belongs to the minibatch (kZout: see above)
     const bool active = jr < mb;
     HPl hz[4];  // B operand: this lane's row of H2, element j of k-step s = column 16 s + 8 hi + j
     {   // pre-split by trunk_adv_kernel in exactly this order: 12 coalesced 16-byte loads per lane, no LDS, no splits
@@ -780,7 +796,14 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
             hmfma_split2(za[0], hz[0], za[1], hz[1], acc, accs, acct);
             hmfma_split2(za[2], hz[2], za[3], hz[3], acc, accs, acct);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = (acc[r] + (accs[r] + acct[r])) * kScZi;
+            for (int r = 0; r < 16; ++r) acc[r] = acc[r] + (accs[r] + acct[r]);
+            if (kZout) {      // four 1 KB stores per wave, issued before the statistics below (nothing waits for them)
+                float4* zp = zslab + ((size_t)(tile0 / kTileN) * (n_pad / kTileM) + (row0 / kTileM)) * kZTileF4 + lane;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) zp[q * 64] = float4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] *= kScZi;
             if (it == 2) CIRS_SSTAMP(45);
             {
                 const int arel = act_r - tile0;
@@ -868,15 +891,20 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
 // workgroup for its own rows, the workgroups of chunk 0 store what later kernels read) instead of a launch of their own between the two head
 // kernels: a 6.5 us launch on the critical path of every minibatch step becomes ~1.5 us of prologue.  The item-sharded learner keeps the
 // merge kernel (its statistics cross the ranks first).
+// kZin: the tile's logits come from the slab head_stats_kernel<true> left one launch earlier (kZTileF4: the same accumulator bits, so both forms give the
+// same results) instead of a second pass over the R planes: no `za` / bias reads, no logits MFMAs (24 of the tile's 72), half the plane staging (the C planes
+// only), no `hz` operand.  The tile's 16 values per lane are requested one tile ahead.  The previous tile's dWa sum, which hides behind the logits MFMAs in
+// the recompute form, sits behind the dH2 MFMAs here.  The recompute form stays for same-box A/B runs and the bit-identity test (CIRS_PPO_HEAD_RECOMPUTE=1).
 struct HeadMergeArgs { cirs_ppo_cfg cfg; cirs_ppo_batch b; const int32_t* idx; int mb_norm, n_schunks; ActorPartialView pv; };
-template <bool kEnt, bool kMerge>
+template <bool kEnt, bool kMerge, bool kZin>
 __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I, int mb, int n_pad, int tiles_per_chunk,
                                                                          const uint4* __restrict__ planes,
                                                                          const float* __restrict__ ba, MbView v,
                                                                          float* __restrict__ dwap, HeadMergeArgs ma) {
     constexpr int kThreads = kBwdWaves * 64;
     static_assert(kThreads == 256, "the plane staging maps one 16-byte unit per thread and plane");
-    __shared__ __attribute__((aligned(16))) unsigned char sW[2][kWBufB];
+    constexpr int kCOff = kZin ? 0 : 3 * kRPlaneB;      // kZin: the C planes only
+    __shared__ __attribute__((aligned(16))) unsigned char sW[2][kCOff + 3 * kCPlaneB];
     __shared__ __attribute__((aligned(16))) float sB[2][kTileN];   // 16-byte aligned: the accumulator init reads 4 consecutive biases as one ds_read_b128
     __shared__ __attribute__((aligned(16))) float sT[kBwdWaves][kTileN * kTStride];
     __shared__ __attribute__((aligned(16))) float sR[2][kBwdWaves][kRSize];   // double-buffered: the sum of tile t runs inside iteration t + 1
@@ -907,9 +935,11 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
         const size_t tb = (size_t)((wave_ok ? row0 : 0) >> 5) * 12 * 64 + lane;
         const uint4* zp = v.h2z + tb;
         const uint4* bp = v.h2b + tb;
+        if (!kZin) {
 #pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-            HPL_SET(hz[s4], zp[(3 * s4) * 64], zp[(3 * s4 + 2) * 64]);
+            for (int s4 = 0; s4 < 4; ++s4) {
+                HPL_SET(hz[s4], zp[(3 * s4) * 64], zp[(3 * s4 + 2) * 64]);
+            }
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c)
@@ -933,26 +963,36 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
     const int n_tiles = max(0, min(tiles_per_chunk, (I - first_tile + kTileN - 1) / kTileN));
     // staging: unit `tid` of each of the six planes; destination offsets inside a buffer
     const int dst_r = (tid >> 3) * kRowB + (tid & 7) * 16;
-    const int dst_c = 3 * kRPlaneB + (tid >> 2) * kColB + (tid & 3) * 16;
+    const int dst_c = kCOff + (tid >> 2) * kColB + (tid & 3) * 16;
     uint4 gr0, gr2, gc0, gc2;
     float gb = 0.f;
 #define CIRS_ISSUE(TILE0)                                                                                  \
     do {                                                                                                   \
         const uint4* src_ = planes + (size_t)((TILE0) / kTileN) * kPlaneTileU4 + tid;                      \
-        gr0 = src_[0]; gr2 = src_[512]; gc0 = src_[768]; gc2 = src_[1280]; \
-        if (tid < kTileN) gb = ((TILE0) + tid) < I ? kScZ * ba[(TILE0) + tid] : 0.f;   /* the accumulators hold kScZ z */ \
+        if (!kZin) { gr0 = src_[0]; gr2 = src_[512]; }                                                     \
+        gc0 = src_[768]; gc2 = src_[1280];                                                                 \
+        if (!kZin && tid < kTileN) gb = ((TILE0) + tid) < I ? kScZ * ba[(TILE0) + tid] : 0.f;   /* the accumulators hold kScZ z */ \
     } while (0)
 #define CIRS_COMMIT(BUF)                                                                                   \
     do {                                                                                                   \
         unsigned char* base_ = sW[BUF];                                                                    \
-        *reinterpret_cast<uint4*>(base_ + dst_r) = gr0;                                                    \
-        \
-        *reinterpret_cast<uint4*>(base_ + 2 * kRPlaneB + dst_r) = gr2;                                     \
+        if (!kZin) {                                                                                       \
+            *reinterpret_cast<uint4*>(base_ + dst_r) = gr0;                                                \
+            *reinterpret_cast<uint4*>(base_ + 2 * kRPlaneB + dst_r) = gr2;                                 \
+        }                                                                                                  \
         *reinterpret_cast<uint4*>(base_ + dst_c) = gc0;                                                    \
         \
         *reinterpret_cast<uint4*>(base_ + 2 * kCPlaneB + dst_c) = gc2;                                     \
-        if (tid < kTileN) sB[BUF][tid] = gb;                                                               \
+        if (!kZin && tid < kTileN) sB[BUF][tid] = gb;                                                      \
     } while (0)
+    // kZin: this wave's tiles of the logit slab, [q][lane] float4 each; `zn` holds the tile requested one iteration ahead
+    const float4* zsl = v.zslab + ((size_t)(first_tile / kTileN) * (n_pad / kTileM) + (wave_ok ? row0 / kTileM : 0)) * kZTileF4 + lane;
+    const size_t zstep = (size_t)(n_pad / kTileM) * kZTileF4;
+    float4 zn[4];
+    if (kZin) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) zn[q] = zsl[q * 64];
+    }
     // the first tile's planes and the H2 planes above are on their way while the row statistics are merged
     if (n_tiles > 0) CIRS_ISSUE(first_tile);
     float lse, c_logp, c_ent, h_ent;
@@ -1098,24 +1138,37 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
         if (wave_ok) {
             const unsigned char* tw = sW[buf];
             // every LDS operand of this tile up front: one latency exposure instead of one per k-step
-            HPl za[4], cb[2][2];
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                const unsigned char* ap = tw + lo * kRowB + (16 * s4 + 8 * hi) * 2;
-                HPL_SET(za[s4], *reinterpret_cast<const uint4*>(ap), *reinterpret_cast<const uint4*>(ap + 2 * kRPlaneB));
-            }
-            f32x16 acc, acc1, acc2;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { acc[r] = sB[buf][acc_row(r, hi)]; acc1[r] = 0.f; acc2[r] = 0.f; }
-            CIRS_HSTAMP(1);
-            // (acc: bias + the h*h terms, acc1 / acc2: the cross terms -- same split as head_stats_kernel, so that p = exp(z - lse) sums to one)
-            hmfma_split2(za[0], hz[0], za[1], hz[1], acc, acc1, acc2);
+            HPl cb[2][2];
+            f32x16 acc;      // the logits' accumulator sum (kScZ z), then dZ in place
             RedRegs rg;
-            if (it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the second logits MFMA group
-            hmfma_split2(za[2], hz[2], za[3], hz[3], acc, acc1, acc2);
+            if (kZin) {
+                // the values head_stats_kernel formed for this (item tile, row tile); the next tile's are requested at once -- unconditionally, with a
+                // clamped tile number (the chunk's last iteration reads its own tile again)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[r] += acc2[r];
-            if (it > 0) reduce_store(rg, tile0 - kTileN);
+                for (int q = 0; q < 4; ++q) { acc[4 * q] = zn[q].x; acc[4 * q + 1] = zn[q].y; acc[4 * q + 2] = zn[q].z; acc[4 * q + 3] = zn[q].w; }
+                const float4* zp = zsl + (size_t)min(it + 1, n_tiles - 1) * zstep;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) zn[q] = zp[q * 64];
+                CIRS_HSTAMP(1);
+            } else {
+                HPl za[4];
+#pragma unroll
+                for (int s4 = 0; s4 < 4; ++s4) {
+                    const unsigned char* ap = tw + lo * kRowB + (16 * s4 + 8 * hi) * 2;
+                    HPL_SET(za[s4], *reinterpret_cast<const uint4*>(ap), *reinterpret_cast<const uint4*>(ap + 2 * kRPlaneB));
+                }
+                f32x16 acc1, acc2;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { acc[r] = sB[buf][acc_row(r, hi)]; acc1[r] = 0.f; acc2[r] = 0.f; }
+                CIRS_HSTAMP(1);
+                // (acc: bias + the h*h terms, acc1 / acc2: the cross terms -- same split as head_stats_kernel, so that p = exp(z - lse) sums to one)
+                hmfma_split2(za[0], hz[0], za[1], hz[1], acc, acc1, acc2);
+                if (it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the second logits MFMA group
+                hmfma_split2(za[2], hz[2], za[3], hz[3], acc, acc1, acc2);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] += acc1[r] + acc2[r];      // = head_stats_kernel's acc + (accs + acct)
+                if (it > 0) reduce_store(rg, tile0 - kTileN);
+            }
             // the B planes of the dH2 product are requested only now: the A planes of the logits are dead (the two sets never coexist:
             // the kernel runs at the 256-VGPR limit and every value beyond it costs an AGPR copy per use) and the dZ arithmetic below
             // covers their LDS latency
@@ -1123,7 +1176,7 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const unsigned char* bp = tw + 3 * kRPlaneB + (32 * c + lo) * kColB + (16 * t + 8 * hi) * 2;
+                    const unsigned char* bp = tw + kCOff + (32 * c + lo) * kColB + (16 * t + 8 * hi) * 2;
                     HPL_SET(cb[c][t], *reinterpret_cast<const uint4*>(bp), *reinterpret_cast<const uint4*>(bp + 2 * kCPlaneB));
                 }
             CIRS_HSTAMP(2);
@@ -1145,7 +1198,7 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             const bool last_tile = tile0 + kTileN > I;
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                const float t0 = __builtin_fmaf(acc[r] + acc1[r], kLog2e * kScZi, nlse2), t1 = __builtin_fmaf(acc[r + 1] + acc1[r + 1], kLog2e * kScZi, nlse2);
+                const float t0 = __builtin_fmaf(acc[r], kLog2e * kScZi, nlse2), t1 = __builtin_fmaf(acc[r + 1], kLog2e * kScZi, nlse2);
                 const float p0 = __builtin_amdgcn_exp2f(t0), p1 = __builtin_amdgcn_exp2f(t1);
                 tk[r] = t0; tk[r + 1] = t1;
                 pmax = __builtin_fmaxf(__builtin_fmaxf(pmax, p0), p1);      // v_max3_f32
@@ -1203,8 +1256,10 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             if (it + 1 < n_tiles) CIRS_COMMIT(buf ^ 1);
             {
                 const HPl a0 = hsplit8(acc, 0), a1 = hsplit8(acc, 8);   // element j: dZ[row lo][item acc_row(8 t + j, hi)]
+                if (kZin && it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: LDS round trip, adds and stores behind the dH2 MFMAs
                 hmfma_pair(a0, cb[0][0], cb[1][0], dh0, dh1);
                 hmfma_pair(a1, cb[0][1], cb[1][1], dh0, dh1);
+                if (kZin && it > 0) reduce_store(rg, tile0 - kTileN);
             }
             CIRS_HSTAMP(5);
             CIRS_HSTAMP(6);
@@ -1247,6 +1302,26 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
     ent += __shfl_xor(ent, 32, CIRS_WAVE);
     if (hi == 0) v.entp[(size_t)chunk * n_pad + jr] = ent;
     CIRS_SSTAMP(35);
+}
+// the instantiation of a step: entropy term in dZ | merge in the prologue | logits from the slab
+typedef void (*HeadBwdFn)(int, int, int, int, const uint4*, const float*, MbView, float*, HeadMergeArgs);
+__host__ inline HeadBwdFn head_bwd_fn(bool ent, bool merge, bool zin) {
+    switch ((ent ? 4 : 0) | (merge ? 2 : 0) | (zin ? 1 : 0)) {
+    case 0: return head_bwd_fused_kernel<false, false, false>;
+    case 1: return head_bwd_fused_kernel<false, false, true>;
+    case 2: return head_bwd_fused_kernel<false, true, false>;
+    case 3: return head_bwd_fused_kernel<false, true, true>;
+    case 4: return head_bwd_fused_kernel<true, false, false>;
+    case 5: return head_bwd_fused_kernel<true, false, true>;
+    case 6: return head_bwd_fused_kernel<true, true, false>;
+    default: return head_bwd_fused_kernel<true, true, true>;
+    }
+}
+// CIRS_PPO_HEAD_RECOMPUTE=1: the head backward forms the logits itself instead of reading head_stats_kernel's from the slab (read per call: the bit-identity
+// test and same-box A/B runs toggle it; not a tuning knob -- both forms give the same bits)
+__host__ inline bool head_recompute_env() {
+    const char* e = getenv("CIRS_PPO_HEAD_RECOMPUTE");
+    return e && atoi(e) != 0;
 }
 
 // ---- slab sums of the wa|ba gradient (one of kWaSumBlocks workgroups of 512 threads) ------------------------------------
@@ -2637,6 +2712,7 @@ struct PpoRun {     // what does not change between the steps of a call
     cirs::MbView v;
     float* tail;            // {clip, vf, ent, 0} partials of this rank (behind the flat gradient)
     bool merge_launch;      // CIRS_PPO_MERGE_KERNEL=1: the round-2 sequence with the merge of the statistics partials as a launch of its own (A/B runs)
+    bool head_recompute;    // CIRS_PPO_HEAD_RECOMPUTE=1: no logit hand-over between the two head kernels (A/B runs, bit-identity test)
 };
 struct PpoStep { const int32_t* idx; int mb; const int32_t* sidx; int mb_norm; float* dobs; float* loss_out; long opt_step; };
 
@@ -2654,6 +2730,7 @@ static PpoRun ppo_run(const cirs_ppo_cfg* cfg, float* params, float* grads, floa
     r.tail = grads + r.L.total;
     const char* mk_ = getenv("CIRS_PPO_MERGE_KERNEL");      // (read per call: tests toggle it)
     r.merge_launch = mk_ && atoi(mk_) != 0;
+    r.head_recompute = head_recompute_env();
     return r;
 }
 static cirs::TrunkRowOut trunk_out_of(const cirs::MbView& v) { return cirs::TrunkRowOut{v.h2, v.value, v.h1, v.obs, v.act, v.dst_row, v.adv, v.h2z, v.h2b}; }
@@ -2680,8 +2757,10 @@ static int launch_head(const PpoRun& r, const PpoStep& st, int* n_bchunks_out, b
     // head statistics (log-sum-exp, E_p[z]) on the matrix cores from the fp16 planes of Wa; all workgroups co-resident (2 per CU) with equal tile counts
     const int tpc_s = head_tiles_per_chunk(n_item_tiles, n_slabs, 2);   // measured: 1 / 2 / 3 workgroups per CU = 17.4 / 14.5 / 16.7 us
     const int n_schunks = cdiv(n_item_tiles, tpc_s);   // <= n_chunks: the partial arrays fit
-    CIRS_PROF_LAUNCH(2, r.s, hipLaunchKernelGGL(head_stats_kernel, dim3(n_schunks, n_slabs), dim3(256), 0, r.s, I, mb, n_pad, tpc_s,
-                                                (const uint4*)v.wa_planes, r.w.ba, (const uint4*)v.h2z, pv, (const int32_t*)v.act, v.za));
+    // (its logits go to v.zslab for the backward kernel unless CIRS_PPO_HEAD_RECOMPUTE=1)
+    const auto stats_fn = r.head_recompute ? head_stats_kernel<false> : head_stats_kernel<true>;
+    CIRS_PROF_LAUNCH(2, r.s, hipLaunchKernelGGL(stats_fn, dim3(n_schunks, n_slabs), dim3(256), 0, r.s, I, mb, n_pad, tpc_s,
+                                                (const uint4*)v.wa_planes, r.w.ba, (const uint4*)v.h2z, pv, (const int32_t*)v.act, v.za, v.zslab));
     CIRS_CHECK_LAUNCH("head_stats_kernel");
     // head backward; the merge of the statistics partials + row losses + backward coefficients (means over the global minibatch) run in
     // its prologue (CIRS_PPO_MERGE_KERNEL=1: as a launch of their own, the round-2 sequence, for A/B runs)
@@ -2695,13 +2774,8 @@ static int launch_head(const PpoRun& r, const PpoStep& st, int* n_bchunks_out, b
     const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
     const int n_bchunks = cdiv(n_item_tiles, tpc);  // <= n_chunks: the d h2 / entropy partial slabs fit
     const dim3 bgrid((n_bchunks + 7) & ~7, n_slabs), bblock(kBwdWaves * 64);
-    if (r.cfg->ent_coef != 0.f) {
-        if (r.merge_launch) CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL((head_bwd_fused_kernel<true, false>), bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, r.w.ba, v, v.dwap, hma));
-        else CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL((head_bwd_fused_kernel<true, true>), bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, r.w.ba, v, v.dwap, hma));
-    } else {
-        if (r.merge_launch) CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL((head_bwd_fused_kernel<false, false>), bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, r.w.ba, v, v.dwap, hma));
-        else CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL((head_bwd_fused_kernel<false, true>), bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, r.w.ba, v, v.dwap, hma));
-    }
+    const HeadBwdFn bwd_fn = head_bwd_fn(r.cfg->ent_coef != 0.f, !r.merge_launch, !r.head_recompute);
+    CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL(bwd_fn, bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)r.w.ba, v, v.dwap, hma));
     CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
     if (with_dh2_sum) {
         hipLaunchKernelGGL(dh2_sum_kernel, dim3(n_pad * (kH / 4) / 64 + cdiv(n_pad, 64)), dim3(64), 0, r.s, mb, n_pad, n_bchunks, v);
@@ -3023,8 +3097,10 @@ extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, flo
         ActorPartialView pv = partial_view(v.head_ws, n_pad, I);
         const int tpc_s = head_tiles_per_chunk(n_item_tiles, n_slabs, 2);
         const int n_schunks = cdiv(n_item_tiles, tpc_s);
-        hipLaunchKernelGGL(head_stats_kernel, dim3(n_schunks, n_slabs), dim3(256), 0, s, I, (int)mb, n_pad, tpc_s, (const uint4*)v.wa_planes, w.ba,
-                           (const uint4*)v.h2z, pv, (const int32_t*)nullptr, (float*)nullptr);
+        // (phase 2 of the same step reads the logits from v.zslab: the switch is the same in both phases of a step)
+        const auto stats_fn = head_recompute_env() ? head_stats_kernel<false> : head_stats_kernel<true>;
+        hipLaunchKernelGGL(stats_fn, dim3(n_schunks, n_slabs), dim3(256), 0, s, I, (int)mb, n_pad, tpc_s, (const uint4*)v.wa_planes, (const float*)w.ba,
+                           (const uint4*)v.h2z, pv, (const int32_t*)nullptr, (float*)nullptr, v.zslab);
         CIRS_CHECK_LAUNCH("head_stats_kernel");
         hipLaunchKernelGGL(head_tp_fold_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, s, *batch, idx, (int)mb, n_pad, n_schunks, pv, (const float*)w.wa,
                            (const float*)w.ba, (int)item_base, I, (const float*)v.h2, stats4);
@@ -3045,13 +3121,8 @@ extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, flo
         const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
         const int n_bchunks = cdiv(n_item_tiles, tpc);
         const HeadMergeArgs no_merge{};    // the row coefficients come from head_stats_merge_kernel above (statistics of every shard)
-        if (cfg->ent_coef != 0.f) {
-            hipLaunchKernelGGL((head_bwd_fused_kernel<true, false>), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(kBwdWaves * 64), 0, s, I, mb, n_pad, tpc,
-                               (const uint4*)v.wa_planes, w.ba, v, v.dwap, no_merge);
-        } else {
-            hipLaunchKernelGGL((head_bwd_fused_kernel<false, false>), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(kBwdWaves * 64), 0, s, I, mb, n_pad, tpc,
-                               (const uint4*)v.wa_planes, w.ba, v, v.dwap, no_merge);
-        }
+        hipLaunchKernelGGL(head_bwd_fn(cfg->ent_coef != 0.f, false, !head_recompute_env()), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(kBwdWaves * 64), 0, s, I,
+                           (int)mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)w.ba, v, v.dwap, no_merge);
         CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
         CIRS_HIP(hipMemsetAsync(red_slots, 0, sizeof(float) * (size_t)world * kWaSumBlocks, s));
         hipLaunchKernelGGL(dh2_sum_kernel, dim3(n_pad * (kH / 4) / 64 + cdiv(n_pad, 64)), dim3(64), 0, s, (int)mb, n_pad, n_bchunks, v, red_dh2, red_ent);

@@ -113,7 +113,7 @@ def parse(fetch_csv, write_csv, tag):
                  "| kernel | launches | FETCH_SIZE KB | WRITE_SIZE KB | HBM MB / launch |\n|---|---|---|---|---|\n")
         for k, v in sorted(kernels.items(), key=lambda kv: -kv[1]["bytes_per_launch"] * kv[1]["launches"]):
             fh.write(f"| `{k}` | {v['launches']} | {v['fetch_kb']} | {v['write_kb']} | {v['bytes_per_launch'] / 1e6:.2f} |\n")
-        for label, names in (("fused head", bench.MINIBATCH_KERNELS), ("split head", bench.MINIBATCH_KERNELS_SPLIT)):
+        for label, names in (("fused head", bench.MINIBATCH_KERNELS),):
             mb = [next((v["bytes_per_launch"] for kk, v in kernels.items() if kk.split("<")[0] == k), None) for k in names]
             if all(x is not None for x in mb):
                 fh.write(f"\nPPO minibatch step, {label} ({len(mb)} kernels; the shared ones are averaged over both paths' launches): **{sum(mb) / 1e6:.1f} MB**\n")
