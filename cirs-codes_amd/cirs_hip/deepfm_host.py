@@ -1,0 +1,94 @@
+"""Host restatement of the DeepFM user-model training step (csrc/deepfm_train.hip) for its three loss kinds; imports without
+libcirs_hip.so.
+
+torch_train   the optimiser steps of UserModel_Pairwise.fit_data (reference core/user_model.py:150-170) in plain torch (autograd +
+              torch.optim.Adam) over a state_dict under the reference's names, in fp32 or fp64:
+                forward      core/user_model_pairwise.py:98-132 (linear + FM + DNN)
+                loss         "pairwise"  loss_kuaishou_pairwise       CIRS-UserModel-kuaishou.py:262-278
+                             "ips"       loss_kuaishou_IPS_pairwise   DeepFM-IPS-pairwise.py:249-258
+                             "pd"        loss_kuaishou_PD_pairwise    PD-pairwise.py:242-251
+                regulariser  core/user_model.py:401-417: embedding_dict.* (l2_embedding), linear_model.* (l2_linear), every
+                             parameter (l2_all); the padding row of the feature table gets no data gradient and still decays
+              The comparison object of the device step for the two debiasing losses, which the test oracle does not know, in tests
+              and in tools/probe_usertrain.py."""
+import numpy as np
+import torch
+
+LOSS_KINDS = ("pairwise", "ips", "pd")
+
+
+def pair_forward(p, X):
+    """X [n,7] = [user, photo, feat0..3, duration] -> y [n] over the parameter dict p (reference names)."""
+    ids = X[:, :6].long()
+    dur = X[:, 6:7]
+    vs = [p["embedding_dict.user_id.weight"][ids[:, 0]], p["embedding_dict.photo_id.weight"][ids[:, 1]]] + \
+         [p["embedding_dict.feat.weight"][ids[:, 2 + q]] for q in range(4)]
+    lin = p["linear.embedding_dict.user_id.weight"][ids[:, 0], 0] + p["linear.embedding_dict.photo_id.weight"][ids[:, 1], 0]
+    for q in range(4):
+        lin = lin + p["linear.embedding_dict.feat.weight"][ids[:, 2 + q], 0]
+    lin = lin + dur[:, 0] * p["linear.weight"].reshape(())
+    S = sum(vs)
+    fm = 0.5 * ((S * S) - sum(v * v for v in vs)).sum(1)
+    x = torch.cat(vs + [dur], dim=1)
+    h1 = torch.relu(x @ p["dnn.linears.0.weight"].T + p["dnn.linears.0.bias"])
+    h2 = torch.relu(h1 @ p["dnn.linears.1.weight"].T + p["dnn.linears.1.bias"])
+    return lin + fm + (h2 @ p["last.weight"].T)[:, 0] + p["out.bias"].reshape(())
+
+
+def loss_terms(kind, y, yp, yn, score, alpha=None, beta=None):
+    """-> (loss_y, bpr, loss_ab) of one batch; score = exposure ("pairwise"), IPS weight ("ips") or popularity ** gamma ("pd")."""
+    log_sg = torch.log(torch.sigmoid(yp - yn))
+    zero = torch.zeros((), dtype=yp.dtype, device=yp.device)
+    if kind == "pairwise":
+        ex_new, loss_ab = score, zero
+        if alpha is not None:
+            ex_new = score * alpha * beta
+            loss_ab = ((alpha - 1) ** 2).mean() + ((beta - 1) ** 2).mean()
+        return ((yp / (1 + ex_new) - y) ** 2).mean(), -log_sg.mean(), loss_ab
+    if kind == "ips":
+        return (((yp - y) ** 2) * score).mean(), -(log_sg * score).mean(), zero
+    if kind == "pd":
+        return ((yp * score - y) ** 2).mean(), -log_sg.mean(), zero
+    raise ValueError(f"loss kind must be one of {LOSS_KINDS}, got {kind!r}")
+
+
+def torch_train(init, x, y, score, batch_size, steps=None, order=None, kind="pairwise", use_ab=False, lambda_ab=0.0, l2_embedding=1e-5,
+                l2_linear=1e-5, l2_all=0.1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype=torch.float32, keep=()):
+    """init: state_dict (numpy / tensors); x [N,14], y [N] or [N,1], score likewise; batch b = rows order[b * batch_size : ...] (None: file
+    order).  -> (losses [steps, 5] = {loss, loss_y, bpr, loss_ab, reg}, {step index: parameters after that step for the indices in
+    `keep`}, final parameters)."""
+    if use_ab and kind != "pairwise":
+        raise ValueError(f"the {kind!r} loss takes no alpha/beta")
+    p = {k: torch.as_tensor(np.asarray(v)).to(dtype).clone().requires_grad_(True) for k, v in init.items()}
+    opt = torch.optim.Adam(list(p.values()), lr=lr, betas=betas, eps=eps)
+    x = torch.as_tensor(np.asarray(x)).to(dtype)
+    y = torch.as_tensor(np.asarray(y)).to(dtype).reshape(-1)
+    score = torch.as_tensor(np.asarray(score)).to(dtype).reshape(-1)
+    order = torch.arange(x.shape[0]) if order is None else torch.as_tensor(np.asarray(order)).long()
+    n_steps = (len(order) + batch_size - 1) // batch_size
+    steps = n_steps if steps is None else min(steps, n_steps)
+    feat = "embedding_dict.feat.weight"
+    losses, kept = [], {}
+    for st in range(steps):
+        idx = order[st * batch_size:(st + 1) * batch_size]
+        xb, yb, sb = x[idx], y[idx], score[idx]
+        yp, yn = pair_forward(p, xb[:, :7]), pair_forward(p, xb[:, 7:])
+        alpha = beta = None
+        if use_ab:
+            alpha = p["ab_embedding_dict.alpha_u.weight"][xb[:, 0].long(), 0]
+            beta = p["ab_embedding_dict.beta_i.weight"][xb[:, 1].long(), 0]
+        loss_y, bpr, loss_ab = loss_terms(kind, yb, yp, yn, sb, alpha, beta)
+        loss = loss_y + bpr + lambda_ab * loss_ab
+        reg = 0.0
+        for k, v in p.items():
+            c = l2_all + (l2_embedding if k.startswith("embedding_dict.") else 0.0) + (l2_linear if k.startswith("linear_model.") else 0.0)
+            reg = reg + c * (v * v).sum()
+        opt.zero_grad()
+        (loss + reg).backward()
+        # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
+        p[feat].grad[0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+        opt.step()
+        losses.append([float(t.detach()) for t in (loss, loss_y, bpr, loss_ab, reg)])
+        if st in keep:
+            kept[st] = {k: v.detach().clone().numpy() for k, v in p.items()}
+    return np.array(losses), kept, {k: v.detach().clone().numpy() for k, v in p.items()}

@@ -1,6 +1,6 @@
 """UserModel (reference core/user_model.py:29-581): the base class of the CIRS user models — training loop surface
 (`compile`, `fit_data`), static-baseline recommendation (`compile_UCB`, `recommend_k_item`) — delegating every computation to
-the device model of the subclass (`device_model()` -> cirs_hip.deepfm.DeviceDeepFM, `cirs_deepfm_train_step`,
+the device model of the subclass (`device_model()` -> cirs_hip.deepfm.DeviceDeepFM, `cirs_deepfm_train_epoch`,
 `cirs_select_items`).  Subclasses build the parameters under the reference's state_dict names (UserModel_Pairwise)."""
 import numpy as np
 import torch
@@ -19,25 +19,27 @@ class UserModel(nn.Module):
     # ---- training (reference core/user_model.py:74-170) ---------------------------------------------------------------
     def compile(self, optimizer, loss_dict=None, metrics=None, metric_fun=None, loss_func=None):
         assert optimizer == "adam" or isinstance(optimizer, torch.optim.Adam), "the device step implements torch.optim.Adam"
-        assert loss_func is not None and hasattr(loss_func, "lambda_ab"), \
-            "pass core.user_model_pairwise.make_loss_kuaishou_pairwise(lambda_ab): the loss runs inside cirs_deepfm_train_step"
+        assert loss_func is not None and (hasattr(loss_func, "lambda_ab") or hasattr(loss_func, "loss_kind")), \
+            "pass core.user_model_pairwise.make_loss_kuaishou_pairwise(lambda_ab), loss_kuaishou_IPS_pairwise or " \
+            "loss_kuaishou_PD_pairwise: the loss runs inside the device training step"
+        assert getattr(loss_func, "loss_kind", "pairwise") == "pairwise" or self.ab_columns is None, \
+            "the IPS and PD losses take no alpha/beta: build the model without ab_columns"
         self.metrics_names = ["loss"]
         self.loss_func, self.metric_fun, self.metrics = loss_func, metric_fun, metrics
         self.optim = "adam"
         self._lr = optimizer.param_groups[0]["lr"] if isinstance(optimizer, torch.optim.Adam) else 1e-3
 
     def fit_data(self, dataset_train, dataset_val=None, batch_size=256, epochs=1, verbose=1, initial_epoch=0, callbacks=None, shuffle=True):
-        """One pass per epoch over (x, y, score) minibatches; every step is cirs_deepfm_train_step on the device."""
+        """One pass per epoch over (x, y, score) minibatches: the data set is made resident on the device once, every epoch is one
+        cirs_deepfm_train_epoch call over the permutation drawn here, and the losses are read back once per epoch."""
         from cirs_hip.deepfm_train import DeepFMTrainer
         assert self.optim is not None, "call compile() first"
         if self._trainer is None:
-            self._trainer = DeepFMTrainer(self.state_dict(), use_ab=self.ab_columns is not None, lambda_ab=self.loss_func.lambda_ab,
-                                          l2_embedding=self._l2[0], l2_linear=self._l2[1], l2_all=self._l2[2], lr=self._lr)
+            self._trainer = DeepFMTrainer(self.state_dict(), use_ab=self.ab_columns is not None, lambda_ab=getattr(self.loss_func, "lambda_ab", 0.0),
+                                          l2_embedding=self._l2[0], l2_linear=self._l2[1], l2_all=self._l2[2], lr=self._lr,
+                                          loss_kind=getattr(self.loss_func, "loss_kind", "pairwise"))
         tr = self._trainer
-        x = torch.as_tensor(dataset_train.x_numpy).to(tr.device, torch.float32)
-        y = torch.as_tensor(dataset_train.y_numpy).to(tr.device, torch.float32)
-        score = torch.as_tensor(dataset_train.score).to(tr.device, torch.float32)
-        n_all = x.shape[0]
+        n_all = tr.load(dataset_train.x_numpy, dataset_train.y_numpy, dataset_train.score)
         callbacks = callbacks or []
         for cb in callbacks:
             cb.on_train_begin()
@@ -45,13 +47,10 @@ class UserModel(nn.Module):
         for epoch in range(initial_epoch, epochs):
             for cb in callbacks:
                 cb.on_epoch_begin(epoch)
-            order = torch.randperm(n_all, device=tr.device) if shuffle else torch.arange(n_all, device=tr.device)
-            loss_sum = torch.zeros((), device=tr.device)
-            for s0 in range(0, n_all, batch_size):
-                idx = order[s0:s0 + batch_size]
-                lo = tr.step(x[idx], y[idx], score[idx])
-                loss_sum += lo[0] + lo[4]
-            logs = {"loss": float(loss_sum) / n_all}       # total_loss_epoch / sample_num (core/user_model.py:205)
+            order = torch.randperm(n_all, device=tr.device) if shuffle else None
+            lo = tr.epoch(order, batch_size, check=False)
+            loss_sum = float((lo[:, 0] + lo[:, 4]).double().sum())     # the fp32 step totals summed in float64, like `+= total_loss.item()`
+            logs = {"loss": loss_sum / n_all}              # total_loss_epoch / sample_num (core/user_model.py:205)
             history.append(logs)
             for cb in callbacks:
                 cb.on_epoch_end(epoch, logs)

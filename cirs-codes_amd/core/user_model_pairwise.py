@@ -27,6 +27,29 @@ def make_loss_kuaishou_pairwise(lambda_ab: float):
     return loss_kuaishou_pairwise
 
 
+_sigmoid = nn.Sigmoid()
+
+
+def loss_kuaishou_IPS_pairwise(y, y_deepfm_pos, y_deepfm_neg, IPS_score):
+    """DeepFM-IPS-pairwise.py:249-258: regression and BPR terms, each sample weighted by its inverse propensity score.  The torch
+    formula is for host use; fit_data recognises the loss by its `loss_kind` and runs it inside cirs_deepfm_train_epoch."""
+    loss_y = (((y_deepfm_pos - y) ** 2) * IPS_score).mean()
+    bpr_click = -(_sigmoid(y_deepfm_pos - y_deepfm_neg).log() * IPS_score).mean()
+    return loss_y + bpr_click
+
+
+def loss_kuaishou_PD_pairwise(y, y_deepfm_pos, y_deepfm_neg, popularity):
+    """PD-pairwise.py:242-251: the positive prediction is multiplied by popularity ** gamma of the item in its time bin before the
+    regression term; plain BPR.  Host use; fit_data runs it inside cirs_deepfm_train_epoch (`loss_kind`)."""
+    loss_y = ((y_deepfm_pos * popularity - y) ** 2).mean()
+    bpr_click = -_sigmoid(y_deepfm_pos - y_deepfm_neg).log().mean()
+    return loss_y + bpr_click
+
+
+loss_kuaishou_IPS_pairwise.loss_kind = "ips"
+loss_kuaishou_PD_pairwise.loss_kind = "pd"
+
+
 class UserModel_Pairwise(UserModel):
     def __init__(self, feature_columns, y_columns, task, task_logit_dim, dnn_hidden_units=(128, 128), l2_reg_embedding=1e-5,
                  l2_reg_dnn=1e-1, init_std=0.0001, task_dnn_units=None, seed=2022, dnn_dropout=0, dnn_activation="relu",

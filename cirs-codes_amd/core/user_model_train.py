@@ -16,6 +16,33 @@ DEFAULTS = dict(env="KuaishouEnv-v0", user_model_name="DeepFM", message="UM", ta
                 l2_reg_dnn=0.1, lambda_ab=10.0, is_ab=True, batch_size=2048, epoch=5, lr=1e-3, seed=2022)
 
 
+class _RLTest:   # epoch-end hook in the position of compile_RL_test
+    def __init__(self, model, rl_test):
+        self.model, self.rl_test = model, rl_test
+
+    def on_train_begin(self): pass
+    def on_train_end(self): pass
+    def on_epoch_begin(self, epoch): pass
+
+    def on_epoch_end(self, epoch, logs):
+        if self.rl_test is not None:
+            logs["RL_val"] = self.rl_test(self.model, epoch)
+
+
+def _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set):
+    """The three files the RL script loads: constructor parameters, the normalised reward table, the state dict (on the CPU)."""
+    paths = SimpleNamespace(params=os.path.join(model_dir, "{}_params_{}.pickle".format(a.user_model_name, a.message)),
+                            normed_mat=os.path.join(model_dir, "normed_mat-{}.pickle".format(a.message)),
+                            state_dict=os.path.join(model_dir, "{}_{}.pt".format(a.user_model_name, a.message)))
+    with open(paths.params, "wb") as fh:
+        pickle.dump(dict(params, device="cpu"), fh)
+    normed_mat = KuaishouEnv.compute_normed_reward(model, lbe_user, lbe_photo, val_set.df_photo_env)
+    with open(paths.normed_mat, "wb") as fh:
+        pickle.dump(normed_mat, fh)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, paths.state_dict)
+    return paths, normed_mat
+
+
 def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, **overrides):
     """Returns SimpleNamespace(model, history, normed_mat, paths).  rl_test(model, epoch) (optional) is called after every epoch,
     the place of the reference's compile_RL_test hook (e.g. a partial of evaluation.test_static_model_in_RL_env)."""
@@ -35,25 +62,49 @@ def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, **ov
     model = UserModel_Pairwise(l2_reg_dnn=a.l2_reg_dnn, **params)
     model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=make_loss_kuaishou_pairwise(a.lambda_ab))
 
-    class _RLTest:   # epoch-end hook in the position of compile_RL_test
-        def on_train_begin(self): pass
-        def on_train_end(self): pass
-        def on_epoch_begin(self, epoch): pass
-        def on_epoch_end(self, epoch, logs):
-            if rl_test is not None:
-                logs["RL_val"] = rl_test(model, epoch)
+    history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [_RLTest(model, rl_test)])
 
-    history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [_RLTest()])
+    paths, normed_mat = _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set)
+    return SimpleNamespace(model=model, history=history, normed_mat=normed_mat, paths=paths, val_set=val_set,
+                           lbe_user=lbe_user, lbe_photo=lbe_photo)
 
-    paths = SimpleNamespace(params=os.path.join(model_dir, "{}_params_{}.pickle".format(a.user_model_name, a.message)),
-                            normed_mat=os.path.join(model_dir, "normed_mat-{}.pickle".format(a.message)),
-                            state_dict=os.path.join(model_dir, "{}_{}.pt".format(a.user_model_name, a.message)))
-    with open(paths.params, "wb") as fh:
-        pickle.dump(dict(params, device="cpu"), fh)
-    normed_mat = KuaishouEnv.compute_normed_reward(model, lbe_user, lbe_photo, val_set.df_photo_env)
-    with open(paths.normed_mat, "wb") as fh:
-        pickle.dump(normed_mat, fh)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, paths.state_dict)
+
+DEBIAS_DEFAULTS = dict(env="KuaishouEnv-v0", feature_dim=16, dnn=(64, 64), l2_reg_dnn=0.1, batch_size=2048, epoch=50, lr=1e-3, seed=2021,
+                       gamma=0.1)
+DEBIAS_NAMES = {"ips": "DeepFM-IPS-pairwise", "pd": "PD-pairwise"}
+
+
+def train_debias_kuaishou(datapath, method="ips", save_root=".", callbacks=None, rl_test=None, **overrides):
+    """The training runs of the two debiasing baselines (DeepFM-IPS-pairwise.py:149-239, PD-pairwise.py:171-238, `main`): KuaiRec files
+    -> training set with the method's score column (core.user_data) -> UserModel_Pairwise without alpha/beta fitted on the device with
+    the method's loss.  rl_test(model, epoch) sits where the scripts' compile_RL_test hook sits.  "ips" writes the three artefacts its
+    script writes (`<name>_params_<msg>.pickle`, `normed_mat-<msg>.pickle`, `<name>_<msg>.pt`); "pd", like its script, writes none.
+    Returns SimpleNamespace(model, history, normed_mat, paths, val_set, lbe_user, lbe_photo), normed_mat and paths None for "pd"."""
+    from core.user_data import load_dataset_kuaishou_IPS_pairwise, load_dataset_kuaishou_PD
+    from core.user_model_pairwise import loss_kuaishou_IPS_pairwise, loss_kuaishou_PD_pairwise
+    if method not in DEBIAS_NAMES:
+        raise ValueError(f"method must be 'ips' or 'pd', got {method!r}")
+    name = DEBIAS_NAMES[method]
+    a = SimpleNamespace(**{**DEBIAS_DEFAULTS, "user_model_name": name, "message": name, **overrides})
+    entity_dim = a.feature_dim
+    model_dir = os.path.join(save_root, "saved_models", a.env, a.user_model_name)
+    os.makedirs(os.path.join(model_dir, "logs"), exist_ok=True)
+
+    mat, lbe_user, lbe_photo, list_feat, df_photo_env, df_dist_small = KuaishouEnv.load_mat(datapath)
+    if method == "ips":
+        train_set, x_columns, y_columns = load_dataset_kuaishou_IPS_pairwise(entity_dim, a.feature_dim, datapath=datapath)
+    else:
+        train_set, x_columns, y_columns = load_dataset_kuaishou_PD(entity_dim, a.feature_dim, a.gamma, datapath=datapath)
+    val_set = load_static_validate_data_kuaishou(entity_dim, a.feature_dim, datapath)
+
+    params = {"feature_columns": x_columns, "y_columns": y_columns, "task": "regression", "task_logit_dim": 1,
+              "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cuda"}
+    model = UserModel_Pairwise(l2_reg_dnn=a.l2_reg_dnn, **params)
+    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr),
+                  loss_func=loss_kuaishou_IPS_pairwise if method == "ips" else loss_kuaishou_PD_pairwise)
+
+    history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [_RLTest(model, rl_test)])
+    paths, normed_mat = _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set) if method == "ips" else (None, None)
     return SimpleNamespace(model=model, history=history, normed_mat=normed_mat, paths=paths, val_set=val_set,
                            lbe_user=lbe_user, lbe_photo=lbe_photo)
 

@@ -5,6 +5,12 @@
 //                           (KuaiRec big matrix: ~1.1e10 terms) -- one wavefront per interaction, lanes stride the history.
 //   cirs_find_negative      find_negative (core/util.py:173-196, numba): the nearest item id above (else below) the positive
 //                           one that the user has interacted with in neither matrix, skipping the absent id 1225.  Integer.
+//   cirs_item_bin_counts /  the score columns of the two debiasing baselines: "how often does this row's item occur among the log
+//   cirs_item_bin_gather    rows of this row's time bin" -- compute_IPS_kuaishouRec (DeepFM-IPS-pairwise.py:79-86, one bin) and
+//                           compute_popularity_kuaishouRec_pairwise (PD-pairwise.py:76-108, num_bin bins, half-open, the last one
+//                           closed, :93-96), both a Series.map over every row in the reference.  The device assigns bins by
+//                           comparison, counts with integer atomics and gathers; every float operation of the scores stays on the
+//                           host (numpy, on the small table), so they equal the reference's bit for bit.
 // Distances come from a table (row-major [n_items, n_items], the reference's 1 / similarity matrix) or, when it is null,
 // from the packed category words (1 / Jaccard, inf when disjoint), exactly like the env kernel.
 #include "common.h"
@@ -64,6 +70,37 @@ __global__ __launch_bounds__(256) void find_negative_kernel(const int64_t* __res
     neg_out[i] = found;   // -1: every other item was seen (the reference leaves the row at its zero initialisation)
 }
 
+// bounds[b] <= ts < bounds[b + 1], the last bin closed; a row that no bin takes gets -1 (rounding at time_max: the reference leaves 0)
+__global__ __launch_bounds__(256) void item_bin_counts_kernel(const int32_t* __restrict__ photo, const double* __restrict__ timestamp, long n,
+                                                              const double* __restrict__ bounds, int num_bin, int n_items,
+                                                              int32_t* __restrict__ bin_out, int32_t* __restrict__ counts) {
+    const long r = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    int bin = -1;
+    if (timestamp) {
+        const double ts = timestamp[r];
+        for (int b = 0; b < num_bin; ++b) {      // the reference assigns bin after bin: a later match would overwrite an earlier one
+            const double lo = bounds[b], hi = bounds[b + 1];
+            if (lo <= ts && (b < num_bin - 1 ? ts < hi : ts <= hi)) bin = b;
+        }
+    } else {
+        bin = 0;
+    }
+    const int p = photo[r];
+    if (p < 0 || p >= n_items) bin = -1;
+    bin_out[r] = bin;
+    if (bin >= 0) atomicAdd(&counts[(size_t)bin * n_items + p], 1);
+}
+
+__global__ __launch_bounds__(256) void item_bin_gather_kernel(const int32_t* __restrict__ photo, const int32_t* __restrict__ bin, long n,
+                                                              const double* __restrict__ table, int num_bin, int n_items,
+                                                              double* __restrict__ out) {
+    const long r = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int b = bin[r], p = photo[r];
+    out[r] = (b < 0 || b >= num_bin || p < 0 || p >= n_items) ? 0.0 : table[(size_t)b * n_items + p];
+}
+
 }  // namespace cirs
 
 extern "C" int cirs_exposure_history(const int64_t* user_start, const int32_t* photo, const double* timestamp, int64_t n_rows,
@@ -88,5 +125,30 @@ extern "C" int cirs_find_negative(const int64_t* user_ids, const int64_t* photo_
     hipLaunchKernelGGL(find_negative_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, user_ids, photo_ids, (long)n, seen_small,
                        seen_big, (n_items + 31) / 32, (long)n_items - 1, (long)absent_id, neg_out);
     CIRS_CHECK_LAUNCH("find_negative_kernel");
+    return CIRS_OK;
+}
+
+extern "C" int cirs_item_bin_counts(const int32_t* photo, const double* timestamp, int64_t n, const double* bounds, int32_t num_bin,
+                                    int32_t n_items, int32_t* bin_out, int32_t* counts, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(num_bin >= 1 && n_items >= 1 && counts, "need at least one bin, one item and the count table");
+    CIRS_REQUIRE(timestamp ? bounds != nullptr : num_bin == 1, "without timestamps there is one bin; with them the bin bounds are needed");
+    CIRS_HIP(hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)num_bin * (size_t)n_items, (hipStream_t)stream));
+    if (n <= 0) return CIRS_OK;
+    CIRS_REQUIRE(photo && bin_out, "null argument");
+    hipLaunchKernelGGL(item_bin_counts_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, photo, timestamp, (long)n, bounds,
+                       num_bin, n_items, bin_out, counts);
+    CIRS_CHECK_LAUNCH("item_bin_counts_kernel");
+    return CIRS_OK;
+}
+
+extern "C" int cirs_item_bin_gather(const int32_t* photo, const int32_t* bin, int64_t n, const double* table, int32_t num_bin,
+                                    int32_t n_items, double* out, void* stream) {
+    using namespace cirs;
+    if (n <= 0) return CIRS_OK;
+    CIRS_REQUIRE(photo && bin && table && out && num_bin >= 1 && n_items >= 1, "null argument");
+    hipLaunchKernelGGL(item_bin_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, photo, bin, (long)n, table, num_bin,
+                       n_items, out);
+    CIRS_CHECK_LAUNCH("item_bin_gather_kernel");
     return CIRS_OK;
 }

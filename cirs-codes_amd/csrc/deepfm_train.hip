@@ -15,8 +15,16 @@
 //   adam_l2_kernel      g += 2 * l2_c * p (the regulariser is dense: every row of every table decays), Adam, and the
 //                       regulariser's value as per-workgroup partials.
 // All reductions have a fixed order: two runs give identical bits.
+//
+// train_rows_kernel takes the loss as a compile-time kind (the pair forward / backward, the GEMMs, the scatter and Adam are shared):
+//   0  loss_kuaishou_pairwise          exposure-discounted regression + BPR + alpha/beta penalty (above)
+//   1  loss_kuaishou_IPS_pairwise      DeepFM-IPS-pairwise.py:249-258: mean((yp - y)^2 w) + mean(-log sigmoid(yp - yn) w), w = score
+//   2  loss_kuaishou_PD_pairwise       PD-pairwise.py:242-251: mean((yp pop - y)^2) + mean(-log sigmoid(yp - yn)), pop = score
+// and reads sample i of a step at row order[r0 + i] of a device-resident data set (r0 + i when order is null), so that
+// cirs_deepfm_train_epoch queues every step of a pass back to back without a gather launch or a host round trip.
 #include <hipcub/hipcub.hpp>
 #include "small_gemm.h"
+#include "train_step.h"
 
 namespace cirs {
 
@@ -131,12 +139,18 @@ __device__ __forceinline__ void pair_backward(const float* __restrict__ P, const
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void train_rows_kernel(cirs_deepfm_cfg cfg, const float* __restrict__ P, const int64_t* __restrict__ uid_pos,
-                                                         const int64_t* __restrict__ pid_pos, const int32_t* __restrict__ feats_pos,
-                                                         const float* __restrict__ dur_pos, const int64_t* __restrict__ uid_neg,
-                                                         const int64_t* __restrict__ pid_neg, const int32_t* __restrict__ feats_neg,
-                                                         const float* __restrict__ dur_neg, const float* __restrict__ y,
-                                                         const float* __restrict__ exposure, int n, int use_ab, float lambda_ab, TrainRows o) {
+struct TrainCols {  // the batch (or the whole data set) in column form; exposure = the score column of the loss kind
+    const int64_t *uid_pos, *pid_pos; const int32_t* feats_pos; const float* dur_pos;
+    const int64_t *uid_neg, *pid_neg; const int32_t* feats_neg; const float* dur_neg;
+    const float *y, *exposure;
+};
+
+constexpr int kLossPairwise = 0, kLossIPS = 1, kLossPD = 2;
+
+template <int KIND>
+__global__ __launch_bounds__(256) void train_rows_kernel(cirs_deepfm_cfg cfg, const float* __restrict__ P, TrainCols c,
+                                                         const int64_t* __restrict__ order, long r0, long n_rows, int n, int use_ab,
+                                                         float lambda_ab, TrainRows o) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int E = cfg.emb_dim, K = 6 * E + 1;
     const TrainLayout L = train_layout(cfg);
@@ -149,37 +163,59 @@ __global__ __launch_bounds__(256) void train_rows_kernel(cirs_deepfm_cfg cfg, co
     float *xn = base + per_pair, *Sn = xn + K + 1, *a1n = Sn + E, *a2n = a1n + tH;
     float* t64 = base + 2 * per_pair;
     float* dxs = t64 + tH;
-    const long up = uid_pos[i], pp = pid_pos[i], un = uid_neg[i], pn = pid_neg[i];
+    long row = order ? (long)order[r0 + i] : r0 + i;
+    const bool bad_row = row < 0 || row >= n_rows;   // an index outside the data set: no read there, the step's loss becomes NaN
+    if (bad_row) row = 0;
+    const long up = c.uid_pos[row], pp = c.pid_pos[row], un = c.uid_neg[row], pn = c.pid_neg[row];
     int32_t fp[4], fn[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { fp[q] = feats_pos[(size_t)i * 4 + q]; fn[q] = feats_neg[(size_t)i * 4 + q]; }
-    const float dp = dur_pos[i], dn = dur_neg[i];
+    for (int q = 0; q < 4; ++q) { fp[q] = c.feats_pos[(size_t)row * 4 + q]; fn[q] = c.feats_neg[(size_t)row * 4 + q]; }
+    const float dp = c.dur_pos[row], dn = c.dur_neg[row];
     const float yp = pair_forward(P, L, E, K, up, pp, fp, dp, lane, xp, Sp, a1p, a2p);
     const float yn = pair_forward(P, L, E, K, un, pn, fn, dn, lane, xn, Sn, a1n, a2n);
-    // ---- loss_kuaishou_pairwise on this sample; every mean is over the n samples of the batch ---------------------
+    // ---- the loss on this sample; every mean is over the n samples of the batch -----------------------------------
     const float inv_n = 1.0f / (float)n;
-    const float ex = exposure[i];
-    float alpha = 1.f, beta = 1.f;
-    if (use_ab) { alpha = P[L.alpha_u + up]; beta = P[L.beta_i + pp]; }
-    const float ex_new = use_ab ? ex * alpha * beta : ex;
-    const float inv1 = 1.0f / (1.0f + ex_new);
-    const float y_exp = inv1 * yp;
-    const float err = y_exp - y[i];
+    const float ex = c.exposure[row];
     const float sg = 1.0f / (1.0f + expf(-(yp - yn)));   // sigmoid(y_pos - y_neg)
-    const float dyp = 2.0f * inv_n * err * inv1 - inv_n * (1.0f - sg);
-    const float dyn = inv_n * (1.0f - sg);
-    float dalpha = 0.f, dbeta = 0.f;
-    if (use_ab) {
-        const float dex = 2.0f * inv_n * err * (-yp * inv1 * inv1);   // d loss_y / d exposure_new
-        dalpha = dex * ex * beta + lambda_ab * 2.0f * inv_n * (alpha - 1.0f);
-        dbeta = dex * ex * alpha + lambda_ab * 2.0f * inv_n * (beta - 1.0f);
+    float dyp, dyn, dalpha = 0.f, dbeta = 0.f, lp4[4];
+    if constexpr (KIND == kLossPairwise) {
+        float alpha = 1.f, beta = 1.f;
+        if (use_ab) { alpha = P[L.alpha_u + up]; beta = P[L.beta_i + pp]; }
+        const float ex_new = use_ab ? ex * alpha * beta : ex;
+        const float inv1 = 1.0f / (1.0f + ex_new);
+        const float y_exp = inv1 * yp;
+        const float err = y_exp - c.y[row];
+        dyp = 2.0f * inv_n * err * inv1 - inv_n * (1.0f - sg);
+        dyn = inv_n * (1.0f - sg);
+        if (use_ab) {
+            const float dex = 2.0f * inv_n * err * (-yp * inv1 * inv1);   // d loss_y / d exposure_new
+            dalpha = dex * ex * beta + lambda_ab * 2.0f * inv_n * (alpha - 1.0f);
+            dbeta = dex * ex * alpha + lambda_ab * 2.0f * inv_n * (beta - 1.0f);
+        }
+        lp4[0] = err * err;
+        lp4[1] = -logf(sg);
+        lp4[2] = use_ab ? (alpha - 1.0f) * (alpha - 1.0f) : 0.f;
+        lp4[3] = use_ab ? (beta - 1.0f) * (beta - 1.0f) : 0.f;
+    } else if constexpr (KIND == kLossIPS) {   // ex = the inverse-propensity weight of the sample
+        const float err = yp - c.y[row];
+        dyp = inv_n * ex * (2.0f * err - (1.0f - sg));
+        dyn = inv_n * ex * (1.0f - sg);
+        lp4[0] = ex * (err * err);
+        lp4[1] = -(ex * logf(sg));
+        lp4[2] = 0.f; lp4[3] = 0.f;
+    } else {                                   // ex = popularity^gamma of the sample's item in its time bin
+        const float err = yp * ex - c.y[row];
+        dyp = 2.0f * inv_n * err * ex - inv_n * (1.0f - sg);
+        dyn = inv_n * (1.0f - sg);
+        lp4[0] = err * err;
+        lp4[1] = -logf(sg);
+        lp4[2] = 0.f; lp4[3] = 0.f;
     }
     if (lane == 0) {
         float* lp = o.LP + (size_t)i * 4;
-        lp[0] = err * err;
-        lp[1] = -logf(sg);
-        lp[2] = use_ab ? (alpha - 1.0f) * (alpha - 1.0f) : 0.f;
-        lp[3] = use_ab ? (beta - 1.0f) * (beta - 1.0f) : 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) lp[q] = lp4[q];
+        if (bad_row) lp[0] = __builtin_nanf("");
     }
     pair_backward(P, L, E, K, up, pp, fp, dp, dyp, dalpha, dbeta, lane, i, xp, Sp, a1p, a2p, t64, dxs, o);
     pair_backward(P, L, E, K, un, pn, fn, dn, dyn, 0.f, 0.f, lane, n + i, xn, Sn, a1n, a2n, t64, dxs, o);
@@ -350,20 +386,22 @@ extern "C" int64_t cirs_deepfm_train_workspace_bytes(const cirs_deepfm_cfg* cfg,
     return (int64_t)cirs::train_ws_floats(cfg, n) * 4;
 }
 
-extern "C" int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
-                                      int64_t step_before, const int64_t* uid_pos, const int64_t* pid_pos, const int32_t* feats_pos,
-                                      const float* dur_pos, const int64_t* uid_neg, const int64_t* pid_neg, const int32_t* feats_neg,
-                                      const float* dur_neg, const float* y, const float* exposure, int32_t n, int32_t use_ab,
-                                      float lambda_ab, float l2_embedding, float l2_linear, float l2_all, float lr, float beta1,
-                                      float beta2, float eps, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
-    using namespace cirs;
-    CIRS_REQUIRE(cfg && params && grads && adam_m && adam_v && loss_out && workspace, "null argument");
+namespace cirs {
+
+struct TrainHyper { int use_ab; float lambda_ab, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps; };
+
+static int train_check_cfg(const cirs_deepfm_cfg* cfg) {
     if (cfg->hidden != tH) return fail(CIRS_E_UNSUPPORTED, "deepfm train: hidden == 64 only");
     CIRS_REQUIRE(cfg->emb_dim >= 1 && cfg->emb_dim <= 64, "emb_dim out of range");
-    CIRS_REQUIRE(n >= 1, "empty batch");
-    CIRS_REQUIRE(uid_pos && pid_pos && feats_pos && dur_pos && uid_neg && pid_neg && feats_neg && dur_neg && y && exposure, "null batch column");
-    CIRS_REQUIRE(workspace_bytes >= cirs_deepfm_train_workspace_bytes(cfg, n), "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
+    return CIRS_OK;
+}
+
+// the launches of one step on the n samples order[r0 .. r0 + n) of the columns (rows r0 .. r0 + n - 1 when order is null)
+static int train_launch_step(const cirs_deepfm_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t step_before,
+                             const TrainCols& c, const int64_t* order, long r0, long n_rows, int n, int kind, const TrainHyper& h,
+                             float* loss_out, void* workspace, hipStream_t s) {
+    const int use_ab = h.use_ab;
+    const float lambda_ab = h.lambda_ab;
     const int E = cfg->emb_dim, K = 6 * E + 1, R = 2 * n;
     const TrainLayout L = train_layout(*cfg);
     float* p = (float*)workspace;
@@ -380,8 +418,20 @@ extern "C" int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params,
     // the data gradient is written sparsely (touched table rows, dense layers): start from zero
     CIRS_HIP(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)L.total, s));
     const size_t shmem = sizeof(float) * 4 * (2 * (size_t)(K + 1 + E + 2 * tH) + tH + 6 * E + 8);
-    hipLaunchKernelGGL(train_rows_kernel, dim3(cdiv(n, 4)), dim3(256), shmem, s, *cfg, (const float*)params, uid_pos, pid_pos, feats_pos, dur_pos,
-                       uid_neg, pid_neg, feats_neg, dur_neg, y, exposure, (int)n, (int)use_ab, lambda_ab, o);
+    const dim3 grid(cdiv(n, 4));
+    switch (kind) {
+    case kLossPairwise:
+        hipLaunchKernelGGL(train_rows_kernel<kLossPairwise>, grid, dim3(256), shmem, s, *cfg, (const float*)params, c, order, r0, n_rows, n, use_ab,
+                           lambda_ab, o);
+        break;
+    case kLossIPS:
+        hipLaunchKernelGGL(train_rows_kernel<kLossIPS>, grid, dim3(256), shmem, s, *cfg, (const float*)params, c, order, r0, n_rows, n, use_ab,
+                           lambda_ab, o);
+        break;
+    default:
+        hipLaunchKernelGGL(train_rows_kernel<kLossPD>, grid, dim3(256), shmem, s, *cfg, (const float*)params, c, order, r0, n_rows, n, use_ab,
+                           lambda_ab, o);
+    }
     CIRS_CHECK_LAUNCH("train_rows_kernel");
     hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(256), 0, s, (const float*)o.LP, (int)n, lambda_ab, loss_out);
     // dense layers: dW = dY^T X over the 2n pair rows
@@ -400,16 +450,61 @@ extern "C" int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params,
     // regulariser + Adam (torch.optim.Adam, bias corrections from the step count)
     L2Segs segs;
     segs.n = 4;
-    segs.end[0] = L.lin_user;  segs.c[0] = l2_embedding + l2_all;   // embedding_dict.*            (core/user_model.py:60-63)
-    segs.end[1] = L.lm_user;   segs.c[1] = l2_all;                  // linear.*, dnn, last, out.bias, alpha_u, beta_i
-    segs.end[2] = L.total;     segs.c[2] = l2_linear + l2_all;      // linear_model.* (unused in forward, still decays)
-    segs.end[3] = L.total;     segs.c[3] = l2_linear + l2_all;
+    segs.end[0] = L.lin_user;  segs.c[0] = h.l2_embedding + h.l2_all;   // embedding_dict.*            (core/user_model.py:60-63)
+    segs.end[1] = L.lm_user;   segs.c[1] = h.l2_all;                      // linear.*, dnn, last, out.bias, alpha_u, beta_i
+    segs.end[2] = L.total;     segs.c[2] = h.l2_linear + h.l2_all;      // linear_model.* (unused in forward, still decays)
+    segs.end[3] = L.total;     segs.c[3] = h.l2_linear + h.l2_all;
     const double t = (double)(step_before + 1);
-    const float step_size = (float)((double)lr / (1.0 - pow((double)beta1, t)));
-    const float bc2s = (float)sqrt(1.0 - pow((double)beta2, t));
-    hipLaunchKernelGGL(adam_l2_kernel, dim3(kRegBlocks), dim3(256), 0, s, params, grads, adam_m, adam_v, L.total, segs, beta1, beta2, eps,
+    const float step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, t)));
+    const float bc2s = (float)sqrt(1.0 - pow((double)h.beta2, t));
+    hipLaunchKernelGGL(adam_l2_kernel, dim3(kRegBlocks), dim3(256), 0, s, params, grads, adam_m, adam_v, L.total, segs, h.beta1, h.beta2, h.eps,
                        step_size, bc2s, regp);
     hipLaunchKernelGGL(reg_final_kernel, dim3(1), dim3(256), 0, s, (const float*)regp, loss_out);
     CIRS_CHECK_LAUNCH("adam_l2_kernel");
     return CIRS_OK;
+}
+
+}  // namespace cirs
+
+extern "C" int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                                      int64_t step_before, const int64_t* uid_pos, const int64_t* pid_pos, const int32_t* feats_pos,
+                                      const float* dur_pos, const int64_t* uid_neg, const int64_t* pid_neg, const int32_t* feats_neg,
+                                      const float* dur_neg, const float* y, const float* exposure, int32_t n, int32_t use_ab,
+                                      float lambda_ab, float l2_embedding, float l2_linear, float l2_all, float lr, float beta1,
+                                      float beta2, float eps, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(cfg && params && grads && adam_m && adam_v && loss_out && workspace, "null argument");
+    if (int rc = train_check_cfg(cfg)) return rc;
+    CIRS_REQUIRE(n >= 1, "empty batch");
+    CIRS_REQUIRE(uid_pos && pid_pos && feats_pos && dur_pos && uid_neg && pid_neg && feats_neg && dur_neg && y && exposure, "null batch column");
+    CIRS_REQUIRE(workspace_bytes >= cirs_deepfm_train_workspace_bytes(cfg, n), "workspace too small");
+    const TrainCols c{uid_pos, pid_pos, feats_pos, dur_pos, uid_neg, pid_neg, feats_neg, dur_neg, y, exposure};
+    const TrainHyper h{(int)use_ab, lambda_ab, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
+    return train_launch_step(cfg, params, grads, adam_m, adam_v, step_before, c, nullptr, 0, n, n, kLossPairwise, h, loss_out, workspace,
+                             (hipStream_t)stream);
+}
+
+extern "C" int cirs_deepfm_train_epoch(const cirs_deepfm_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                                       int64_t step_before, const int64_t* uid_pos, const int64_t* pid_pos, const int32_t* feats_pos,
+                                       const float* dur_pos, const int64_t* uid_neg, const int64_t* pid_neg, const int32_t* feats_neg,
+                                       const float* dur_neg, const float* y, const float* score, int64_t n_rows, const int64_t* order,
+                                       int64_t n_order, int32_t batch_size, int32_t loss_kind, int32_t use_ab, float lambda_ab,
+                                       float l2_embedding, float l2_linear, float l2_all, float lr, float beta1, float beta2, float eps,
+                                       float* losses_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(cfg, "null argument");
+    if (int rc = train_check_cfg(cfg)) return rc;
+    CIRS_REQUIRE(loss_kind == kLossPairwise || loss_kind == kLossIPS || loss_kind == kLossPD, "deepfm train: unknown loss kind (0 pairwise, 1 IPS, 2 PD)");
+    CIRS_REQUIRE(loss_kind == kLossPairwise || !use_ab, "deepfm train: the IPS and PD losses take no alpha/beta (their models are built without ab_columns)");
+    const int64_t bmax = batch_size < n_order ? batch_size : n_order;
+    const TrainCols c{uid_pos, pid_pos, feats_pos, dur_pos, uid_neg, pid_neg, feats_neg, dur_neg, y, score};
+    const TrainHyper h{(int)use_ab, loss_kind == kLossPairwise ? lambda_ab : 0.f, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
+    return tstep::run_steps(params, grads, adam_m, adam_v, losses_out, workspace,
+                            uid_pos && pid_pos && feats_pos && dur_pos && uid_neg && pid_neg && feats_neg && dur_neg && y && score, "null data column",
+                            n_rows >= 1 && n_order >= 1 && batch_size >= 1 && (order || n_order <= n_rows), "empty data set, index array or batch",
+                            step_before, workspace_bytes, cirs_deepfm_train_workspace_bytes(cfg, (int32_t)bmax), n_order, batch_size,
+                            [&](int64_t st, int64_t r0, int nb) {
+                                return train_launch_step(cfg, params, grads, adam_m, adam_v, step_before + st, c, order, r0, n_rows, nb, loss_kind, h,
+                                                         losses_out + 5 * st, workspace, (hipStream_t)stream);
+                            });
 }

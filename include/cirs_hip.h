@@ -636,6 +636,25 @@ int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params, float* gra
                            const float* dur_neg, const float* y, const float* exposure, int32_t n, int32_t use_ab,
                            float lambda_ab, float l2_embedding, float l2_linear, float l2_all, float lr, float beta1,
                            float beta2, float eps, float* loss_out, void* workspace, int64_t workspace_bytes, void* stream);
+/* All steps of one pass over a data set that stays on the device in the column form of the step (every column n_rows long,
+ * feats [n_rows,4]): batch b is the rows order[b * batch_size .. min(n_order, (b + 1) * batch_size)) (int64, device, every entry in
+ * [0, n_rows); NULL = the identity, then n_order <= n_rows; the last batch may be short).  The row kernel reads through `order`: there
+ * is no gather launch, no host synchronisation and no host round trip between the steps; step_before advances per step.
+ * loss_kind selects the loss of the row kernel and the meaning of `score`:
+ *   0  loss_kuaishou_pairwise (score = exposure), as cirs_deepfm_train_step;
+ *   1  loss_kuaishou_IPS_pairwise (DeepFM-IPS-pairwise.py:249-258): mean((yp - y)^2 w) + mean(-log sigmoid(yp - yn) w), w = score;
+ *   2  loss_kuaishou_PD_pairwise (PD-pairwise.py:242-251): mean((yp pop - y)^2) + mean(-log sigmoid(yp - yn)), pop = score.
+ * Kinds 1 and 2 take no alpha/beta: use_ab != 0 with them is refused (both scripts build the model without ab_columns); lambda_ab
+ * is ignored.  losses_out [ceil(n_order / batch_size)][5] = per-step {loss, loss_y, bpr, loss_ab, reg_loss} (device).
+ * Kind 0 is bit-identical to one cirs_deepfm_train_step per batch on the gathered rows; a single step of kind 1 or 2 is this call with
+ * n_order = batch_size = n.  workspace: cirs_deepfm_train_workspace_bytes(cfg, min(batch_size, n_order)). */
+int cirs_deepfm_train_epoch(const cirs_deepfm_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
+                            int64_t step_before, const int64_t* uid_pos, const int64_t* pid_pos, const int32_t* feats_pos,
+                            const float* dur_pos, const int64_t* uid_neg, const int64_t* pid_neg, const int32_t* feats_neg,
+                            const float* dur_neg, const float* y, const float* score, int64_t n_rows, const int64_t* order,
+                            int64_t n_order, int32_t batch_size, int32_t loss_kind, int32_t use_ab, float lambda_ab,
+                            float l2_embedding, float l2_linear, float l2_all, float lr, float beta1, float beta2, float eps,
+                            float* losses_out, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- user-model dataset preparation ---------------------------------------------------------------
  * cirs_exposure_history replaces compute_exposure_each_user / the per-user loop of compute_exposure_effect_kuaishouRec
@@ -651,6 +670,18 @@ int cirs_exposure_history(const int64_t* user_start, const int32_t* photo, const
                           void* stream);
 int cirs_find_negative(const int64_t* user_ids, const int64_t* photo_ids, int64_t n, const uint32_t* seen_small,
                        const uint32_t* seen_big, int32_t n_items, int64_t absent_id, int64_t* neg_out, void* stream);
+/* The score columns of the debiasing baselines: the count of every item among the log rows of a time bin.
+ * cirs_item_bin_counts replaces the Series.map passes of compute_IPS_kuaishouRec (DeepFM-IPS-pairwise.py:79-86) and
+ * compute_popularity_kuaishouRec_pairwise (PD-pairwise.py:76-108): photo [n] item ids, timestamp [n] float64, bounds [num_bin + 1]
+ * float64; row r falls in bin b when bounds[b] <= ts < bounds[b + 1], the last bin closed (PD-pairwise.py:93-96).  timestamp NULL: one
+ * bin takes every row (num_bin must be 1, bounds unused).  bin_out [n] = the row's bin, -1 when no bin takes it or its item id is
+ * outside [0, n_items); counts [num_bin, n_items] int32 is cleared and filled with integer atomics (independent of the order).
+ * cirs_item_bin_gather: out[r] = table[bin[r], photo[r]] (float64 [num_bin, n_items]), 0 where bin[r] < 0.  The host turns counts
+ * into the score table with the reference's own float64 arithmetic; the device does none. */
+int cirs_item_bin_counts(const int32_t* photo, const double* timestamp, int64_t n, const double* bounds, int32_t num_bin,
+                         int32_t n_items, int32_t* bin_out, int32_t* counts, void* stream);
+int cirs_item_bin_gather(const int32_t* photo, const int32_t* bin, int64_t n, const double* table, int32_t num_bin,
+                         int32_t n_items, double* out, void* stream);
 
 /* ---- the user model as a static recommendation policy ---------------------------------------------
  * cirs_select_items replaces the tail of UserModel.recommend_k_item (reference core/user_model.py:296-346, k = 1) for n

@@ -1,5 +1,10 @@
 """Scratch probe: throughput of cirs_deepfm_train_step at the shipped model's shape (7176 x 10729, E = 16), batch 2048, and the
-torch-fp32 restatement of the same step on the host cores for comparison."""
+torch-fp32 restatement of the same step on the host cores for comparison.
+
+--epoch    per optimiser step over a resident data set of 50 batches: (a) the per-step route fit_data took before the whole-pass
+           entry (torch gathers x[idx], y[idx], score[idx] + step()), (b) epoch() for the pairwise loss, (c) epoch() for the IPS and
+           PD losses; each the median of 5 timed passes after one warm-up pass.
+--scores   ips_scores / popularity_scores on a 10^6-row synthetic log against the reference's pandas `map` formulation on the host."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cirs-codes_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -35,4 +40,56 @@ if "--cpu" in sys.argv:
     nn_oracle.deepfm_train(init, x[:5 * n], y[:5 * n], score[:5 * n], n, 5, True, 10.0)
     tc = (time.perf_counter() - t0) / 5
     out.update(cpu_us_per_step=1e6 * tc, cpu_samples_per_s=n / tc, cpu_threads=16)
+if "--epoch" in sys.argv:
+    def med(fn, reps=5):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / steps)
+        return 1e6 * float(np.median(ts))
+    order = torch.randperm(N, device="cuda")
+
+    def old_route():
+        for s0 in range(0, N, n):
+            idx = order[s0:s0 + n]
+            tr.step(xd[idx], yd[idx], sd[idx])
+    out["a_gather_step_us"] = med(old_route)
+    tr.load(xd, yd, sd)
+    out["b_epoch_pairwise_us"] = med(lambda: tr.epoch(order, n, check=False))
+    no_ab = {k: v for k, v in init.items() if not k.startswith("ab_")}
+    for kind in ("ips", "pd"):
+        tk = DeepFMTrainer(no_ab, use_ab=False, loss_kind=kind)
+        tk.load(xd, yd, sd.clamp(0.05, 1.0))
+        out[f"c_epoch_{kind}_us"] = med(lambda: tk.epoch(order, n, check=False))
+if "--scores" in sys.argv:
+    import collections
+    import pandas as pd
+    from cirs_hip.dataprep import ips_scores, popularity_scores
+    rows, items = 1_000_000, 10729
+    photo = np.minimum(rng.zipf(1.2, rows) - 1, items - 1).astype(np.int64)
+    ts = 1.6e9 + np.sort(rng.uniform(0, 5e6, rows))
+
+    def host_ips():
+        cnt = collections.Counter(photo.tolist())
+        v = pd.Series(photo).map(lambda p: cnt[p])
+        v[v < 1] = 1
+        return (1.0 / v).to_numpy()[:, None]
+
+    def host_pd(gamma=0.1, num_bin=5):
+        t = pd.Series(ts); ph = pd.Series(photo)
+        interval = (t.max() - t.min()) / num_bin
+        pop = np.zeros((rows, 1))
+        for i in range(num_bin):
+            lo, hi = interval * i + t.min(), interval * (i + 1) + t.min()
+            index = (lo <= t) & ((t < hi) if i < num_bin - 1 else (t <= hi))
+            cnt = collections.Counter(ph[index].tolist()); total = sum(cnt.values())
+            pop[index] = ph[index].map(lambda p: cnt[p] / total).to_frame()
+        return pop ** gamma
+    for name, dev_fn, host_fn in (("ips", lambda: ips_scores(photo), host_ips), ("pd", lambda: popularity_scores(photo, ts, 0.1), host_pd)):
+        dev_fn(); torch.cuda.synchronize()
+        t0 = time.perf_counter(); got = dev_fn(); torch.cuda.synchronize(); td = time.perf_counter() - t0
+        t0 = time.perf_counter(); want = host_fn(); th = time.perf_counter() - t0
+        out[f"scores_{name}_device_ms"] = 1e3 * td; out[f"scores_{name}_host_map_ms"] = 1e3 * th
+        out[f"scores_{name}_equal"] = bool(np.array_equal(got, want))
 print(json.dumps(out))
