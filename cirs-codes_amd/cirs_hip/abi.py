@@ -85,6 +85,11 @@ class DeepFMCfg(C.Structure):
                 ("emb_dim", C.c_int32), ("hidden", C.c_int32)]
 
 
+class DiceCfg(C.Structure):
+    _fields_ = [("n_user_vocab", C.c_int32), ("n_item_vocab", C.c_int32), ("n_feat_vocab", C.c_int32),
+                ("emb_dim", C.c_int32), ("hidden", C.c_int32)]
+
+
 DEEPFM_FIELDS = ("emb_user", "emb_item", "emb_feat", "lin_user", "lin_item", "lin_feat", "lin_dense", "w1", "b1", "w2", "b2",
                  "last", "out_bias")
 
@@ -325,6 +330,12 @@ SIGNATURES = {
     "cirs_deepfm_train_epoch": (C.c_int, [C.POINTER(DeepFMCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64,
                                           _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float, C.c_float, C.c_float, _P, _P, C.c_int64, _P]),
+    "cirs_dice_train_param_count": (C.c_int64, [C.POINTER(DiceCfg)]),
+    "cirs_dice_train_workspace_bytes": (C.c_int64, [C.POINTER(DiceCfg), C.c_int32]),
+    "cirs_dice_train_epoch": (C.c_int, [C.POINTER(DiceCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64,
+                                        _P, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        _P, _P, C.c_int64, _P]),
+    "cirs_dice_forward": (C.c_int, [C.POINTER(DiceCfg), _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
     "cirs_mmoe_train_param_count": (C.c_int64, [C.POINTER(MmoeTrainCfg)]),
     "cirs_mmoe_train_workspace_bytes": (C.c_int64, [C.POINTER(MmoeTrainCfg), C.c_int32]),
     "cirs_mmoe_train_step": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),

@@ -1,5 +1,5 @@
 """Assembly of the user-model training sets from the KuaiRec files (reference CIRS-UserModel-kuaishou.py:86-148,
-`load_dataset_kuaishou`; DeepFM-IPS-pairwise.py:89-146 and PD-pairwise.py:111-168 for the two debiasing baselines): positives from big_matrix.csv joined with the item categories, one sampled negative per row, the
+`load_dataset_kuaishou`; DeepFM-IPS-pairwise.py:89-146, PD-pairwise.py:111-168 and DICE.py:77-182 for the debiasing baselines): positives from big_matrix.csv joined with the item categories, one sampled negative per row, the
 exposure effect of every interaction; the two O(big) loops run on the device (core.util.negative_sampling,
 core.util.compute_exposure_effect_kuaishouRec)."""
 import json
@@ -106,4 +106,44 @@ def load_dataset_kuaishou_PD(entity_dim, feature_dim, gamma, datapath=None):
     big, _, x_columns, y_columns, _, pos_y, x_all = _training_log(entity_dim, feature_dim, datapath)
     dataset = StaticDataset(x_columns, y_columns, num_workers=4)
     dataset.compile_dataset(x_all, pos_y, popularity_scores(big["photo_id"].to_numpy(), big["timestamp"].to_numpy(), gamma))
+    return dataset, x_columns, y_columns
+
+
+def dice_feature_columns(n_user, n_photo, n_feat, entity_dim, feature_dim):
+    """The 16 input columns of the DICE model (DICE.py:119-144): interest and conformity copies of the user and the photo id, four
+    category slots sharing one table (0 = padding), duration; then the negative item's photo copies, slots and duration."""
+    def item(sfx):
+        return [SparseFeatP("photo_id_int" + sfx, n_photo, embedding_dim=entity_dim, embedding_name="photo_int"),
+                SparseFeatP("photo_id_con" + sfx, n_photo, embedding_dim=entity_dim, embedding_name="photo_con")] + \
+               [SparseFeatP(f"feat{i}{sfx}", n_feat, embedding_dim=feature_dim, embedding_name="feat", padding_idx=0) for i in range(4)] + \
+               [DenseFeat("photo_duration" + sfx, 1)]
+    return [SparseFeatP("user_id_int", n_user, embedding_dim=entity_dim, embedding_name="user_int"),
+            SparseFeatP("user_id_con", n_user, embedding_dim=entity_dim, embedding_name="user_con")] + item("") + item("_neg")
+
+
+def dice_conformity_score(photo_pos, photo_neg, photo_log):
+    """compute_popularity_kuaishouRec and the sign rule of DICE.py:77-87, 175-177: an item's popularity is its number of rows in the whole
+    log (an item the log does not hold counts 1); +1 where the positive is the more popular item, -1 otherwise (ties included).
+    -> int64 [n, 1]"""
+    photo_pos, photo_neg, photo_log = (np.asarray(a, np.int64).reshape(-1) for a in (photo_pos, photo_neg, photo_log))
+    count = np.bincount(photo_log, minlength=int(max(photo_pos.max(), photo_neg.max())) + 1)
+    pop_pos, pop_neg = np.maximum(count[photo_pos], 1), np.maximum(count[photo_neg], 1)
+    return np.where(pop_pos > pop_neg, 1, -1).astype(np.int64)[:, None]
+
+
+def load_dataset_kuaishou_DICE(entity_dim, feature_dim, datapath=None):
+    """The training set of DICE.py:90-182: the user and the photo id of the positive row in an interest and a conformity column each, the
+    sampled negative's photo id likewise, and the conformity score of the pair as the score column.
+    -> (StaticDataset, x_columns, y_columns)"""
+    datapath = DATAPATH if datapath is None else datapath
+    big, _, _, y_columns, pos_x, pos_y, x_all = _training_log(entity_dim, feature_dim, datapath)
+    _, df_feat = item_feature_table(datapath)
+    x_columns = dice_feature_columns(big["user_id"].max() + 1, big["photo_id"].max() + 1, df_feat.max().max() + 1, entity_dim, feature_dim)
+    item = ["feat0", "feat1", "feat2", "feat3", "photo_duration"]
+    x16 = pd.concat([x_all[["user_id", "user_id", "photo_id", "photo_id"] + item],
+                     x_all[["photo_id_neg", "photo_id_neg"] + [c + "_neg" for c in item]]], axis=1)
+    x16.columns = [c.name for c in x_columns]
+    score = dice_conformity_score(pos_x["photo_id"].to_numpy(), x_all["photo_id_neg"].to_numpy(), big["photo_id"].to_numpy())
+    dataset = StaticDataset(x_columns, y_columns, num_workers=4)
+    dataset.compile_dataset(x16, pos_y, score)
     return dataset, x_columns, y_columns

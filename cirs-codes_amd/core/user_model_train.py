@@ -109,6 +109,42 @@ def train_debias_kuaishou(datapath, method="ips", save_root=".", callbacks=None,
                            lbe_user=lbe_user, lbe_photo=lbe_photo)
 
 
+DICE_DEFAULTS = dict(env="KuaishouEnv-v0", user_model_name="DICE", message="DICE", feature_dim=16, dnn=(64, 64), l2_reg_dnn=0.1, batch_size=2048,
+                     epoch=50, lr=1e-3, seed=2021)
+
+
+def train_dice_kuaishou(datapath, save_root=".", callbacks=None, rl_test=None, **overrides):
+    """The training run of the DICE baseline (DICE.py:185-261, `main`): KuaiRec files -> the 16-column training set with the conformity
+    score (core.user_data.load_dataset_kuaishou_DICE) -> UserModel_DICE fitted on the device with loss_kuaishou_DICE.  rl_test(model) ->
+    dict goes through compile_RL_test, like the script's partial of test_static_model_in_RL_env: it is called on the untrained model
+    (epoch -1) and after every epoch, its results joining the epoch's logs.  Like the script, the run writes one artefact, the
+    constructor parameters (`<name>_params_<msg>.pickle`).
+    Returns SimpleNamespace(model, history, paths, train_set, val_set, lbe_user, lbe_photo)."""
+    from core.user_data import load_dataset_kuaishou_DICE
+    from core.user_model_DICE import UserModel_DICE, loss_kuaishou_DICE
+    a = SimpleNamespace(**{**DICE_DEFAULTS, **overrides})
+    entity_dim = a.feature_dim
+    model_dir = os.path.join(save_root, "saved_models", a.env, a.user_model_name)
+    os.makedirs(os.path.join(model_dir, "logs"), exist_ok=True)
+
+    mat, lbe_user, lbe_photo, list_feat, df_photo_env, df_dist_small = KuaishouEnv.load_mat(datapath)
+    train_set, x_columns, y_columns = load_dataset_kuaishou_DICE(entity_dim, a.feature_dim, datapath=datapath)
+    val_set = load_static_validate_data_kuaishou(entity_dim, a.feature_dim, datapath)
+
+    params = {"feature_columns": x_columns, "y_columns": y_columns, "task": "regression", "task_logit_dim": 1,
+              "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cuda"}
+    model = UserModel_DICE(l2_reg_dnn=a.l2_reg_dnn, **params)
+    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=loss_kuaishou_DICE)
+    if rl_test is not None:
+        model.compile_RL_test(rl_test)
+
+    history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []))
+    paths = SimpleNamespace(params=os.path.join(model_dir, "{}_params_{}.pickle".format(a.user_model_name, a.message)))
+    with open(paths.params, "wb") as fh:
+        pickle.dump(dict(params, device="cpu"), fh)
+    return SimpleNamespace(model=model, history=history, paths=paths, train_set=train_set, val_set=val_set, lbe_user=lbe_user, lbe_photo=lbe_photo)
+
+
 TAOBAO_DEFAULTS = dict(env="VirtualTB-v0", user_model_name="MLP", message="UM", tau=0.01, feature_dim=8, dnn=(64, 64), batch_size=100,
                        epoch=5, seed=2022)
 

@@ -1,0 +1,135 @@
+// table_step.h -- the back half of an optimiser step over embedding tables, shared by the Kuaishou trainers (deepfm_train.hip: the
+// pairwise / IPS / PD DeepFM; dice_train.hip: the DICE model).  Each trainer keeps its own row kernel and per-row contribution tables;
+// what follows them exists once, here:
+//   train_scatter       stable radix sort of (key, row) + ordered segment sums (no float atomics) of a contribution table [R, W] into up
+//                       to three destination tables, each taking a column range of the contribution row; a destination either takes the
+//                       segment sum (the gradient buffer starts from zero) or, marked `add`, adds it to what an earlier pass left.
+//   adam_l2_kernel      g += 2 * l2_c * p (the regulariser is dense: every row of every table decays), Adam, and the regulariser's
+//                       value as per-workgroup partials; reg_final_kernel sums them in index order into one slot of the loss vector.
+// Every sum has a fixed order: two runs give identical bits.
+#pragma once
+#include <hipcub/hipcub.hpp>
+
+#include "common.h"
+
+namespace cirs {
+// ---- sorted scatter: contributions [R, W] keyed by row id -> up to three destination tables -----------------------
+static __global__ __launch_bounds__(256) void train_keys_kernel(const int32_t* __restrict__ keys, int R, int n_table, uint32_t* __restrict__ k_out,
+                                                         int32_t* __restrict__ rows) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int32_t k = keys[r];
+    k_out[r] = (k < 0 || k >= n_table) ? (uint32_t)n_table : (uint32_t)k;
+    rows[r] = r;
+}
+
+struct ScatterDst { float* p[3]; int w[3]; int add[3]; };  // column ranges of the contribution row -> table [n_table, w] each; add: += instead of =
+
+static __global__ __launch_bounds__(256) void train_segment_sum_kernel(const uint32_t* __restrict__ ks, const int32_t* __restrict__ rs,
+                                                                const float* __restrict__ contrib, int R, int W, int n_table, ScatterDst dst) {
+    const int l = threadIdx.x & 31;
+    const int pth = blockIdx.x * 8 + (threadIdx.x >> 5);
+    if (pth >= R) return;
+    const uint32_t key = ks[pth];
+    if (key >= (uint32_t)n_table || (pth > 0 && ks[pth - 1] == key)) return;  // not a segment head
+    // segment length once (the 32 lanes scan cooperatively), then every lane streams its columns with 16 loads in flight
+    int len = 0;
+    for (int base = pth; base < R; base += 32) {
+        const bool same = base + l < R && ks[base + l] == key;
+        const unsigned long long m = __ballot(same) >> ((threadIdx.x & 32) ? 32 : 0) & 0xFFFFFFFFull;
+        const int run = m == 0xFFFFFFFFull ? 32 : __builtin_ctzll(~m);
+        len += run;
+        if (run < 32) break;
+    }
+    for (int d = l; d < W; d += 32) {
+        float acc = 0.f;
+        for (int q0 = 0; q0 < len; q0 += 16) {
+            float t16[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) t16[u] = (q0 + u < len) ? contrib[(size_t)rs[pth + q0 + u] * W + d] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) acc += t16[u];      // rows ascend inside a key: fixed order
+        }
+        int c = d;
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            if (dst.p[t] && c < dst.w[t]) {
+                float* out = dst.p[t] + (size_t)key * dst.w[t] + c;
+                *out = dst.add[t] ? *out + acc : acc;
+                break;
+            }
+            c -= dst.w[t];
+        }
+    }
+}
+
+static size_t train_sort_bytes(long R) { return (size_t)R * 64 + (1u << 20); }
+
+static int train_scatter(const int32_t* keys, const float* contrib, int R, int W, int n_table, const ScatterDst& dst, void* scratch,
+                         size_t scratch_bytes, hipStream_t s) {
+    uint32_t* k_in = (uint32_t*)scratch;
+    uint32_t* k_out = k_in + R;
+    int32_t* r_in = (int32_t*)(k_out + R);
+    int32_t* r_out = r_in + R;
+    char* temp = (char*)(((uintptr_t)(r_out + R) + 255) & ~(uintptr_t)255);
+    const size_t avail = scratch_bytes - (size_t)(temp - (char*)scratch);
+    int end_bit = 1;
+    while ((1u << end_bit) <= (uint32_t)n_table && end_bit < 32) ++end_bit;
+    size_t need = 0;
+    CIRS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k_in, k_out, r_in, r_out, R, 0, end_bit, s));
+    CIRS_REQUIRE(need <= avail, "train scatter: sort scratch too small");
+    hipLaunchKernelGGL(train_keys_kernel, dim3(cdiv(R, 256)), dim3(256), 0, s, keys, R, n_table, k_in, r_in);
+    CIRS_HIP(hipcub::DeviceRadixSort::SortPairs(temp, need, k_in, k_out, r_in, r_out, R, 0, end_bit, s));
+    hipLaunchKernelGGL(train_segment_sum_kernel, dim3(cdiv(R, 8)), dim3(256), 0, s, k_out, r_out, contrib, R, W, n_table, dst);
+    CIRS_CHECK_LAUNCH("train_segment_sum_kernel");
+    return CIRS_OK;
+}
+
+// ---- regulariser + Adam over the whole flat buffer ----------------------------------------------------------------
+struct L2Segs { long end[6]; float c[6]; int n; };  // element i belongs to the first segment with i < end
+
+constexpr int kRegBlocks = 1024;
+static __global__ __launch_bounds__(256) void adam_l2_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                      long n, L2Segs segs, float beta1, float beta2, float eps, float step_size, float bc2s,
+                                                      float* __restrict__ reg_partial) {
+    __shared__ float sh[256];
+    const int tid = threadIdx.x;
+    float reg = 0.f;
+    for (long i = blockIdx.x * 256L + tid; i < n; i += (long)kRegBlocks * 256) {
+        float c = segs.c[segs.n - 1];
+#pragma unroll
+        for (int q = 5; q >= 0; --q)
+            if (q < segs.n && i < segs.end[q]) c = segs.c[q];
+        const float pi = p[i];
+        reg = __builtin_fmaf(c * pi, pi, reg);
+        const float gi = __builtin_fmaf(2.0f * c, pi, g[i]);   // d/dp of c * p^2 joins the data gradient
+        g[i] = gi;
+        const float mi = m[i] + (1.0f - beta1) * (gi - m[i]);
+        const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
+        m[i] = mi; v[i] = vi;
+        p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
+    }
+    sh[tid] = reg;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) reg_partial[blockIdx.x] = sh[0];
+}
+
+static __global__ __launch_bounds__(256) void reg_final_kernel(const float* __restrict__ part, float* __restrict__ loss_out, int slot) {
+    __shared__ float sh[256];
+    const int tid = threadIdx.x;
+    float t = 0.f;
+    for (int q = tid; q < kRegBlocks; q += 256) t += part[q];
+    sh[tid] = t;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) loss_out[slot] = sh[0];
+}
+
+}  // namespace cirs

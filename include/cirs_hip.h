@@ -656,6 +656,57 @@ int cirs_deepfm_train_epoch(const cirs_deepfm_cfg* cfg, float* params, float* gr
                             float l2_embedding, float l2_linear, float l2_all, float lr, float beta1, float beta2, float eps,
                             float* losses_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the DICE debiasing baseline (UserModel_DICE) ------------------------------------------------------------------
+ * replaces  core/user_model_DICE.py:122-160 (_deepfm), :162-187 (get_loss), :189-192 (forward), DICE.py:273-286 (loss_kuaishou_DICE),
+ *           core/user_model.py:401-417 (get_regularization_loss) and the inner loop of fit_data (core/user_model.py:150-170).
+ * Two DeepFM networks over five shared embedding tables (entity_dim == feature_dim == E):
+ *   main  fields [user_int, user_con, photo_int, photo_con, feat0..3] + duration: linear_main + FM over 8 fields + dnn_main -> last_main
+ *         + out_main.bias; run on the positive row and on the negative row (same user ids, the negative item's columns);
+ *   ui    fields (user, photo): linear_ui + FM over 2 fields + dnn_ui -> last_ui + out_ui.bias; run on (user_int, photo_int) and on
+ *         (user_con, photo_con), positive and negative item each.  linear_ui has the tables user_int / photo_int only and is indexed
+ *         with the ids of the call's own columns (the con ids in the con calls), as the reference does.
+ * loss = mean((yp - y)^2) + mean(-log sigmoid(yp - yn)) + mean(-log sigmoid(yp_con - yn_con) s) + mean(-log sigmoid(yp_int - yn_int) [s < 0]),
+ * s = score in {+1, -1}.
+ * Parameters, gradients and the two Adam moments are flat fp32 buffers of cirs_dice_train_param_count(cfg) floats in the order
+ *   embedding_dict.{user_int [U,E] | user_con [U,E] | photo_int [I,E] | photo_con [I,E] | feat [F,E]}
+ * | linear_main.embedding_dict.{user_int [U] | user_con [U] | photo_int [I] | photo_con [I] | feat [F]} | linear_main.weight [1]
+ * | linear_ui.embedding_dict.{user_int [U] | photo_int [I]}
+ * | dnn_main.linears.0 [64,8E+1],[64] | dnn_main.linears.1 [64,64],[64] | last_main [64] | out_main.bias [1]
+ * | dnn_ui.linears.0 [64,2E],[64] | dnn_ui.linears.1 [64,64],[64] | last_ui [64] | out_ui.bias [1]
+ * | linear_model.embedding_dict.{user_int [U] | user_con [U] | photo_int [I] | photo_con [I] | feat [F]} | linear_model.weight [2]
+ *   (the base class's unused copy: no data gradient, decayed by l2_linear + l2_all).
+ * emb_dim in {8, 16, 32}, hidden == 64.  Row 0 of embedding_dict.feat (padding_idx) gets no data gradient. */
+typedef struct cirs_dice_cfg {
+    int32_t n_user_vocab, n_item_vocab, n_feat_vocab;
+    int32_t emb_dim; /* E */
+    int32_t hidden;  /* 64 */
+} cirs_dice_cfg;
+
+int64_t cirs_dice_train_param_count(const cirs_dice_cfg* cfg);
+int64_t cirs_dice_train_workspace_bytes(const cirs_dice_cfg* cfg, int32_t n);
+/* All steps of one pass over a data set resident on the device in column form, like cirs_deepfm_train_epoch: the 16 columns of the
+ * reference's x as uid_int, uid_con, pid_int, pid_con, feats_pos [n_rows,4], dur_pos | pid_int_neg, pid_con_neg, feats_neg [n_rows,4],
+ * dur_neg (the int and con id columns are separate arguments and need not be equal), then y and score.  Batch b is the rows
+ * order[b * batch_size .. min(n_order, (b + 1) * batch_size)) (int64, device; NULL = the identity, then n_order <= n_rows), read by the
+ * row kernel itself; an entry outside [0, n_rows) is not read and turns that step's loss into NaN.  The steps are queued back to back
+ * without a host round trip; step_before advances per step.  losses_out [ceil(n_order / batch_size)][6] = per-step
+ * {loss, loss_y, bpr_click, bpr_con, bpr_int, reg_loss} (device).  A single step is this call with n_order = batch_size = n.
+ * Every sum has a fixed order (no float atomics): two runs give identical bits.
+ * Precondition, as for cirs_deepfm_train_epoch: every id of the data set lies inside its table (user ids in [0, n_user_vocab), photo ids in
+ * [0, n_item_vocab), feat ids in [0, n_feat_vocab)); the row kernel indexes the tables with them unchecked (DiceTrainer.load checks once).
+ * workspace: cirs_dice_train_workspace_bytes(cfg, min(batch_size, n_order)). */
+int cirs_dice_train_epoch(const cirs_dice_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t step_before,
+                          const int64_t* uid_int, const int64_t* uid_con, const int64_t* pid_int, const int64_t* pid_con,
+                          const int32_t* feats_pos, const float* dur_pos, const int64_t* pid_int_neg, const int64_t* pid_con_neg,
+                          const int32_t* feats_neg, const float* dur_neg, const float* y, const float* score, int64_t n_rows,
+                          const int64_t* order, int64_t n_order, int32_t batch_size, float l2_embedding, float l2_linear, float l2_all,
+                          float lr, float beta1, float beta2, float eps, float* losses_out, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+/* UserModel_DICE.forward on n rows (uid, pid, feats [n,4], dur): the main DeepFM with the user and the photo id in both of their
+ * columns, over the flat parameter buffer above.  A row with an id outside its table is not read and gives NaN. */
+int cirs_dice_forward(const cirs_dice_cfg* cfg, const float* params, const int64_t* uid, const int64_t* pid, const int32_t* feats,
+                      const float* dur, int64_t n, float* out, void* stream);
+
 /* ---- user-model dataset preparation ---------------------------------------------------------------
  * cirs_exposure_history replaces compute_exposure_each_user / the per-user loop of compute_exposure_effect_kuaishouRec
  * (reference core/util.py:56-76,135-169): rows are the logged interactions in file order, a user's rows contiguous;

@@ -4,7 +4,10 @@ torch-fp32 restatement of the same step on the host cores for comparison.
 --epoch    per optimiser step over a resident data set of 50 batches: (a) the per-step route fit_data took before the whole-pass
            entry (torch gathers x[idx], y[idx], score[idx] + step()), (b) epoch() for the pairwise loss, (c) epoch() for the IPS and
            PD losses; each the median of 5 timed passes after one warm-up pass.
---scores   ips_scores / popularity_scores on a 10^6-row synthetic log against the reference's pandas `map` formulation on the host."""
+--scores   ips_scores / popularity_scores on a 10^6-row synthetic log against the reference's pandas `map` formulation on the host.
+--dice     per optimiser step of the DICE baseline over a resident data set of 50 batches: DiceTrainer.epoch() against the same steps
+           in plain torch on the same GPU (the loop of dice_host.torch_train on device tensors: autograd + torch.optim.Adam, parameters and
+           optimiser built once outside the timed passes, losses kept on the device); each the median of 5 timed passes after one warm-up pass, device first and torch second, then both once more."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cirs-codes_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -92,4 +95,47 @@ if "--scores" in sys.argv:
         t0 = time.perf_counter(); want = host_fn(); th = time.perf_counter() - t0
         out[f"scores_{name}_device_ms"] = 1e3 * td; out[f"scores_{name}_host_map_ms"] = 1e3 * th
         out[f"scores_{name}_equal"] = bool(np.array_equal(got, want))
+if "--dice" in sys.argv:
+    from cirs_hip import dice_host, dice_train
+    dinit = {name: rng.normal(0, 0.05, shape).astype(np.float32) for name, shape in dice_train.layout(U, I, F, E)}
+    dinit["embedding_dict.feat.weight"][0] = 0
+    x16 = np.concatenate([col(rng.randint(0, U, N)), col(rng.randint(0, U, N)), col(rng.randint(0, I, N)), col(rng.randint(0, I, N)), feats(),
+                          col(rng.uniform(2, 60, N)), col(rng.randint(0, I, N)), col(rng.randint(0, I, N)), feats(), col(rng.uniform(2, 60, N))], axis=1)
+    s16 = np.where(rng.uniform(size=(N, 1)) < 0.5, 1.0, -1.0)
+    x16d, s16d = torch.as_tensor(x16, dtype=torch.float32).cuda(), torch.as_tensor(s16, dtype=torch.float32).cuda()
+    order = torch.randperm(N, device="cuda")
+    td = dice_train.DiceTrainer(dinit)
+    td.load(x16d, yd, s16d)
+    # plain torch on the same GPU: parameters, torch.optim.Adam and the order live outside the timed region, like the device trainer's; the
+    # timed pass is the statements of dice_host.torch_train's loop, the per-step losses kept on the device
+    tp = {k: torch.as_tensor(v).cuda().requires_grad_(True) for k, v in dinit.items()}
+    topt = torch.optim.Adam(list(tp.values()), lr=1e-3)
+    y1, s1, feat = yd.reshape(-1), s16d.reshape(-1), "embedding_dict.feat.weight"
+
+    def torch_fn():
+        losses = []
+        for s0 in range(0, N, n):
+            idx = order[s0:s0 + n]
+            terms = dice_host.get_loss(tp, x16d[idx], y1[idx], s1[idx])
+            loss = terms[0] + terms[1] + terms[2] + terms[3]
+            reg = dice_host.regulariser(tp)
+            topt.zero_grad()
+            (loss + reg).backward()
+            tp[feat].grad[0] = 2 * (0.1 + 1e-5) * tp[feat].detach()[0]
+            topt.step()
+            losses.append(torch.stack([v.detach() for v in (loss,) + terms + (reg,)]))
+        return torch.stack(losses)
+
+    def med(fn, reps=5):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / steps)
+        return 1e6 * float(np.median(ts))
+    dev_fn = lambda: td.epoch(order, n, check=False)
+    d1, t1 = med(dev_fn), med(torch_fn)
+    d2, t2 = med(dev_fn), med(torch_fn)
+    out.update(dice_epoch_us=min(d1, d2), dice_torch_us=min(t1, t2), dice_epoch_us_runs=[d1, d2], dice_torch_us_runs=[t1, t2],
+               dice_speedup=min(t1, t2) / min(d1, d2))
 print(json.dumps(out))
