@@ -336,6 +336,10 @@ SIGNATURES = {
                                         _P, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                         _P, _P, C.c_int64, _P]),
     "cirs_dice_forward": (C.c_int, [C.POINTER(DiceCfg), _P, _P, _P, _P, _P, C.c_int64, _P, _P]),
+    "cirs_deepfm_validate_workspace_bytes": (C.c_int64, [C.POINTER(DeepFMCfg), C.c_int64]),
+    "cirs_deepfm_validate": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "cirs_dice_validate_workspace_bytes": (C.c_int64, [C.POINTER(DiceCfg), C.c_int64]),
+    "cirs_dice_validate": (C.c_int, [C.POINTER(DiceCfg), _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "cirs_mmoe_train_param_count": (C.c_int64, [C.POINTER(MmoeTrainCfg)]),
     "cirs_mmoe_train_workspace_bytes": (C.c_int64, [C.POINTER(MmoeTrainCfg), C.c_int32]),
     "cirs_mmoe_train_step": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),

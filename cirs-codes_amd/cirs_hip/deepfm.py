@@ -75,6 +75,12 @@ class DeviceDeepFM:
                                               ws.data_ptr(), ws.numel(), self._stream()), "cirs_deepfm_sweep")
         return pred, mm
 
+    def validate(self, valset, want_pred=False, want_sums=True):
+        """The validation pass (cirs_deepfm_validate) over a cirs_hip.userval.ValSet -> (pred [n] fp32 or None, float64 device pair
+        {sum |pred - y|, sum (pred - y)^2} or None)."""
+        from .userval import deepfm_validate
+        return deepfm_validate(self.cfg, self.w, valset, want_pred, want_sums)
+
     def normed_reward(self, user_ids, item_ids, item_feats, item_dur):
         """KuaishouEnv.compute_normed_reward: float64 (pred - min) / (max - min) over all users x items."""
         pred, mm = self.sweep(user_ids, item_ids, item_feats, item_dur)

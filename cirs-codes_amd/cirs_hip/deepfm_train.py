@@ -90,6 +90,15 @@ class DeepFMTrainer:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
+    def validate(self, valset, want_pred=False, want_sums=True):
+        """The validation pass (cirs_deepfm_validate) of the LIVE parameters over a cirs_hip.userval.ValSet: the weights struct points
+        into the flat buffer's views -> (pred or None, sums or None)."""
+        from .deepfm import STATE_DICT_MAP
+        from .userval import deepfm_validate
+        if getattr(self, "_val_w", None) is None:
+            self._val_w = abi.DeepFMWeights(**{f: self.views[k].data_ptr() for k, f in STATE_DICT_MAP.items()})
+        return deepfm_validate(self.cfg, self._val_w, valset, want_pred, want_sums)
+
     def _hyper(self):
         return (int(self.use_ab), self.lambda_ab, *self.l2, self.lr, self.betas[0], self.betas[1], self.eps)
 

@@ -122,6 +122,11 @@ class DiceTrainer:
         self.step_count += steps
         return losses
 
+    def validate(self, valset, want_pred=False, want_sums=True):
+        """The validation pass (cirs_dice_validate) of the LIVE parameters over a cirs_hip.userval.ValSet -> (pred or None, sums or None)."""
+        from .userval import dice_validate
+        return dice_validate(self.cfg, self.flat, valset, want_pred, want_sums)
+
     def step(self, x, y, score):
         """One optimiser step on the batch x [n,16], y, score [n] or [n,1] (a pass of one batch over these rows).  Returns the device loss
         vector {loss, loss_y, bpr_click, bpr_con, bpr_int, reg}."""
@@ -176,6 +181,12 @@ class DeviceDice:
         abi.check(self._lib.cirs_dice_forward(C.byref(self.cfg), self.flat.data_ptr(), uid.data_ptr(), pid.data_ptr(), feats.data_ptr(),
                                               dur.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "cirs_dice_forward")
         return out
+
+    def validate(self, valset, want_pred=False, want_sums=True):
+        """The validation pass (cirs_dice_validate) over a cirs_hip.userval.ValSet -> (pred [n] fp32 or None, float64 device pair
+        {sum |pred - y|, sum (pred - y)^2} or None)."""
+        from .userval import dice_validate
+        return dice_validate(self.cfg, self.flat, valset, want_pred, want_sums)
 
     def sweep(self, user_ids, item_ids, item_feats, item_dur, want_pred=True):
         """All (user, item) pairs -> (pred [nu, ni] fp32, minmax [2]): cirs_dice_forward over the nu * ni pairs, a block of users per call."""

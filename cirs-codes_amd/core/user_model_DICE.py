@@ -3,7 +3,8 @@ embeddings of user and item and a second DeepFM shared by the interest pair and 
 device (cirs_hip.dice_train: cirs_dice_train_epoch, cirs_dice_forward).
 
 Constructor call, state_dict names and shapes are the reference's, so its checkpoints load.  recommend_k_item comes from
-core.user_model.UserModel and runs over device_model() (cirs_hip.dice_train.DeviceDice)."""
+core.user_model.UserModel and runs over device_model() (cirs_hip.dice_train.DeviceDice); so do compile_RL_test, fit_data, predict_data and
+evaluate_data (the trainer is cirs_hip.dice_train.DiceTrainer, the validation pass cirs_dice_validate)."""
 import torch
 from torch import nn
 
@@ -115,10 +116,6 @@ class UserModel_DICE(UserModel):
         return y if score is None else y * torch.as_tensor(score).to(y.device, y.dtype)
 
     # ---- training (reference core/user_model.py:71-170) -----------------------------------------------------------------------
-    def compile_RL_test(self, RL_eval_fun):
-        """reference core/user_model.py:71-72: fit_data evaluates fn(self.eval()) before training and after every epoch."""
-        self.RL_eval_fun = RL_eval_fun
-
     def compile(self, optimizer, loss_dict=None, metrics=None, metric_fun=None, loss_func=None):
         assert optimizer == "adam" or isinstance(optimizer, torch.optim.Adam), "the device step implements torch.optim.Adam"
         assert getattr(loss_func, "loss_kind", None) == "dice", \
@@ -128,47 +125,8 @@ class UserModel_DICE(UserModel):
         self.optim = "adam"
         self._lr = optimizer.param_groups[0]["lr"] if isinstance(optimizer, torch.optim.Adam) else 1e-3
 
-    def _publish(self):
-        """The trained parameters into the module, under its state_dict names."""
-        with torch.no_grad():
-            mine = dict(self.named_parameters())
-            for k, v in self._trainer.state_dict().items():
-                mine[k].copy_(v.reshape(mine[k].shape).to(mine[k].device))
-        self._dev = None
-
-    def fit_data(self, dataset_train, dataset_val=None, batch_size=256, epochs=1, verbose=1, initial_epoch=0, callbacks=None, shuffle=True):
-        """One pass per epoch over (x, y, score) minibatches, the last one short: the data set is made resident on the device once, every
-        epoch is one cirs_dice_train_epoch call over the permutation drawn here, and the losses are read back once per epoch.  With
-        compile_RL_test set, its results join the logs of epoch -1 (the untrained model) and of every epoch."""
+    def _new_trainer(self):
         from cirs_hip.dice_train import DiceTrainer
-        assert self.optim is not None, "call compile() first"
-        if self._trainer is None:
-            self._trainer = DiceTrainer(self.state_dict(), l2_embedding=self._l2[0], l2_linear=self._l2[1], l2_all=self._l2[2], lr=self._lr)
-        tr = self._trainer
-        n_all = tr.load(dataset_train.x_numpy, dataset_train.y_numpy, dataset_train.score)
-        callbacks = callbacks or []
-        for cb in callbacks:
-            cb.on_train_begin()
-        if self.RL_eval_fun:             # core/user_model.py:129-135
-            logs = dict(self.RL_eval_fun(self.eval()))
-            for cb in callbacks:
-                cb.on_epoch_end(-1, logs)
-        history = []
-        for epoch in range(initial_epoch, epochs):
-            for cb in callbacks:
-                cb.on_epoch_begin(epoch)
-            order = torch.randperm(n_all, device=tr.device) if shuffle else None
-            lo = tr.epoch(order, batch_size, check=False)
-            loss_sum = float((lo[:, 0] + lo[:, 5]).double().sum())     # the fp32 step totals summed in float64, like `+= total_loss.item()`
-            logs = {"loss": loss_sum / n_all}              # total_loss_epoch / sample_num (core/user_model.py:205)
-            if self.RL_eval_fun:         # core/user_model.py:215-219
-                self._publish()
-                for name, result in self.RL_eval_fun(self.eval()).items():
-                    logs[name] = result
-            history.append(logs)
-            for cb in callbacks:
-                cb.on_epoch_end(epoch, logs)
-        for cb in callbacks:
-            cb.on_train_end()
-        self._publish()
-        return history
+        return DiceTrainer(self.state_dict(), l2_embedding=self._l2[0], l2_linear=self._l2[1], l2_all=self._l2[2], lr=self._lr)
+
+    _loss_columns = (0, 5)      # {loss, reg_loss} of cirs_dice_train_epoch's per-step rows; fit_data itself is the base class's

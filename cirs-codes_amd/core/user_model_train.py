@@ -29,6 +29,22 @@ class _RLTest:   # epoch-end hook in the position of compile_RL_test
             logs["RL_val"] = self.rl_test(self.model, epoch)
 
 
+class EpochLines:
+    """Callback that keeps (epoch, logs) of every on_epoch_end call, epoch -1 (the untrained model) included, and prints one line per
+    call in the manner of the scripts' LoggerCallback_Update."""
+    def __init__(self, echo=True):
+        self.records, self.echo = [], echo
+
+    def on_train_begin(self): pass
+    def on_train_end(self): pass
+    def on_epoch_begin(self, epoch): pass
+
+    def on_epoch_end(self, epoch, logs):
+        self.records.append((epoch, dict(logs)))
+        if self.echo:
+            print("Epoch: [{}], Info: [{}]".format(epoch, logs), flush=True)
+
+
 def _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set):
     """The three files the RL script loads: constructor parameters, the normalised reward table, the state dict (on the CPU)."""
     paths = SimpleNamespace(params=os.path.join(model_dir, "{}_params_{}.pickle".format(a.user_model_name, a.message)),
@@ -43,9 +59,12 @@ def _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set):
     return paths, normed_mat
 
 
-def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, **overrides):
+def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, metric_fun=None, **overrides):
     """Returns SimpleNamespace(model, history, normed_mat, paths).  rl_test(model, epoch) (optional) is called after every epoch,
-    the place of the reference's compile_RL_test hook (e.g. a partial of evaluation.test_static_model_in_RL_env)."""
+    the place of the reference's compile_RL_test hook (e.g. a partial of evaluation.test_static_model_in_RL_env); a hook of the
+    reference's own shape, fn(model) -> dict, goes through `model.compile_RL_test` by the caller instead.  metric_fun: the script's
+    {"mae": ..., "mse": ...} (core.user_model.metric_mae / metric_mse run fused on the device): evaluated on the validation set before
+    training (epoch -1 of the callbacks) and after every epoch, into the epoch's logs; None keeps the logs at {"loss"}."""
     a = SimpleNamespace(**{**DEFAULTS, **overrides})
     entity_dim = a.feature_dim
     model_dir = os.path.join(save_root, "saved_models", a.env, a.user_model_name)
@@ -60,7 +79,7 @@ def train_user_model(datapath, save_root=".", callbacks=None, rl_test=None, **ov
     params = {"feature_columns": x_columns, "y_columns": y_columns, "task": "regression", "task_logit_dim": 1,
               "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cuda", "ab_columns": ab_columns}
     model = UserModel_Pairwise(l2_reg_dnn=a.l2_reg_dnn, **params)
-    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=make_loss_kuaishou_pairwise(a.lambda_ab))
+    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=make_loss_kuaishou_pairwise(a.lambda_ab), metric_fun=metric_fun)
 
     history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [_RLTest(model, rl_test)])
 
@@ -74,10 +93,10 @@ DEBIAS_DEFAULTS = dict(env="KuaishouEnv-v0", feature_dim=16, dnn=(64, 64), l2_re
 DEBIAS_NAMES = {"ips": "DeepFM-IPS-pairwise", "pd": "PD-pairwise"}
 
 
-def train_debias_kuaishou(datapath, method="ips", save_root=".", callbacks=None, rl_test=None, **overrides):
+def train_debias_kuaishou(datapath, method="ips", save_root=".", callbacks=None, rl_test=None, metric_fun=None, **overrides):
     """The training runs of the two debiasing baselines (DeepFM-IPS-pairwise.py:149-239, PD-pairwise.py:171-238, `main`): KuaiRec files
     -> training set with the method's score column (core.user_data) -> UserModel_Pairwise without alpha/beta fitted on the device with
-    the method's loss.  rl_test(model, epoch) sits where the scripts' compile_RL_test hook sits.  "ips" writes the three artefacts its
+    the method's loss.  rl_test(model, epoch) sits where the scripts' compile_RL_test hook sits, metric_fun as in train_user_model.  "ips" writes the three artefacts its
     script writes (`<name>_params_<msg>.pickle`, `normed_mat-<msg>.pickle`, `<name>_<msg>.pt`); "pd", like its script, writes none.
     Returns SimpleNamespace(model, history, normed_mat, paths, val_set, lbe_user, lbe_photo), normed_mat and paths None for "pd"."""
     from core.user_data import load_dataset_kuaishou_IPS_pairwise, load_dataset_kuaishou_PD
@@ -101,7 +120,7 @@ def train_debias_kuaishou(datapath, method="ips", save_root=".", callbacks=None,
               "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cuda"}
     model = UserModel_Pairwise(l2_reg_dnn=a.l2_reg_dnn, **params)
     model.compile(torch.optim.Adam(model.parameters(), lr=a.lr),
-                  loss_func=loss_kuaishou_IPS_pairwise if method == "ips" else loss_kuaishou_PD_pairwise)
+                  loss_func=loss_kuaishou_IPS_pairwise if method == "ips" else loss_kuaishou_PD_pairwise, metric_fun=metric_fun)
 
     history = model.fit_data(train_set, val_set, batch_size=a.batch_size, epochs=a.epoch, callbacks=list(callbacks or []) + [_RLTest(model, rl_test)])
     paths, normed_mat = _write_artefacts(model, params, a, model_dir, lbe_user, lbe_photo, val_set) if method == "ips" else (None, None)
@@ -113,11 +132,12 @@ DICE_DEFAULTS = dict(env="KuaishouEnv-v0", user_model_name="DICE", message="DICE
                      epoch=50, lr=1e-3, seed=2021)
 
 
-def train_dice_kuaishou(datapath, save_root=".", callbacks=None, rl_test=None, **overrides):
+def train_dice_kuaishou(datapath, save_root=".", callbacks=None, rl_test=None, metric_fun=None, **overrides):
     """The training run of the DICE baseline (DICE.py:185-261, `main`): KuaiRec files -> the 16-column training set with the conformity
     score (core.user_data.load_dataset_kuaishou_DICE) -> UserModel_DICE fitted on the device with loss_kuaishou_DICE.  rl_test(model) ->
     dict goes through compile_RL_test, like the script's partial of test_static_model_in_RL_env: it is called on the untrained model
-    (epoch -1) and after every epoch, its results joining the epoch's logs.  Like the script, the run writes one artefact, the
+    (epoch -1) and after every epoch, its results joining the epoch's logs, behind the validation metrics of metric_fun (as in
+    train_user_model).  Like the script, the run writes one artefact, the
     constructor parameters (`<name>_params_<msg>.pickle`).
     Returns SimpleNamespace(model, history, paths, train_set, val_set, lbe_user, lbe_photo)."""
     from core.user_data import load_dataset_kuaishou_DICE
@@ -134,7 +154,7 @@ def train_dice_kuaishou(datapath, save_root=".", callbacks=None, rl_test=None, *
     params = {"feature_columns": x_columns, "y_columns": y_columns, "task": "regression", "task_logit_dim": 1,
               "dnn_hidden_units": tuple(a.dnn), "seed": a.seed, "device": "cuda"}
     model = UserModel_DICE(l2_reg_dnn=a.l2_reg_dnn, **params)
-    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=loss_kuaishou_DICE)
+    model.compile(torch.optim.Adam(model.parameters(), lr=a.lr), loss_func=loss_kuaishou_DICE, metric_fun=metric_fun)
     if rl_test is not None:
         model.compile_RL_test(rl_test)
 

@@ -1,6 +1,7 @@
 """The Kuaishou DICE debiasing baseline (reference DICE.py) on synthetic files in the KuaiRec layout: the 16-column training set with the
 conformity score of every (positive, negative) pair, UserModel_DICE trained on the device (cirs_dice_train_epoch), a top-k
-recommendation of the static-policy evaluation after every epoch (cirs_dice_forward), the per-epoch loss printed.  The KuaiRec files
+recommendation of the static-policy evaluation after every epoch (cirs_dice_forward), the validation mae / mse (cirs_dice_validate)
+and the loss printed per epoch, epoch -1 (the untrained model) first.  The KuaiRec files
 of the reference are not shipped.
 
     python examples/cirs_dice_kuaishou_synth.py [--epoch 5] [--batch_size 256] [--feature_dim 16]"""
@@ -22,7 +23,8 @@ def main():
     args = ap.parse_args()
     from cirs_hip.synthetic import write_kuairec_workspace
     from core.user_data import load_static_validate_data_kuaishou
-    from core.user_model_train import train_dice_kuaishou
+    from core.user_model import metric_mae, metric_mse
+    from core.user_model_train import EpochLines, train_dice_kuaishou
     with tempfile.TemporaryDirectory() as tmp:
         data = os.path.join(tmp, "data")
         made = write_kuairec_workspace(data, n_users=args.users, n_env_users=args.users // 2)
@@ -34,11 +36,11 @@ def main():
             _, raw, value = model.recommend_k_item(user, val_set, k=3, is_softmax=False)
             return {"top3": raw.tolist(), "top_value": float(value[0])}
         run = train_dice_kuaishou(data, save_root=tmp, epoch=args.epoch, batch_size=args.batch_size, feature_dim=args.feature_dim, lr=5e-3,
-                                  rl_test=rl_test)
+                                  rl_test=rl_test, metric_fun={"mae": metric_mae, "mse": metric_mse}, callbacks=[EpochLines()])
         score = run.train_set.score
         print(f"score column: {int((score > 0).sum())} rows +1, {int((score < 0).sum())} rows -1")
         for e, h in enumerate(run.history):
-            print(f"epoch {e}: loss {h['loss']:.4f}  top-3 for user {user}: {h['top3']} (value {h['top_value']:.4f})")
+            print(f"epoch {e}: loss {h['loss']:.4f}  val mae {h['mae']:.4f} mse {h['mse']:.4f}  top-3 for user {user}: {h['top3']} (value {h['top_value']:.4f})")
         print("artefact:", os.path.basename(run.paths.params))
 
 

@@ -126,7 +126,8 @@ def prepare_workspace(root, args, seed=0, um_epochs=3):
     """What the reference expects to find on disk: the KuaiRec files under environments/KuaishouRec/data and the three user-model
     artefacts of CIRS-UserModel-kuaishou.py under saved_models/<env>/<user_model_name>/.  Synthetic files + a short training run."""
     from cirs_hip.synthetic import write_kuairec_workspace
-    from core.user_model_train import train_user_model
+    from core.user_model import metric_mae, metric_mse
+    from core.user_model_train import EpochLines, train_user_model
     datapath = os.path.join(root, "environments", "KuaishouRec", "data")
     os.makedirs(datapath, exist_ok=True)
     if not os.path.isfile(os.path.join(datapath, "small_matrix.csv")):
@@ -135,7 +136,8 @@ def prepare_workspace(root, args, seed=0, um_epochs=3):
     um_dir = os.path.join(root, "saved_models", args.env, args.user_model_name)
     if not os.path.isfile(os.path.join(um_dir, "{}_{}.pt".format(args.user_model_name, args.read_message))):
         train_user_model(datapath, save_root=root, env=args.env, user_model_name=args.user_model_name, message=args.read_message,
-                         tau=float(args.tau) * 10, feature_dim=8, batch_size=256, epoch=um_epochs, lr=5e-3)
+                         tau=float(args.tau) * 10, feature_dim=8, batch_size=256, epoch=um_epochs, lr=5e-3,
+                         metric_fun={"mae": metric_mae, "mse": metric_mse}, callbacks=[EpochLines()])
     return datapath
 
 

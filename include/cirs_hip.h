@@ -707,6 +707,27 @@ int cirs_dice_train_epoch(const cirs_dice_cfg* cfg, float* params, float* grads,
 int cirs_dice_forward(const cirs_dice_cfg* cfg, const float* params, const int64_t* uid, const int64_t* pid, const int32_t* feats,
                       const float* dur, int64_t n, float* out, void* stream);
 
+/* ---- validation pass of the Kuaishou user models (csrc/userval.hip) -------------------------------------------------
+ * replaces  core/user_model.py:351-359 (evaluate_data), :361-399 (predict_data) and the scripts' metric lambdas
+ *           (CIRS-UserModel-kuaishou.py:204-207, DICE.py:236-239) for UserModel_Pairwise.forward and UserModel_DICE.forward.
+ * One launch scores the n rows (uid, pid, feats [n,4], dur) in tiles of 32 rows per wavefront -- both dense layers on the fp32 matrix
+ * cores, the weights staged in LDS once per workgroup -- and reduces the errors against y [n] (float64):
+ *   pred = the fp32 forward (cirs_deepfm_forward / cirs_dice_forward up to fp32 summation order), e = (double)pred - y[r];
+ *   pred_out [n] fp32, NULL: no prediction is written;  sums_out [2] float64 = {sum |e|, sum e^2}, NULL: y is not read.
+ * At least one of the two outputs is given.  Per-wavefront partial pairs go to the workspace and a final launch adds them in index
+ * order: no atomics, two runs give the same bits.  n < 1 is refused (CIRS_E_INVALID).  emb_dim as for the forward entries
+ * ({8,16,32,64} DeepFM, {8,16,32} DICE), hidden == 64.
+ * Precondition, as for cirs_deepfm_train_epoch: every id lies inside its table; the kernel indexes the tables with them unchecked
+ * (cirs_hip.userval.ValSet checks once at load).  workspace: cirs_*_validate_workspace_bytes(cfg, n), needed with sums_out only. */
+int64_t cirs_deepfm_validate_workspace_bytes(const cirs_deepfm_cfg* cfg, int64_t n);
+int cirs_deepfm_validate(const cirs_deepfm_cfg* cfg, const cirs_deepfm_weights* w, const int64_t* uid, const int64_t* pid,
+                         const int32_t* feats, const float* dur, const double* y, int64_t n, float* pred_out, double* sums_out,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int64_t cirs_dice_validate_workspace_bytes(const cirs_dice_cfg* cfg, int64_t n);
+int cirs_dice_validate(const cirs_dice_cfg* cfg, const float* params, const int64_t* uid, const int64_t* pid, const int32_t* feats,
+                       const float* dur, const double* y, int64_t n, float* pred_out, double* sums_out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* ---- user-model dataset preparation ---------------------------------------------------------------
  * cirs_exposure_history replaces compute_exposure_each_user / the per-user loop of compute_exposure_effect_kuaishouRec
  * (reference core/util.py:56-76,135-169): rows are the logged interactions in file order, a user's rows contiguous;

@@ -7,7 +7,12 @@ torch-fp32 restatement of the same step on the host cores for comparison.
 --scores   ips_scores / popularity_scores on a 10^6-row synthetic log against the reference's pandas `map` formulation on the host.
 --dice     per optimiser step of the DICE baseline over a resident data set of 50 batches: DiceTrainer.epoch() against the same steps
            in plain torch on the same GPU (the loop of dice_host.torch_train on device tensors: autograd + torch.optim.Adam, parameters and
-           optimiser built once outside the timed passes, losses kept on the device); each the median of 5 timed passes after one warm-up pass, device first and torch second, then both once more."""
+           optimiser built once outside the timed passes, losses kept on the device); each the median of 5 timed passes after one warm-up pass, device first and torch second, then both once more.
+--validate one evaluate_data (mae, mse) over the scripts' validation set, the whole small matrix 1411 x 3327 = 4.69 M rows, for the pairwise
+           DeepFM and DICE: (a) the per-row forward entry over all rows in one call + a torch float64 reduction of the predictions, (b) the
+           reference-shaped loop, 2048 rows per forward call with a read-back each, metrics on the host, (c) the fused call
+           (cirs_*_validate, sums read back); wall-clock medians after one warm-up pass (5 passes; 3 for (b)), in the order a, c, b, then a
+           and c once more; and the fused launch pair's time from device events (median of 20)."""
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "cirs-codes_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -138,4 +143,51 @@ if "--dice" in sys.argv:
     d2, t2 = med(dev_fn), med(torch_fn)
     out.update(dice_epoch_us=min(d1, d2), dice_torch_us=min(t1, t2), dice_epoch_us_runs=[d1, d2], dice_torch_us_runs=[t1, t2],
                dice_speedup=min(t1, t2) / min(d1, d2))
+if "--validate" in sys.argv:
+    from cirs_hip import dice_train
+    from cirs_hip.deepfm import DeviceDeepFM
+    from cirs_hip.userval import ValSet
+    NU, NI = 1411, 3327
+    NV = NU * NI
+    vu, vi = np.repeat(rng.randint(0, U, NU), NI), np.tile(rng.randint(0, I, NI), NU)
+    vfeat = np.tile(np.where(np.arange(4)[None, :] < rng.randint(1, 5, NI)[:, None], rng.randint(1, F, (NI, 4)), 0), (NU, 1))
+    xv = np.concatenate([col(vu), col(vi), vfeat, col(np.tile(rng.uniform(2, 60, NI), NU))], axis=1)
+    yv = rng.uniform(0, 5, (NV, 1))
+    dinit = {name: rng.normal(0, 0.05, shape).astype(np.float32) for name, shape in dice_train.layout(U, I, F, E)}
+    dinit["embedding_dict.feat.weight"][0] = 0
+
+    def wall(fn, reps):
+        fn(); torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+        return 1e3 * float(np.median(ts))
+    for tag, dm in (("pairwise", DeviceDeepFM(init)), ("dice", dice_train.DeviceDice(dinit))):
+        vs = ValSet(xv, yv, dm.cfg, dm.device)
+
+        def per_row():
+            e = dm.forward(vs.uid, vs.pid, vs.feats, vs.dur).double() - vs.y
+            return float(e.abs().sum().cpu()) / NV, float((e * e).sum().cpu()) / NV
+
+        def batched():
+            preds = [dm.forward(vs.uid[s0:s0 + 2048], vs.pid[s0:s0 + 2048], vs.feats[s0:s0 + 2048], vs.dur[s0:s0 + 2048]).cpu().numpy()
+                     for s0 in range(0, NV, 2048)]
+            e = np.concatenate(preds).astype("float64") - yv[:, 0]
+            return np.abs(e).mean(), (e * e).mean()
+
+        def fused():
+            s = dm.validate(vs)[1].cpu().numpy()
+            return s[0] / NV, s[1] / NV
+        a1, c1, b1 = wall(per_row, 5), wall(fused, 5), wall(batched, 3)
+        a2, c2 = wall(per_row, 5), wall(fused, 5)
+        ev = []
+        for _ in range(21):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); dm.validate(vs); e1.record(); torch.cuda.synchronize()
+            ev.append(e0.elapsed_time(e1))
+        ra, rc = per_row(), fused()
+        out[f"validate_{tag}"] = dict(rows=NV, a_per_row_ms=min(a1, a2), b_batched_loop_ms=b1, c_fused_ms=min(c1, c2), a_runs=[a1, a2], c_runs=[c1, c2],
+                                      fused_kernel_ms=float(np.median(ev[1:])), speedup_vs_a=min(a1, a2) / min(c1, c2),
+                                      metrics_agree=bool(np.allclose(ra, rc, rtol=1e-6)))
 print(json.dumps(out))
