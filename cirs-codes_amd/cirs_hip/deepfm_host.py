@@ -10,7 +10,9 @@ torch_train   the optimiser steps of UserModel_Pairwise.fit_data (reference core
                 regulariser  core/user_model.py:401-417: embedding_dict.* (l2_embedding), linear_model.* (l2_linear), every
                              parameter (l2_all); the padding row of the feature table gets no data gradient and still decays
               The comparison object of the device step for the two debiasing losses, which the test oracle does not know, in tests
-              and in tools/probe_usertrain.py."""
+              and in tools/probe_usertrain.py.
+loss_and_grad the loss columns and the total gradient (loss + regulariser) of one batch; torch_train's step and, in float64, the
+              reference of the device's gradient buffer (tests/gradcase.py)."""
 import numpy as np
 import torch
 
@@ -52,6 +54,43 @@ def loss_terms(kind, y, yp, yn, score, alpha=None, beta=None):
     raise ValueError(f"loss kind must be one of {LOSS_KINDS}, got {kind!r}")
 
 
+def loss_and_grad(p, x, y, score, kind="pairwise", use_ab=False, lambda_ab=0.0, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1,
+                  dtype=torch.float64):
+    """Loss and total gradient of one batch: p a state_dict (numpy / tensors; leaf tensors of `dtype` that require a gradient are used as
+    they are), x [n,14], y and score [n] or [n,1].  -> (loss columns in the device's order {loss, loss_y, bpr, loss_ab, reg} as one detached
+    tensor, {name: d (loss + reg) / d p[name]}).  The padding row 0 of embedding_dict.feat.weight carries the regulariser's 2 c p only
+    (nn.Embedding(padding_idx=0)); linear_model.* is moved by the regulariser alone; without alpha/beta the ab_* tensors are not
+    parameters: absent from p, they are absent from the gradient."""
+    if use_ab and kind != "pairwise":
+        raise ValueError(f"the {kind!r} loss takes no alpha/beta")
+
+    def leaf(v):
+        if isinstance(v, torch.Tensor) and v.requires_grad and v.is_leaf and v.dtype == dtype:
+            return v
+        return (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(dtype).clone().requires_grad_(True)
+    p = {k: leaf(v) for k, v in p.items()}
+    xb = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(dtype)
+    yb = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(dtype).reshape(-1)
+    sb = torch.as_tensor(np.asarray(score) if not isinstance(score, torch.Tensor) else score).to(dtype).reshape(-1)
+    feat = "embedding_dict.feat.weight"
+    yp, yn = pair_forward(p, xb[:, :7]), pair_forward(p, xb[:, 7:])
+    alpha = beta = None
+    if use_ab:
+        alpha = p["ab_embedding_dict.alpha_u.weight"][xb[:, 0].long(), 0]
+        beta = p["ab_embedding_dict.beta_i.weight"][xb[:, 1].long(), 0]
+    loss_y, bpr, loss_ab = loss_terms(kind, yb, yp, yn, sb, alpha, beta)
+    loss = loss_y + bpr + lambda_ab * loss_ab
+    reg = 0.0
+    for k, v in p.items():
+        c = l2_all + (l2_embedding if k.startswith("embedding_dict.") else 0.0) + (l2_linear if k.startswith("linear_model.") else 0.0)
+        reg = reg + c * (v * v).sum()
+    names = list(p)
+    grads = dict(zip(names, torch.autograd.grad(loss + reg, [p[k] for k in names])))
+    # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
+    grads[feat][0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+    return torch.stack([t.detach() for t in (loss, loss_y, bpr, loss_ab, reg)]), grads
+
+
 def torch_train(init, x, y, score, batch_size, steps=None, order=None, kind="pairwise", use_ab=False, lambda_ab=0.0, l2_embedding=1e-5,
                 l2_linear=1e-5, l2_all=0.1, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, dtype=torch.float32, keep=()):
     """init: state_dict (numpy / tensors); x [N,14], y [N] or [N,1], score likewise; batch b = rows order[b * batch_size : ...] (None: file
@@ -67,28 +106,14 @@ def torch_train(init, x, y, score, batch_size, steps=None, order=None, kind="pai
     order = torch.arange(x.shape[0]) if order is None else torch.as_tensor(np.asarray(order)).long()
     n_steps = (len(order) + batch_size - 1) // batch_size
     steps = n_steps if steps is None else min(steps, n_steps)
-    feat = "embedding_dict.feat.weight"
     losses, kept = [], {}
     for st in range(steps):
         idx = order[st * batch_size:(st + 1) * batch_size]
-        xb, yb, sb = x[idx], y[idx], score[idx]
-        yp, yn = pair_forward(p, xb[:, :7]), pair_forward(p, xb[:, 7:])
-        alpha = beta = None
-        if use_ab:
-            alpha = p["ab_embedding_dict.alpha_u.weight"][xb[:, 0].long(), 0]
-            beta = p["ab_embedding_dict.beta_i.weight"][xb[:, 1].long(), 0]
-        loss_y, bpr, loss_ab = loss_terms(kind, yb, yp, yn, sb, alpha, beta)
-        loss = loss_y + bpr + lambda_ab * loss_ab
-        reg = 0.0
+        cols, grads = loss_and_grad(p, x[idx], y[idx], score[idx], kind, use_ab, lambda_ab, l2_embedding, l2_linear, l2_all, dtype)
         for k, v in p.items():
-            c = l2_all + (l2_embedding if k.startswith("embedding_dict.") else 0.0) + (l2_linear if k.startswith("linear_model.") else 0.0)
-            reg = reg + c * (v * v).sum()
-        opt.zero_grad()
-        (loss + reg).backward()
-        # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
-        p[feat].grad[0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+            v.grad = grads[k]
         opt.step()
-        losses.append([float(t.detach()) for t in (loss, loss_y, bpr, loss_ab, reg)])
+        losses.append([float(t) for t in cols])
         if st in keep:
             kept[st] = {k: v.detach().clone().numpy() for k, v in p.items()}
     return np.array(losses), kept, {k: v.detach().clone().numpy() for k, v in p.items()}

@@ -8,7 +8,9 @@ torch_train   the optimiser steps of fit_data (core/user_model.py:150-170) in pl
               state_dict under the reference's names, in fp32 or fp64, on any device.  Regulariser (core/user_model.py:401-417):
               embedding_dict.* (l2_embedding), linear_model.* (l2_linear; unused in the forward, still decayed), every parameter
               (l2_all); the padding row of the feature table gets no data gradient and still decays.
-              The comparison object of the device step in tests and in tools/probe_usertrain.py."""
+              The comparison object of the device step in tests and in tools/probe_usertrain.py.
+loss_and_grad the loss columns and the total gradient (loss + regulariser) of one batch; torch_train's step and, in float64, the
+              reference of the device's gradient buffer (tests/gradcase.py)."""
 import numpy as np
 import torch
 
@@ -73,6 +75,31 @@ def regulariser(p, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1):
     return reg
 
 
+def loss_and_grad(p, x, y, score, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1, dtype=torch.float64, device=None):
+    """Loss and total gradient of one batch: p a state_dict (numpy / tensors; leaf tensors of `dtype` that require a gradient are used as
+    they are), x [n,16], y and score [n] or [n,1].  -> (loss columns in the device's order {loss, loss_y, bpr_click, bpr_con, bpr_int,
+    reg} as one detached tensor, {name: d (loss + reg) / d p[name]}).  The padding row 0 of embedding_dict.feat.weight carries the
+    regulariser's 2 c p only (nn.Embedding(padding_idx=0)); linear_model.* is moved by the regulariser alone."""
+    def t(v):
+        v = v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+        return v.to(v.device if device is None else device, dtype)
+
+    def leaf(v):
+        if isinstance(v, torch.Tensor) and v.requires_grad and v.is_leaf and v.dtype == dtype:
+            return v
+        return t(v).clone().requires_grad_(True)
+    p = {k: leaf(v) for k, v in p.items()}
+    feat = "embedding_dict.feat.weight"
+    terms = get_loss(p, t(x), t(y).reshape(-1), t(score).reshape(-1))
+    loss = terms[0] + terms[1] + terms[2] + terms[3]
+    reg = regulariser(p, l2_embedding, l2_linear, l2_all)
+    names = list(p)
+    grads = dict(zip(names, torch.autograd.grad(loss + reg, [p[k] for k in names])))
+    # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
+    grads[feat][0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+    return torch.stack([v.detach() for v in (loss,) + terms + (reg,)]), grads
+
+
 def torch_train(init, x, y, score, batch_size, steps=None, order=None, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1, lr=1e-3,
                 betas=(0.9, 0.999), eps=1e-8, dtype=torch.float32, keep=(), device="cpu"):
     """init: state_dict (numpy / tensors); x [N,16], y [N] or [N,1], score likewise; batch b = rows order[b * batch_size : ...] (None: file
@@ -86,19 +113,14 @@ def torch_train(init, x, y, score, batch_size, steps=None, order=None, l2_embedd
     order = torch.arange(x.shape[0], device=device) if order is None else torch.as_tensor(np.asarray(order)).long().to(device)
     n_steps = (len(order) + batch_size - 1) // batch_size
     steps = n_steps if steps is None else min(steps, n_steps)
-    feat = "embedding_dict.feat.weight"
     losses, kept = [], {}
     for st in range(steps):
         idx = order[st * batch_size:(st + 1) * batch_size]
-        terms = get_loss(p, x[idx], y[idx], score[idx])
-        loss = terms[0] + terms[1] + terms[2] + terms[3]
-        reg = regulariser(p, l2_embedding, l2_linear, l2_all)
-        opt.zero_grad()
-        (loss + reg).backward()
-        # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
-        p[feat].grad[0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+        cols, grads = loss_and_grad(p, x[idx], y[idx], score[idx], l2_embedding, l2_linear, l2_all, dtype, device)
+        for k, v in p.items():
+            v.grad = grads[k]
         opt.step()
-        losses.append(torch.stack([v.detach() for v in (loss,) + terms + (reg,)]))
+        losses.append(cols)
         if st in keep:
             kept[st] = {k: v.detach().cpu().clone().numpy() for k, v in p.items()}
     return torch.stack(losses).cpu().numpy().astype(np.float64), kept, {k: v.detach().cpu().clone().numpy() for k, v in p.items()}
