@@ -13,8 +13,9 @@ torch_train   the optimiser steps of UserModel_Pairwise.fit_data (reference core
               and in tools/probe_usertrain.py.
 loss_and_grad the loss columns and the total gradient (loss + regulariser) of one batch; torch_train's step and, in float64, the
               reference of the device's gradient buffer (tests/gradcase.py)."""
-import numpy as np
 import torch
+
+from . import usertrain_host as H
 
 LOSS_KINDS = ("pairwise", "ips", "pd")
 
@@ -29,12 +30,8 @@ def pair_forward(p, X):
     for q in range(4):
         lin = lin + p["linear.embedding_dict.feat.weight"][ids[:, 2 + q], 0]
     lin = lin + dur[:, 0] * p["linear.weight"].reshape(())
-    S = sum(vs)
-    fm = 0.5 * ((S * S) - sum(v * v for v in vs)).sum(1)
-    x = torch.cat(vs + [dur], dim=1)
-    h1 = torch.relu(x @ p["dnn.linears.0.weight"].T + p["dnn.linears.0.bias"])
-    h2 = torch.relu(h1 @ p["dnn.linears.1.weight"].T + p["dnn.linears.1.bias"])
-    return lin + fm + (h2 @ p["last.weight"].T)[:, 0] + p["out.bias"].reshape(())
+    fm, dnn, out = H.tower(p, "dnn", "last", "out", vs, [dur])
+    return lin + fm + dnn + out
 
 
 def loss_terms(kind, y, yp, yn, score, alpha=None, beta=None):
@@ -64,15 +61,8 @@ def loss_and_grad(p, x, y, score, kind="pairwise", use_ab=False, lambda_ab=0.0, 
     if use_ab and kind != "pairwise":
         raise ValueError(f"the {kind!r} loss takes no alpha/beta")
 
-    def leaf(v):
-        if isinstance(v, torch.Tensor) and v.requires_grad and v.is_leaf and v.dtype == dtype:
-            return v
-        return (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(dtype).clone().requires_grad_(True)
-    p = {k: leaf(v) for k, v in p.items()}
-    xb = torch.as_tensor(np.asarray(x) if not isinstance(x, torch.Tensor) else x).to(dtype)
-    yb = torch.as_tensor(np.asarray(y) if not isinstance(y, torch.Tensor) else y).to(dtype).reshape(-1)
-    sb = torch.as_tensor(np.asarray(score) if not isinstance(score, torch.Tensor) else score).to(dtype).reshape(-1)
-    feat = "embedding_dict.feat.weight"
+    p = {k: H.leaf(v, dtype) for k, v in p.items()}
+    xb, yb, sb = H.tensor(x, dtype), H.tensor(y, dtype).reshape(-1), H.tensor(score, dtype).reshape(-1)
     yp, yn = pair_forward(p, xb[:, :7]), pair_forward(p, xb[:, 7:])
     alpha = beta = None
     if use_ab:
@@ -80,14 +70,8 @@ def loss_and_grad(p, x, y, score, kind="pairwise", use_ab=False, lambda_ab=0.0, 
         beta = p["ab_embedding_dict.beta_i.weight"][xb[:, 1].long(), 0]
     loss_y, bpr, loss_ab = loss_terms(kind, yb, yp, yn, sb, alpha, beta)
     loss = loss_y + bpr + lambda_ab * loss_ab
-    reg = 0.0
-    for k, v in p.items():
-        c = l2_all + (l2_embedding if k.startswith("embedding_dict.") else 0.0) + (l2_linear if k.startswith("linear_model.") else 0.0)
-        reg = reg + c * (v * v).sum()
-    names = list(p)
-    grads = dict(zip(names, torch.autograd.grad(loss + reg, [p[k] for k in names])))
-    # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
-    grads[feat][0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+    reg = H.regulariser(p, l2_embedding, l2_linear, l2_all)
+    grads = H.total_grad(p, loss, reg, l2_embedding, l2_all)
     return torch.stack([t.detach() for t in (loss, loss_y, bpr, loss_ab, reg)]), grads
 
 
@@ -98,22 +82,5 @@ def torch_train(init, x, y, score, batch_size, steps=None, order=None, kind="pai
     `keep`}, final parameters)."""
     if use_ab and kind != "pairwise":
         raise ValueError(f"the {kind!r} loss takes no alpha/beta")
-    p = {k: torch.as_tensor(np.asarray(v)).to(dtype).clone().requires_grad_(True) for k, v in init.items()}
-    opt = torch.optim.Adam(list(p.values()), lr=lr, betas=betas, eps=eps)
-    x = torch.as_tensor(np.asarray(x)).to(dtype)
-    y = torch.as_tensor(np.asarray(y)).to(dtype).reshape(-1)
-    score = torch.as_tensor(np.asarray(score)).to(dtype).reshape(-1)
-    order = torch.arange(x.shape[0]) if order is None else torch.as_tensor(np.asarray(order)).long()
-    n_steps = (len(order) + batch_size - 1) // batch_size
-    steps = n_steps if steps is None else min(steps, n_steps)
-    losses, kept = [], {}
-    for st in range(steps):
-        idx = order[st * batch_size:(st + 1) * batch_size]
-        cols, grads = loss_and_grad(p, x[idx], y[idx], score[idx], kind, use_ab, lambda_ab, l2_embedding, l2_linear, l2_all, dtype)
-        for k, v in p.items():
-            v.grad = grads[k]
-        opt.step()
-        losses.append([float(t) for t in cols])
-        if st in keep:
-            kept[st] = {k: v.detach().clone().numpy() for k, v in p.items()}
-    return np.array(losses), kept, {k: v.detach().clone().numpy() for k, v in p.items()}
+    return H.torch_train(lambda p, xb, yb, sb: loss_and_grad(p, xb, yb, sb, kind, use_ab, lambda_ab, l2_embedding, l2_linear, l2_all, dtype),
+                         init, x, y, score, batch_size, steps, order, lr, betas, eps, dtype, keep)

@@ -11,19 +11,17 @@ torch_train   the optimiser steps of fit_data (core/user_model.py:150-170) in pl
               The comparison object of the device step in tests and in tools/probe_usertrain.py.
 loss_and_grad the loss columns and the total gradient (loss + regulariser) of one batch; torch_train's step and, in float64, the
               reference of the device's gradient buffer (tests/gradcase.py)."""
-import numpy as np
 import torch
+
+from . import usertrain_host as H
+from .usertrain_host import regulariser  # noqa: F401  (tools/probe_usertrain.py times it as part of this model's step)
 
 TABLES = ("user_int", "user_con", "photo_int", "photo_con")
 
 
 def _tower(p, name, vs, dense):
-    S = sum(vs)
-    fm = 0.5 * ((S * S) - sum(v * v for v in vs)).sum(1)
-    x = torch.cat(vs + dense, dim=1)
-    h1 = torch.relu(x @ p[f"dnn_{name}.linears.0.weight"].T + p[f"dnn_{name}.linears.0.bias"])
-    h2 = torch.relu(h1 @ p[f"dnn_{name}.linears.1.weight"].T + p[f"dnn_{name}.linears.1.bias"])
-    return fm + (h2 @ p[f"last_{name}.weight"].T)[:, 0] + p[f"out_{name}.bias"].reshape(())
+    fm, dnn, out = H.tower(p, f"dnn_{name}", f"last_{name}", f"out_{name}", vs, dense)
+    return fm + dnn + out
 
 
 def main_forward(p, X):
@@ -67,36 +65,16 @@ def get_loss(p, x, y, score):
     return loss_terms(y, yp, yn, ypi, yni, ypc, ync, score)
 
 
-def regulariser(p, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1):
-    reg = 0.0
-    for k, v in p.items():
-        c = l2_all + (l2_embedding if k.startswith("embedding_dict.") else 0.0) + (l2_linear if k.startswith("linear_model.") else 0.0)
-        reg = reg + c * (v * v).sum()
-    return reg
-
-
 def loss_and_grad(p, x, y, score, l2_embedding=1e-5, l2_linear=1e-5, l2_all=0.1, dtype=torch.float64, device=None):
     """Loss and total gradient of one batch: p a state_dict (numpy / tensors; leaf tensors of `dtype` that require a gradient are used as
     they are), x [n,16], y and score [n] or [n,1].  -> (loss columns in the device's order {loss, loss_y, bpr_click, bpr_con, bpr_int,
     reg} as one detached tensor, {name: d (loss + reg) / d p[name]}).  The padding row 0 of embedding_dict.feat.weight carries the
     regulariser's 2 c p only (nn.Embedding(padding_idx=0)); linear_model.* is moved by the regulariser alone."""
-    def t(v):
-        v = v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-        return v.to(v.device if device is None else device, dtype)
-
-    def leaf(v):
-        if isinstance(v, torch.Tensor) and v.requires_grad and v.is_leaf and v.dtype == dtype:
-            return v
-        return t(v).clone().requires_grad_(True)
-    p = {k: leaf(v) for k, v in p.items()}
-    feat = "embedding_dict.feat.weight"
-    terms = get_loss(p, t(x), t(y).reshape(-1), t(score).reshape(-1))
+    p = {k: H.leaf(v, dtype, device) for k, v in p.items()}
+    terms = get_loss(p, H.tensor(x, dtype, device), H.tensor(y, dtype, device).reshape(-1), H.tensor(score, dtype, device).reshape(-1))
     loss = terms[0] + terms[1] + terms[2] + terms[3]
     reg = regulariser(p, l2_embedding, l2_linear, l2_all)
-    names = list(p)
-    grads = dict(zip(names, torch.autograd.grad(loss + reg, [p[k] for k in names])))
-    # nn.Embedding(padding_idx=0): the padding row never receives a data gradient, but it is regularised
-    grads[feat][0] = 2 * (l2_all + l2_embedding) * p[feat].detach()[0]
+    grads = H.total_grad(p, loss, reg, l2_embedding, l2_all)
     return torch.stack([v.detach() for v in (loss,) + terms + (reg,)]), grads
 
 
@@ -105,22 +83,5 @@ def torch_train(init, x, y, score, batch_size, steps=None, order=None, l2_embedd
     """init: state_dict (numpy / tensors); x [N,16], y [N] or [N,1], score likewise; batch b = rows order[b * batch_size : ...] (None: file
     order).  -> (losses [steps, 6] = {loss, loss_y, bpr_click, bpr_con, bpr_int, reg}, {step index: parameters after that step for the
     indices in `keep`}, final parameters)."""
-    def t(v):
-        return (v.detach() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))).to(device, dtype)
-    p = {k: t(v).clone().requires_grad_(True) for k, v in init.items()}
-    opt = torch.optim.Adam(list(p.values()), lr=lr, betas=betas, eps=eps)
-    x, y, score = t(x), t(y).reshape(-1), t(score).reshape(-1)
-    order = torch.arange(x.shape[0], device=device) if order is None else torch.as_tensor(np.asarray(order)).long().to(device)
-    n_steps = (len(order) + batch_size - 1) // batch_size
-    steps = n_steps if steps is None else min(steps, n_steps)
-    losses, kept = [], {}
-    for st in range(steps):
-        idx = order[st * batch_size:(st + 1) * batch_size]
-        cols, grads = loss_and_grad(p, x[idx], y[idx], score[idx], l2_embedding, l2_linear, l2_all, dtype, device)
-        for k, v in p.items():
-            v.grad = grads[k]
-        opt.step()
-        losses.append(cols)
-        if st in keep:
-            kept[st] = {k: v.detach().cpu().clone().numpy() for k, v in p.items()}
-    return torch.stack(losses).cpu().numpy().astype(np.float64), kept, {k: v.detach().cpu().clone().numpy() for k, v in p.items()}
+    return H.torch_train(lambda p, xb, yb, sb: loss_and_grad(p, xb, yb, sb, l2_embedding, l2_linear, l2_all, dtype, device),
+                         init, x, y, score, batch_size, steps, order, lr, betas, eps, dtype, keep, device)

@@ -6,16 +6,17 @@ views follow the reference's state_dict.  DeviceDice is the evaluation side (for
 import ctypes as C
 from typing import Dict
 
-import numpy as np
 import torch
 
 from . import abi
+from .flat_train import TableTrainer, fill_views
 
 TABLES = (("user_int", "U"), ("user_con", "U"), ("photo_int", "I"), ("photo_con", "I"), ("feat", "F"))
 LOSS_COLUMNS = ("loss", "loss_y", "bpr_click", "bpr_con", "bpr_int", "reg")
 
 
-# (state_dict name, shape) in buffer order -- must match dice_layout() in csrc/dice_train.hip
+# (state_dict name, shape) in buffer order -- must match dice_layout() in csrc/dice_train.hip (a tower's six slots: tower_net() of
+# csrc/deepfm_tower.h)
 def layout(U: int, I: int, F: int, E: int):
     V = {"U": U, "I": I, "F": F}
 
@@ -29,7 +30,9 @@ def layout(U: int, I: int, F: int, E: int):
            [(f"linear_model.embedding_dict.{t}.weight", (V[v], 1)) for t, v in TABLES] + [("linear_model.weight", (2, 1))]
 
 
-def _cfg_of(sd):
+def _cfg_of(state_dict):
+    """-> (tensors of the state_dict, cfg, its layout)."""
+    sd = {k: torch.as_tensor(v) for k, v in state_dict.items()}
     U, E = sd["embedding_dict.user_int.weight"].shape
     I = sd["embedding_dict.photo_int.weight"].shape[0]
     F = sd["embedding_dict.feat.weight"].shape[0]
@@ -37,24 +40,13 @@ def _cfg_of(sd):
         raise ValueError(f"the DICE device model takes an embedding size of 8, 16 or 32, got {E}")
     if tuple(sd["dnn_main.linears.0.weight"].shape) != (64, 8 * E + 1) or tuple(sd["dnn_ui.linears.0.weight"].shape) != (64, 2 * E):
         raise ValueError("the DICE device model takes dnn_hidden_units == (64, 64) and entity_dim == feature_dim")
-    return abi.DiceCfg(n_user_vocab=U, n_item_vocab=I, n_feat_vocab=F, emb_dim=E, hidden=64), (U, I, F, E)
+    return sd, abi.DiceCfg(n_user_vocab=U, n_item_vocab=I, n_feat_vocab=F, emb_dim=E, hidden=64), layout(U, I, F, E)
 
 
-def _flatten(state_dict, device):
-    """-> (cfg, flat fp32 device buffer, {name: view})."""
-    sd = {k: torch.as_tensor(v) for k, v in state_dict.items()}
-    cfg, (U, I, F, E) = _cfg_of(sd)
-    total = abi.lib().cirs_dice_train_param_count(C.byref(cfg))
-    flat = torch.zeros(total, dtype=torch.float32, device=device)
-    views, off = {}, 0
-    for name, shape in layout(U, I, F, E):
-        n = int(np.prod(shape))
-        views[name] = flat[off:off + n].view(shape)
-        if not name.startswith("linear_model.") or name in sd:       # the unused copy may be absent from a hand-made dict
-            views[name].copy_(sd[name].to(device, torch.float32).reshape(shape))
-        off += n
-    assert off == total
-    return cfg, flat, views
+def _absent(name):
+    if name.startswith("linear_model."):       # the unused copy may be absent from a hand-made dict
+        return 0.0
+    raise KeyError(name)
 
 
 def split_columns(x, y, score, device):
@@ -72,30 +64,17 @@ def split_columns(x, y, score, device):
     return cols + [y, score]
 
 
-class DiceTrainer:
+class DiceTrainer(TableTrainer):
+    _param_count, _workspace_bytes, _epoch_fn = "cirs_dice_train_param_count", "cirs_dice_train_workspace_bytes", "cirs_dice_train_epoch"
+    LOSS_COLUMNS = LOSS_COLUMNS
+    split_columns = staticmethod(split_columns)
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], *, l2_embedding=1e-5, l2_linear=1e-5, l2_all=1e-1, lr=1e-3, betas=(0.9, 0.999),
                  eps=1e-8, device="cuda"):
-        self.device = torch.device(device)
-        self._lib = abi.lib()
-        self.cfg, self.flat, self.views = _flatten(state_dict, self.device)
-        self.grads = torch.zeros_like(self.flat)
-        self.adam_m = torch.zeros_like(self.flat)
-        self.adam_v = torch.zeros_like(self.flat)
-        self.step_count = 0
-        self.l2 = (float(l2_embedding), float(l2_linear), float(l2_all))
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        self._ws = None
-        self._data = None
-        self.loss = torch.zeros(6, dtype=torch.float32, device=self.device)
+        sd, cfg, names = _cfg_of(state_dict)
+        self._setup(cfg, names, sd, _absent, (l2_embedding, l2_linear, l2_all), lr, betas, eps, device)
 
-    def state_dict(self):
-        return {k: v.clone() for k, v in self.views.items()}
-
-    def _workspace(self, n):
-        need = self._lib.cirs_dice_train_workspace_bytes(C.byref(self.cfg), n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+    _epoch_args = TableTrainer._adam
 
     def _check_ids(self, cols):
         """The kernels index the tables with the data set's ids as they are: one range check per data set, in front of the passes."""
@@ -107,58 +86,17 @@ class DiceTrainer:
                 if int(lo) < 0 or int(up) >= hi:
                     raise IndexError(f"{what} ids outside [0, {hi})")
 
-    def _run_epoch(self, cols, n_rows, order, n_order, batch_size):
-        if int(batch_size) < 1:
-            raise ValueError("batch_size must be at least 1")
-        if n_rows < 1 or n_order < 1:
-            raise ValueError("empty data set or index array")
-        steps = (n_order + batch_size - 1) // batch_size
-        losses = torch.zeros(steps, 6, dtype=torch.float32, device=self.device)
-        ws = self._workspace(min(int(batch_size), n_order))
-        abi.check(self._lib.cirs_dice_train_epoch(
-            C.byref(self.cfg), self.flat.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.step_count,
-            *[c.data_ptr() for c in cols], n_rows, abi.ptr(order), n_order, int(batch_size), *self.l2, self.lr, self.betas[0], self.betas[1],
-            self.eps, losses.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "cirs_dice_train_epoch")
-        self.step_count += steps
-        return losses
-
     def validate(self, valset, want_pred=False, want_sums=True):
         """The validation pass (cirs_dice_validate) of the LIVE parameters over a cirs_hip.userval.ValSet -> (pred or None, sums or None)."""
         from .userval import dice_validate
         return dice_validate(self.cfg, self.flat, valset, want_pred, want_sums)
 
     def step(self, x, y, score):
-        """One optimiser step on the batch x [n,16], y, score [n] or [n,1] (a pass of one batch over these rows).  Returns the device loss
-        vector {loss, loss_y, bpr_click, bpr_con, bpr_int, reg}."""
+        """One optimiser step on the batch x [n,16], y, score [n] or [n,1].  Returns the device loss vector {loss, loss_y, bpr_click,
+        bpr_con, bpr_int, reg}."""
         cols = split_columns(x, y, score, self.device)
         self._check_ids(cols)
-        n = cols[0].numel()
-        self.loss.copy_(self._run_epoch(cols, n, None, n, n)[0])
-        return self.loss
-
-    def load(self, x, y, score):
-        """Make the data set resident on the device in the column form of the kernels (the split runs once); epoch() trains on it."""
-        cols = split_columns(x, y, score, self.device)
-        self._check_ids(cols)
-        self._data = cols
-        return cols[0].numel()
-
-    def epoch(self, order, batch_size, check=True):
-        """One pass over the loaded data set from one call: batch b is the rows order[b * batch_size : (b + 1) * batch_size] (int64 indices
-        into the data set; None = every row in file order), the last batch short.  Returns the [steps, 6] device tensor of per-step
-        {loss, loss_y, bpr_click, bpr_con, bpr_int, reg}.  check=False skips the range check of `order` (one read-back in front of the
-        pass) for a caller that built the permutation itself; the kernel answers an index outside the data set with a NaN loss, not a
-        read."""
-        assert self._data is not None, "call load(x, y, score) first"
-        n_rows = self._data[0].numel()
-        if order is None:
-            return self._run_epoch(self._data, n_rows, None, n_rows, batch_size)
-        order = torch.as_tensor(order).to(self.device, torch.int64).reshape(-1).contiguous()
-        if check and order.numel():
-            lo, hi = torch.aminmax(order)
-            if int(lo) < 0 or int(hi) >= n_rows:
-                raise IndexError(f"order holds row indices outside [0, {n_rows})")
-        return self._run_epoch(self._data, n_rows, order, order.numel(), batch_size)
+        return self._step_as_epoch(cols)
 
 
 class DeviceDice:
@@ -169,7 +107,9 @@ class DeviceDice:
     def __init__(self, state_dict, device="cuda"):
         self.device = torch.device(device)
         self._lib = abi.lib()
-        self.cfg, self.flat, self.views = _flatten(state_dict, self.device)
+        sd, self.cfg, names = _cfg_of(state_dict)
+        self.flat = torch.zeros(self._lib.cirs_dice_train_param_count(C.byref(self.cfg)), dtype=torch.float32, device=self.device)
+        self.views = fill_views(self.flat, names, sd, _absent)
 
     def forward(self, uid, pid, feats, dur):
         dev = self.device

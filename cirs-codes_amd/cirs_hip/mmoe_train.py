@@ -10,32 +10,27 @@ import numpy as np
 import torch
 
 from . import abi
+from .flat_train import FlatTrainer
 from .mmoe_host import ACTION_COLS, D_IN, USER_COLS, mlp_shape_of, mlp_shapes, shapes
 
-class _FlatTrainer:
-    """What both trainers share: parameters, gradients and the Adam moments as one flat fp32 device buffer each, the named views, the
-    workspace and the calls of the library's _step / _epoch entries.  A subclass's __init__ reads its shape off the state_dict and
+class _FlatTrainer(FlatTrainer):
+    """What both trainers share on top of the flat buffers: the named slots (some stored transposed) and the calls of the library's
+    _step / _epoch entries.  A subclass's __init__ reads its shape off the state_dict and
     calls _setup; it names its four ABI functions and supplies _cols(*columns) -> the validated, contiguous data columns (x first)."""
     _param_count = _workspace_bytes = _step_fn = _epoch_fn = None   # names of the ABI functions
 
     def _setup(self, cfg, sd, shapes, order, device):
         """cfg: the ABI's cfg struct; shapes: [(state_dict name, shape)] in state_dict order; order: [(name, stored transposed)] in
         buffer order."""
-        self.device = torch.device(device)
-        self.cfg = cfg
-        self._lib = abi.lib()
-        total = getattr(self._lib, self._param_count)(C.byref(cfg))
+        total = getattr(abi.lib(), self._param_count)(C.byref(cfg))
         if total <= 0:
-            msg = self._lib.cirs_last_error()
+            msg = abi.lib().cirs_last_error()
             raise ValueError(msg.decode() if msg else "unsupported MMoE shape")
         self._shapes = shapes
         want = dict(shapes)
         if set(sd) != set(want):
             raise ValueError(f"unexpected parameters for the VirtualTaobao MMoE: {sorted(set(sd) ^ set(want))}")
-        self.flat = torch.zeros(total, dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros_like(self.flat)
-        self.adam_m = torch.zeros_like(self.flat)
-        self.adam_v = torch.zeros_like(self.flat)
+        self._alloc(cfg, total, device)
         self._slots = {}
         off = 0
         for name, transposed in order:
@@ -46,8 +41,6 @@ class _FlatTrainer:
             self.flat[off:off + n].copy_((src.t() if transposed else src).reshape(-1))
             off += n
         assert off == total and set(self._slots) == set(want)
-        self.step_count = 0
-        self._ws = None
         self.loss = torch.zeros(2, dtype=torch.float32, device=self.device)
 
     def _named(self, flat):
@@ -68,18 +61,6 @@ class _FlatTrainer:
     def gradients(self):
         """The gradients of loss + reg of the last step, under the same names."""
         return self._named(self.grads)
-
-    def _workspace(self, n):
-        need = getattr(self._lib, self._workspace_bytes)(C.byref(self.cfg), int(n))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _buffers(self):
-        return C.byref(self.cfg), self.flat.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.step_count
 
     def _step(self, cols):
         n = cols[0].shape[0]

@@ -8,13 +8,14 @@
 //                       per-row DNN pre-activation gradients / inputs go to global memory for the weight-gradient GEMMs,
 //                       per-row embedding contributions (FM + DNN input gradient + linear term + alpha/beta) to the
 //                       contribution tables.
-//   dw_gemm (small_gemm.h)  dW1|db1, dW2|db2, dlast|dout_bias, dlin_dense: fp32 MFMA row-slab partials, fixed-order sums.
-//   scatter             (table_step.h, shared with dice_train.hip, as is adam_l2_kernel) stable radix sort of (key, row) + ordered
-//                       segment sums (no float atomics), one pass per key space
-//                       (user rows: [d emb_user | d lin_user | d alpha], item rows: [d emb_item | d lin_item | d beta],
-//                       feature rows: [d emb_feat | d lin_feat]; padding row 0 of emb_feat gets no gradient).
-//   adam_l2_kernel      g += 2 * l2_c * p (the regulariser is dense: every row of every table decays), Adam, and the
-//                       regulariser's value as per-workgroup partials.
+// This file holds the model's own parts: the parameter layout, the linear term and the contribution rows around the tower, the three
+// losses, the workspace carve and the entry points.  Shared with dice_train.hip:
+//   deepfm_tower.h      the tower (FM cross term + DNN) forward / backward of one row, the feature contribution rows, the row lookup,
+//                       the loss means, the tower's weight-gradient GEMMs (dw_gemm of small_gemm.h: fp32 MFMA row-slab partials,
+//                       fixed-order sums)
+//   table_step.h        the workspace allocator, the sorted scatter (user rows: [d emb_user | d lin_user | d alpha], item rows:
+//                       [d emb_item | d lin_item | d beta], feature rows: [d emb_feat | d lin_feat]; padding row 0 of emb_feat gets no
+//                       gradient), regulariser + Adam
 // All reductions have a fixed order: two runs give identical bits.
 //
 // train_rows_kernel takes the loss as a compile-time kind (the pair forward / backward, the GEMMs, the scatter and Adam are shared):
@@ -23,17 +24,14 @@
 //   2  loss_kuaishou_PD_pairwise       PD-pairwise.py:242-251: mean((yp pop - y)^2) + mean(-log sigmoid(yp - yn)), pop = score
 // and reads sample i of a step at row order[r0 + i] of a device-resident data set (r0 + i when order is null), so that
 // cirs_deepfm_train_epoch queues every step of a pass back to back without a gather launch or a host round trip.
-#include "small_gemm.h"
-#include "table_step.h"
-#include "train_step.h"
+#include "deepfm_tower.h"
 
 namespace cirs {
 
-constexpr int tH = 64;
-
 struct TrainLayout {  // offsets (floats) into the flat parameter / gradient / moment buffers
-    long emb_user, emb_item, emb_feat, lin_user, lin_item, lin_feat, lin_dense, w1, b1, w2, b2, last, out_bias, alpha_u, beta_i,
-        lm_user, lm_item, lm_feat, lm_dense, total;
+    long emb_user, emb_item, emb_feat, lin_user, lin_item, lin_feat, lin_dense;
+    TowerNet net;
+    long alpha_u, beta_i, lm_user, lm_item, lm_feat, lm_dense, total;
 };
 __host__ __device__ inline TrainLayout train_layout(const cirs_deepfm_cfg& c) {
     const long U = c.n_user_vocab, I = c.n_item_vocab, F = c.n_feat_vocab, E = c.emb_dim, K = 6 * E + 1;
@@ -41,7 +39,7 @@ __host__ __device__ inline TrainLayout train_layout(const cirs_deepfm_cfg& c) {
     long o = 0;
     L.emb_user = o; o += U * E; L.emb_item = o; o += I * E; L.emb_feat = o; o += F * E;
     L.lin_user = o; o += U; L.lin_item = o; o += I; L.lin_feat = o; o += F; L.lin_dense = o; o += 1;
-    L.w1 = o; o += tH * K; L.b1 = o; o += tH; L.w2 = o; o += tH * tH; L.b2 = o; o += tH; L.last = o; o += tH; L.out_bias = o; o += 1;
+    L.net = tower_net(o, K);
     L.alpha_u = o; o += U; L.beta_i = o; o += I;
     L.lm_user = o; o += U; L.lm_item = o; o += I; L.lm_feat = o; o += F; L.lm_dense = o; o += 1;
     L.total = o;
@@ -49,11 +47,26 @@ __host__ __device__ inline TrainLayout train_layout(const cirs_deepfm_cfg& c) {
 }
 
 struct TrainRows {  // per-pair-row outputs of train_rows_kernel, R = 2n rows (positives first)
-    float *X, *H1, *H2, *DA1, *DA2, *DY, *DUR;  // [R,K] [R,64] [R,64] [R,64] [R,64] [R] [R]
+    TowerRows t;                                // the tower's GEMM operands
+    float* DUR;                                 // [R]
     float *CU, *CI, *CF;                        // contributions [R,E+2] [R,E+2] [4R,E+1]
     int32_t *KU, *KI, *KF;                      // keys [R] [R] [4R]
     float* LP;                                  // [n,4] per-sample loss terms {sq err, bpr, (alpha-1)^2, (beta-1)^2}
 };
+
+// the workspace of a step on n samples: the size query runs this carve without a base pointer, the launch on the caller's workspace
+struct TrainWs { TrainRows o; StepScratch x; };
+static TrainWs train_carve(Bump& w, int E, size_t n) {
+    const size_t R = 2 * n;
+    const int K = 6 * E + 1;
+    TrainWs t;
+    t.o.t = tower_rows(w, R, K); t.o.DUR = w.take(R);
+    t.o.CU = w.take(R * (E + 2)); t.o.CI = w.take(R * (E + 2)); t.o.CF = w.take(4 * R * (E + 1));
+    t.o.KU = (int32_t*)w.take(R); t.o.KI = (int32_t*)w.take(R); t.o.KF = (int32_t*)w.take(4 * R);
+    t.o.LP = w.take(4 * n + 8);
+    t.x = step_scratch(w, tower_partial_floats(R, K), 4 * R);
+    return t;
+}
 
 // forward of one (user, item) pair by one wavefront; x / S / a1 / a2 stay in LDS for the backward
 __device__ __forceinline__ float pair_forward(const float* __restrict__ P, const TrainLayout& L, int E, int K, long u, long p,
@@ -68,31 +81,13 @@ __device__ __forceinline__ float pair_forward(const float* __restrict__ P, const
     }
     if (lane == 0) x[6 * E] = dur;
     __builtin_amdgcn_wave_barrier();
-    float cross = 0.f;
-    for (int e = lane; e < E; e += CIRS_WAVE) {
-        float s = 0.f, q = 0.f;
-        for (int fl = 0; fl < 6; ++fl) { const float v = x[fl * E + e]; s += v; q += v * v; }
-        S[e] = s;
-        cross += s * s - q;
-    }
-    cross = wave_sum_f32(cross);
     float logit = P[L.lin_user + u] + P[L.lin_item + p];
 #pragma unroll
     for (int q = 0; q < 4; ++q) logit += P[L.lin_feat + f4[q]];
     logit += dur * P[L.lin_dense];
-    logit += 0.5f * cross;
-    float acc = P[L.b1 + lane];
-    const float* w1r = P + L.w1 + (size_t)lane * K;
-    for (int k = 0; k < K; ++k) acc = __builtin_fmaf(w1r[k], x[k], acc);
-    a1[lane] = acc;
-    __builtin_amdgcn_wave_barrier();
-    acc = P[L.b2 + lane];
-    const float* w2r = P + L.w2 + (size_t)lane * tH;
-    for (int k = 0; k < tH; ++k) acc = __builtin_fmaf(w2r[k], fmaxf(a1[k], 0.f), acc);
-    a2[lane] = acc;
-    const float dnn = wave_sum_f32(P[L.last + lane] * fmaxf(acc, 0.f));
-    __builtin_amdgcn_wave_barrier();
-    return logit + (dnn + P[L.out_bias]);
+    const TowerOut t = tower_forward(P, L.net, 6, E, K, lane, x, S, a1, a2);
+    logit += 0.5f * t.cross;
+    return logit + t.dnn;
 }
 
 // backward of one pair row r given dy; writes the row's GEMM operands and embedding contributions
@@ -100,43 +95,14 @@ __device__ __forceinline__ void pair_backward(const float* __restrict__ P, const
                                               const int32_t* f4, float dur, float dy, float dalpha, float dbeta, int lane, int r,
                                               const float* x, const float* S, const float* a1, const float* a2, float* t64,
                                               float* dxs, const TrainRows& o) {
-    // DNN: da2 = dy * last * relu'(a2); dh1 = W2^T da2; da1 = dh1 * relu'(a1); dx = W1^T da1
-    const float da2 = a2[lane] > 0.f ? dy * P[L.last + lane] : 0.f;
-    o.DA2[(size_t)r * tH + lane] = da2;
-    o.H2[(size_t)r * tH + lane] = fmaxf(a2[lane], 0.f);
-    o.H1[(size_t)r * tH + lane] = fmaxf(a1[lane], 0.f);
-    t64[lane] = da2;
-    __builtin_amdgcn_wave_barrier();
-    float dh1 = 0.f;
-    for (int q = 0; q < tH; ++q) dh1 = __builtin_fmaf(P[L.w2 + (size_t)q * tH + lane], t64[q], dh1);
-    const float da1 = a1[lane] > 0.f ? dh1 : 0.f;
-    o.DA1[(size_t)r * tH + lane] = da1;
-    __builtin_amdgcn_wave_barrier();
-    t64[lane] = da1;
-    __builtin_amdgcn_wave_barrier();
-    for (int k = lane; k < K; k += CIRS_WAVE) {
-        o.X[(size_t)r * K + k] = x[k];
-        if (k < 6 * E) {
-            float dx = 0.f;
-            for (int q = 0; q < tH; ++q) dx = __builtin_fmaf(P[L.w1 + (size_t)q * K + k], t64[q], dx);
-            // FM: d/dv_f,e of 0.5 * sum_e (S_e^2 - Q_e) = S_e - v_f,e
-            dxs[k] = __builtin_fmaf(dy, S[k % E] - x[k], dx);
-        }
-    }
-    if (lane == 0) { o.DY[r] = dy; o.DUR[r] = dur; o.KU[r] = (int32_t)u; o.KI[r] = (int32_t)p; }
-    __builtin_amdgcn_wave_barrier();
-    const int WU = E + 2, WF = E + 1;
+    tower_backward(P, L.net, 6, E, K, dy, lane, (size_t)r, x, S, a1, a2, t64, dxs, o.t);
+    if (lane == 0) { o.DUR[r] = dur; o.KU[r] = (int32_t)u; o.KI[r] = (int32_t)p; }
+    const int WU = E + 2;
     for (int e = lane; e < WU; e += CIRS_WAVE) {
         o.CU[(size_t)r * WU + e] = e < E ? dxs[e] : (e == E ? dy : dalpha);
         o.CI[(size_t)r * WU + e] = e < E ? dxs[E + e] : (e == E ? dy : dbeta);
     }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int fid = f4[q];
-        for (int e = lane; e < WF; e += CIRS_WAVE)  // padding_idx = 0: the embedding row gets no gradient, the 1-d weight does
-            o.CF[((size_t)r * 4 + q) * WF + e] = e < E ? (fid == 0 ? 0.f : dxs[(2 + q) * E + e]) : dy;
-        if (lane == 0) o.KF[(size_t)r * 4 + q] = fid;
-    }
+    write_feat_contrib(o.CF, o.KF, (size_t)r, E, f4, dxs, 2, dy, lane);
     __builtin_amdgcn_wave_barrier();
 }
 
@@ -158,15 +124,14 @@ __global__ __launch_bounds__(256) void train_rows_kernel(cirs_deepfm_cfg cfg, co
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wv;
     if (i >= n) return;
-    const int per_pair = K + 1 + E + 2 * tH;
-    float* base = smem + (size_t)wv * (2 * per_pair + tH + 6 * E + 8);
-    float *xp = base, *Sp = xp + K + 1, *a1p = Sp + E, *a2p = a1p + tH;
-    float *xn = base + per_pair, *Sn = xn + K + 1, *a1n = Sn + E, *a2n = a1n + tH;
+    const int per_pair = K + 1 + E + 2 * kTowerH;
+    float* base = smem + (size_t)wv * (2 * per_pair + kTowerH + 6 * E + 8);
+    float *xp = base, *Sp = xp + K + 1, *a1p = Sp + E, *a2p = a1p + kTowerH;
+    float *xn = base + per_pair, *Sn = xn + K + 1, *a1n = Sn + E, *a2n = a1n + kTowerH;
     float* t64 = base + 2 * per_pair;
-    float* dxs = t64 + tH;
-    long row = order ? (long)order[r0 + i] : r0 + i;
-    const bool bad_row = row < 0 || row >= n_rows;   // an index outside the data set: no read there, the step's loss becomes NaN
-    if (bad_row) row = 0;
+    float* dxs = t64 + kTowerH;
+    bool bad_row;
+    const long row = step_row(order, r0, i, n_rows, bad_row);
     const long up = c.uid_pos[row], pp = c.pid_pos[row], un = c.uid_neg[row], pn = c.pid_neg[row];
     int32_t fp[4], fn[4];
 #pragma unroll
@@ -222,42 +187,15 @@ __global__ __launch_bounds__(256) void train_rows_kernel(cirs_deepfm_cfg cfg, co
     pair_backward(P, L, E, K, un, pn, fn, dn, dyn, 0.f, 0.f, lane, n + i, xn, Sn, a1n, a2n, t64, dxs, o);
 }
 
-// batch loss terms: fixed-order sums of the per-sample terms -> {loss, loss_y, bpr, loss_ab}
+// batch loss terms -> {loss, loss_y, bpr, loss_ab}
 __global__ __launch_bounds__(256) void train_loss_kernel(const float* __restrict__ LP, int n, float lambda_ab, float* __restrict__ loss_out) {
-    __shared__ float sh[4][256];
-    const int tid = threadIdx.x;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < n; i += 256)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] += LP[(size_t)i * 4 + q];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sh[q][tid] = a[q];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sh[q][tid] += sh[q][tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float inv = 1.0f / (float)n;
-        const float ly = sh[0][0] * inv, bpr = sh[1][0] * inv, lab = sh[2][0] * inv + sh[3][0] * inv;
+    float m[4];
+    loss_means4(LP, n, m);
+    if (threadIdx.x == 0) {
+        const float ly = m[0], bpr = m[1], lab = m[2] + m[3];
         loss_out[0] = ly + bpr + lambda_ab * lab;
         loss_out[1] = ly; loss_out[2] = bpr; loss_out[3] = lab;
     }
-}
-
-static size_t train_ws_floats(const cirs_deepfm_cfg* cfg, long n) {
-    const long E = cfg->emb_dim, K = 6 * E + 1, R = 2 * n;
-    size_t f = 0;
-    f += (size_t)R * K + 4 * (size_t)R * tH + 2 * (size_t)R;          // X, H1, H2, DA1, DA2, DY, DUR
-    f += 2 * (size_t)R * (E + 2) + 4 * (size_t)R * (E + 1);           // CU, CI, CF
-    f += 2 * (size_t)R + 4 * (size_t)R;                               // keys
-    f += 4 * (size_t)n + 64;                                          // LP
-    f += dwg_partial_floats(R, tH, (int)K) + 64;                      // dW slab partials (largest job: 64 x K)
-    f += kRegBlocks + 64;
-    f += train_sort_bytes(4 * R) / 4 + 64;
-    return f + 64 * 16;
 }
 
 }  // namespace cirs
@@ -269,15 +207,17 @@ extern "C" int64_t cirs_deepfm_train_param_count(const cirs_deepfm_cfg* cfg) {
 
 extern "C" int64_t cirs_deepfm_train_workspace_bytes(const cirs_deepfm_cfg* cfg, int32_t n) {
     if (!cfg || n <= 0) return 0;
-    return (int64_t)cirs::train_ws_floats(cfg, n) * 4;
+    cirs::Bump w{nullptr};
+    cirs::train_carve(w, cfg->emb_dim, n);
+    return (int64_t)(w.used * sizeof(float));
 }
 
 namespace cirs {
 
-struct TrainHyper { int use_ab; float lambda_ab, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps; };
+struct TrainHyper { int use_ab; float lambda_ab; TableHyper t; };
 
 static int train_check_cfg(const cirs_deepfm_cfg* cfg) {
-    if (cfg->hidden != tH) return fail(CIRS_E_UNSUPPORTED, "deepfm train: hidden == 64 only");
+    if (cfg->hidden != kTowerH) return fail(CIRS_E_UNSUPPORTED, "deepfm train: hidden == 64 only");
     CIRS_REQUIRE(cfg->emb_dim >= 1 && cfg->emb_dim <= 64, "emb_dim out of range");
     return CIRS_OK;
 }
@@ -290,20 +230,12 @@ static int train_launch_step(const cirs_deepfm_cfg* cfg, float* params, float* g
     const float lambda_ab = h.lambda_ab;
     const int E = cfg->emb_dim, K = 6 * E + 1, R = 2 * n;
     const TrainLayout L = train_layout(*cfg);
-    float* p = (float*)workspace;
-    auto take = [&](size_t cnt) { float* r = p; p += (cnt + 3) & ~(size_t)3; return r; };
-    TrainRows o;
-    o.X = take((size_t)R * K); o.H1 = take((size_t)R * tH); o.H2 = take((size_t)R * tH); o.DA1 = take((size_t)R * tH); o.DA2 = take((size_t)R * tH);
-    o.DY = take(R); o.DUR = take(R);
-    o.CU = take((size_t)R * (E + 2)); o.CI = take((size_t)R * (E + 2)); o.CF = take((size_t)4 * R * (E + 1));
-    o.KU = (int32_t*)take(R); o.KI = (int32_t*)take(R); o.KF = (int32_t*)take((size_t)4 * R);
-    o.LP = take((size_t)4 * n + 8);
-    float* partial = take(dwg_partial_floats(R, tH, K) + 64);
-    float* regp = take(kRegBlocks + 8);
-    void* sort_ws = (void*)take(train_sort_bytes(4L * R) / 4 + 64);
+    Bump w{(float*)workspace};
+    const TrainWs ws = train_carve(w, E, n);
+    const TrainRows& o = ws.o;
     // the data gradient is written sparsely (touched table rows, dense layers): start from zero
     CIRS_HIP(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)L.total, s));
-    const size_t shmem = sizeof(float) * 4 * (2 * (size_t)(K + 1 + E + 2 * tH) + tH + 6 * E + 8);
+    const size_t shmem = sizeof(float) * 4 * (2 * (size_t)(K + 1 + E + 2 * kTowerH) + kTowerH + 6 * E + 8);
     const dim3 grid(cdiv(n, 4));
     switch (kind) {
     case kLossPairwise:
@@ -321,33 +253,23 @@ static int train_launch_step(const cirs_deepfm_cfg* cfg, float* params, float* g
     CIRS_CHECK_LAUNCH("train_rows_kernel");
     hipLaunchKernelGGL(train_loss_kernel, dim3(1), dim3(256), 0, s, (const float*)o.LP, (int)n, lambda_ab, loss_out);
     // dense layers: dW = dY^T X over the 2n pair rows
-    launch_dw_gemm(o.DA1, tH, o.X, K, R, tH, K, grads + L.w1, grads + L.b1, partial, s);
-    launch_dw_gemm(o.DA2, tH, o.H1, tH, R, tH, tH, grads + L.w2, grads + L.b2, partial, s);
-    launch_dw_gemm(o.DY, 1, o.H2, tH, R, 1, tH, grads + L.last, grads + L.out_bias, partial, s);
-    launch_dw_gemm(o.DY, 1, o.DUR, 1, R, 1, 1, grads + L.lin_dense, nullptr, partial, s);
+    launch_tower_dw(o.t, R, K, grads, L.net, true, ws.x.partial, s);
+    launch_dw_gemm(o.t.DY, 1, o.DUR, 1, R, 1, 1, grads + L.lin_dense, nullptr, ws.x.partial, s);
     CIRS_CHECK_LAUNCH("deepfm train dW");
     // table rows
     ScatterDst du{{grads + L.emb_user, grads + L.lin_user, use_ab ? grads + L.alpha_u : nullptr}, {E, 1, 1}};
     ScatterDst di{{grads + L.emb_item, grads + L.lin_item, use_ab ? grads + L.beta_i : nullptr}, {E, 1, 1}};
     ScatterDst df{{grads + L.emb_feat, grads + L.lin_feat, nullptr}, {E, 1, 0}};
-    if (int rc = train_scatter(o.KU, o.CU, R, E + 2, cfg->n_user_vocab, du, sort_ws, train_sort_bytes(4L * R), s)) return rc;
-    if (int rc = train_scatter(o.KI, o.CI, R, E + 2, cfg->n_item_vocab, di, sort_ws, train_sort_bytes(4L * R), s)) return rc;
-    if (int rc = train_scatter(o.KF, o.CF, 4 * R, E + 1, cfg->n_feat_vocab, df, sort_ws, train_sort_bytes(4L * R), s)) return rc;
-    // regulariser + Adam (torch.optim.Adam, bias corrections from the step count)
+    if (int rc = train_scatter(o.KU, o.CU, R, E + 2, cfg->n_user_vocab, du, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KI, o.CI, R, E + 2, cfg->n_item_vocab, di, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KF, o.CF, 4 * R, E + 1, cfg->n_feat_vocab, df, ws.x.sort, ws.x.sort_bytes, s)) return rc;
     L2Segs segs;
     segs.n = 4;
-    segs.end[0] = L.lin_user;  segs.c[0] = h.l2_embedding + h.l2_all;   // embedding_dict.*            (core/user_model.py:60-63)
-    segs.end[1] = L.lm_user;   segs.c[1] = h.l2_all;                      // linear.*, dnn, last, out.bias, alpha_u, beta_i
-    segs.end[2] = L.total;     segs.c[2] = h.l2_linear + h.l2_all;      // linear_model.* (unused in forward, still decays)
-    segs.end[3] = L.total;     segs.c[3] = h.l2_linear + h.l2_all;
-    const double t = (double)(step_before + 1);
-    const float step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, t)));
-    const float bc2s = (float)sqrt(1.0 - pow((double)h.beta2, t));
-    hipLaunchKernelGGL(adam_l2_kernel, dim3(kRegBlocks), dim3(256), 0, s, params, grads, adam_m, adam_v, L.total, segs, h.beta1, h.beta2, h.eps,
-                       step_size, bc2s, regp);
-    hipLaunchKernelGGL(reg_final_kernel, dim3(1), dim3(256), 0, s, (const float*)regp, loss_out, 4);
-    CIRS_CHECK_LAUNCH("adam_l2_kernel");
-    return CIRS_OK;
+    segs.end[0] = L.lin_user;  segs.c[0] = h.t.l2_embedding + h.t.l2_all;   // embedding_dict.*            (core/user_model.py:60-63)
+    segs.end[1] = L.lm_user;   segs.c[1] = h.t.l2_all;                        // linear.*, dnn, last, out.bias, alpha_u, beta_i
+    segs.end[2] = L.total;     segs.c[2] = h.t.l2_linear + h.t.l2_all;      // linear_model.* (unused in forward, still decays)
+    segs.end[3] = L.total;     segs.c[3] = h.t.l2_linear + h.t.l2_all;
+    return table_adam_step(params, grads, adam_m, adam_v, L.total, segs, h.t, step_before, ws.x.regp, loss_out, 4, s);
 }
 
 }  // namespace cirs
@@ -365,7 +287,7 @@ extern "C" int cirs_deepfm_train_step(const cirs_deepfm_cfg* cfg, float* params,
     CIRS_REQUIRE(uid_pos && pid_pos && feats_pos && dur_pos && uid_neg && pid_neg && feats_neg && dur_neg && y && exposure, "null batch column");
     CIRS_REQUIRE(workspace_bytes >= cirs_deepfm_train_workspace_bytes(cfg, n), "workspace too small");
     const TrainCols c{uid_pos, pid_pos, feats_pos, dur_pos, uid_neg, pid_neg, feats_neg, dur_neg, y, exposure};
-    const TrainHyper h{(int)use_ab, lambda_ab, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
+    const TrainHyper h{(int)use_ab, lambda_ab, {l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps}};
     return train_launch_step(cfg, params, grads, adam_m, adam_v, step_before, c, nullptr, 0, n, n, kLossPairwise, h, loss_out, workspace,
                              (hipStream_t)stream);
 }
@@ -384,7 +306,7 @@ extern "C" int cirs_deepfm_train_epoch(const cirs_deepfm_cfg* cfg, float* params
     CIRS_REQUIRE(loss_kind == kLossPairwise || !use_ab, "deepfm train: the IPS and PD losses take no alpha/beta (their models are built without ab_columns)");
     const int64_t bmax = batch_size < n_order ? batch_size : n_order;
     const TrainCols c{uid_pos, pid_pos, feats_pos, dur_pos, uid_neg, pid_neg, feats_neg, dur_neg, y, score};
-    const TrainHyper h{(int)use_ab, loss_kind == kLossPairwise ? lambda_ab : 0.f, l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
+    const TrainHyper h{(int)use_ab, loss_kind == kLossPairwise ? lambda_ab : 0.f, {l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps}};
     return tstep::run_steps(params, grads, adam_m, adam_v, losses_out, workspace,
                             uid_pos && pid_pos && feats_pos && dur_pos && uid_neg && pid_neg && feats_neg && dur_neg && y && score, "null data column",
                             n_rows >= 1 && n_order >= 1 && batch_size >= 1 && (order || n_order <= n_rows), "empty data set, index array or batch",

@@ -14,24 +14,22 @@
 //                       forward, then the backward of all six: per-row DNN operands to global memory for the weight-gradient GEMMs
 //                       (dnn_main on 2n rows, dnn_ui on 4n rows), the sample's embedding / linear contributions, summed per key in a
 //                       fixed order in LDS, to the contribution tables.
-//   dw_gemm (small_gemm.h)  the seven dense weight gradients: fp32 MFMA row-slab partials, fixed-order sums.
-//   train_scatter, adam_l2_kernel (table_step.h)  ordered scatter of the contributions (five key spaces), regulariser + Adam.
+// This file holds the model's own parts: the parameter layout, the linear terms around the two towers, the six-forward / six-backward
+// sequence with its per-key sums, the loss, the workspace carve and the entry points.  Shared with deepfm_train.hip:
+//   deepfm_tower.h      the tower (FM cross term + DNN) forward / backward of one row, the feature contribution rows, the row lookup,
+//                       the loss means, a tower's weight-gradient GEMMs (dw_gemm of small_gemm.h: fp32 MFMA row-slab partials,
+//                       fixed-order sums)
+//   table_step.h        the workspace allocator, the ordered scatter of the contributions (five key spaces), regulariser + Adam
 // All reductions have a fixed order: two runs give identical bits.
-#include "small_gemm.h"
-#include "table_step.h"
-#include "train_step.h"
+#include "deepfm_tower.h"
 
 namespace cirs {
-
-constexpr int dH = 64;
-
-struct DiceNet { long w1, b1, w2, b2, last, out; };   // one DNN tower: [64, K] [64] [64, 64] [64] [64] [1]
 
 struct DiceLayout {  // offsets (floats) into the flat parameter / gradient / moment buffers
     long emb_user_int, emb_user_con, emb_photo_int, emb_photo_con, emb_feat;
     long lm_user_int, lm_user_con, lm_photo_int, lm_photo_con, lm_feat, lm_dense;   // linear_main
     long lu_user, lu_photo;                                                         // linear_ui
-    DiceNet main, ui;
+    TowerNet main, ui;
     long unused, total;                                                             // linear_model.* (no data gradient)
 };
 __host__ __device__ inline DiceLayout dice_layout(const cirs_dice_cfg& c) {
@@ -43,51 +41,20 @@ __host__ __device__ inline DiceLayout dice_layout(const cirs_dice_cfg& c) {
     L.lm_user_int = o; o += U; L.lm_user_con = o; o += U; L.lm_photo_int = o; o += I; L.lm_photo_con = o; o += I; L.lm_feat = o; o += F;
     L.lm_dense = o; o += 1;
     L.lu_user = o; o += U; L.lu_photo = o; o += I;
-    L.main.w1 = o; o += dH * (8 * E + 1); L.main.b1 = o; o += dH; L.main.w2 = o; o += dH * dH; L.main.b2 = o; o += dH;
-    L.main.last = o; o += dH; L.main.out = o; o += 1;
-    L.ui.w1 = o; o += dH * (2 * E); L.ui.b1 = o; o += dH; L.ui.w2 = o; o += dH * dH; L.ui.b2 = o; o += dH; L.ui.last = o; o += dH;
-    L.ui.out = o; o += 1;
+    L.main = tower_net(o, 8 * E + 1);
+    L.ui = tower_net(o, 2 * E);
     L.unused = o; o += 2 * U + 2 * I + F + 2;
     L.total = o;
     return L;
 }
 
-struct DiceRows {  // per-row outputs of one tower: R rows
-    float *X, *H1, *H2, *DA1, *DA2, *DY;   // [R,K] [R,64] [R,64] [R,64] [R,64] [R]
-};
 struct DiceOut {
-    DiceRows m, u;                       // main: 2n rows (positives first); ui: 4n rows (int pos | int neg | con pos | con neg)
+    TowerRows m, u;                      // main: 2n rows (positives first); ui: 4n rows (int pos | int neg | con pos | con neg)
     float* DUR;                          // [2n]
     float *CUI, *CUC, *CPI, *CPC, *CF;   // contributions [n,E+2] [n,E+2] [2n,E+2] [2n,E+2] [8n,E+1]
     int32_t *KUI, *KUC, *KPI, *KPC, *KF; // keys [n] [n] [2n] [2n] [8n]
     float* LP;                           // [n,4] per-sample loss terms {sq err, bpr_click, bpr_con, bpr_int}
 };
-
-// FM cross term and the two DNN layers of one tower by one wavefront over x [K] (NF * E embedding values, then the dense ones);
-// S / a1 / a2 stay in LDS for the backward.  -> 0.5 * cross + last . relu(a2) + out bias
-__device__ __forceinline__ float dice_tower_forward(const float* __restrict__ P, const DiceNet& N, int NF, int E, int K, int lane, const float* x,
-                                                    float* S, float* a1, float* a2) {
-    float cross = 0.f;
-    for (int e = lane; e < E; e += CIRS_WAVE) {
-        float s = 0.f, q = 0.f;
-        for (int fl = 0; fl < NF; ++fl) { const float v = x[fl * E + e]; s += v; q += v * v; }
-        S[e] = s;
-        cross += s * s - q;
-    }
-    cross = wave_sum_f32(cross);
-    float acc = P[N.b1 + lane];
-    const float* w1r = P + N.w1 + (size_t)lane * K;
-    for (int k = 0; k < K; ++k) acc = __builtin_fmaf(w1r[k], x[k], acc);
-    a1[lane] = acc;
-    __builtin_amdgcn_wave_barrier();
-    acc = P[N.b2 + lane];
-    const float* w2r = P + N.w2 + (size_t)lane * dH;
-    for (int k = 0; k < dH; ++k) acc = __builtin_fmaf(w2r[k], fmaxf(a1[k], 0.f), acc);
-    a2[lane] = acc;
-    const float dnn = wave_sum_f32(P[N.last + lane] * fmaxf(acc, 0.f));
-    __builtin_amdgcn_wave_barrier();
-    return 0.5f * cross + (dnn + P[N.out]);
-}
 
 // the main DeepFM (is_main=True) on one row: ids[0..3] = user_int, user_con, photo_int, photo_con
 __device__ __forceinline__ float dice_main_forward(const float* __restrict__ P, const DiceLayout& L, int E, const long* ids, const int32_t* f4,
@@ -109,7 +76,8 @@ __device__ __forceinline__ float dice_main_forward(const float* __restrict__ P, 
 #pragma unroll
     for (int q = 0; q < 4; ++q) logit += P[L.lm_feat + f4[q]];
     logit += dur * P[L.lm_dense];
-    return logit + dice_tower_forward(P, L.main, 8, E, K, lane, x, S, a1, a2);
+    const TowerOut t = tower_forward(P, L.main, 8, E, K, lane, x, S, a1, a2);
+    return logit + (0.5f * t.cross + t.dnn);
 }
 
 // the UI DeepFM (is_main=False) on one (user, photo) pair: embeddings from the tables at emb_u / emb_p, linear_ui indexed with the same ids
@@ -118,38 +86,8 @@ __device__ __forceinline__ float dice_ui_forward(const float* __restrict__ P, co
     for (int k = lane; k < 2 * E; k += CIRS_WAVE) x[k] = k < E ? P[emb_u + u * E + k] : P[emb_p + p * E + (k - E)];
     __builtin_amdgcn_wave_barrier();
     const float logit = P[L.lu_user + u] + P[L.lu_photo + p];
-    return logit + dice_tower_forward(P, L.ui, 2, E, 2 * E, lane, x, S, a1, a2);
-}
-
-// backward of one tower row r given dy: writes the row's GEMM operands; dxs[k], k < NF * E = d loss / d x[k] (DNN input gradient + FM)
-__device__ __forceinline__ void dice_tower_backward(const float* __restrict__ P, const DiceNet& N, int NF, int E, int K, float dy, int lane, size_t r,
-                                                    const float* x, const float* S, const float* a1, const float* a2, float* t64, float* dxs,
-                                                    const DiceRows& o) {
-    // da2 = dy * last * relu'(a2); dh1 = W2^T da2; da1 = dh1 * relu'(a1); dx = W1^T da1
-    const float da2 = a2[lane] > 0.f ? dy * P[N.last + lane] : 0.f;
-    o.DA2[r * dH + lane] = da2;
-    o.H2[r * dH + lane] = fmaxf(a2[lane], 0.f);
-    o.H1[r * dH + lane] = fmaxf(a1[lane], 0.f);
-    t64[lane] = da2;
-    __builtin_amdgcn_wave_barrier();
-    float dh1 = 0.f;
-    for (int q = 0; q < dH; ++q) dh1 = __builtin_fmaf(P[N.w2 + (size_t)q * dH + lane], t64[q], dh1);
-    const float da1 = a1[lane] > 0.f ? dh1 : 0.f;
-    o.DA1[r * dH + lane] = da1;
-    __builtin_amdgcn_wave_barrier();
-    t64[lane] = da1;
-    __builtin_amdgcn_wave_barrier();
-    for (int k = lane; k < K; k += CIRS_WAVE) {
-        o.X[r * K + k] = x[k];
-        if (k < NF * E) {
-            float dx = 0.f;
-            for (int q = 0; q < dH; ++q) dx = __builtin_fmaf(P[N.w1 + (size_t)q * K + k], t64[q], dx);
-            // FM: d/dv_f,e of 0.5 * sum_e (S_e^2 - Q_e) = S_e - v_f,e
-            dxs[k] = __builtin_fmaf(dy, S[k % E] - x[k], dx);
-        }
-    }
-    if (lane == 0) o.DY[r] = dy;
-    __builtin_amdgcn_wave_barrier();
+    const TowerOut t = tower_forward(P, L.ui, 2, E, 2 * E, lane, x, S, a1, a2);
+    return logit + (0.5f * t.cross + t.dnn);
 }
 
 struct DiceCols {  // the data set in column form (x16 of the reference split by column; feats [n_rows,4])
@@ -159,9 +97,9 @@ struct DiceCols {  // the data set in column form (x16 of the reference split by
 };
 
 // LDS floats of one wavefront
-__host__ __device__ inline int dice_main_lds(int E) { return (8 * E + 2) + E + 2 * dH; }
-__host__ __device__ inline int dice_ui_lds(int E) { return 2 * E + E + 2 * dH; }
-__host__ __device__ inline int dice_wave_lds(int E) { return 2 * dice_main_lds(E) + 4 * dice_ui_lds(E) + dH + 8 * E + 6 * E + 8; }
+__host__ __device__ inline int dice_main_lds(int E) { return (8 * E + 2) + E + 2 * kTowerH; }
+__host__ __device__ inline int dice_ui_lds(int E) { return 2 * E + E + 2 * kTowerH; }
+__host__ __device__ inline int dice_wave_lds(int E) { return 2 * dice_main_lds(E) + 4 * dice_ui_lds(E) + kTowerH + 8 * E + 6 * E + 8; }
 
 __global__ __launch_bounds__(256) void dice_rows_kernel(cirs_dice_cfg cfg, const float* __restrict__ P, DiceCols c, const int64_t* __restrict__ order,
                                                         long r0, long n_rows, int n, DiceOut o) {
@@ -174,15 +112,14 @@ __global__ __launch_bounds__(256) void dice_rows_kernel(cirs_dice_cfg cfg, const
     float* base = smem + (size_t)wv * dice_wave_lds(E);
     float *xm[2], *Sm[2], *a1m[2], *a2m[2], *xu[4], *Su[4], *a1u[4], *a2u[4];
 #pragma unroll
-    for (int q = 0; q < 2; ++q) { xm[q] = base; Sm[q] = xm[q] + 8 * E + 2; a1m[q] = Sm[q] + E; a2m[q] = a1m[q] + dH; base += dice_main_lds(E); }
+    for (int q = 0; q < 2; ++q) { xm[q] = base; Sm[q] = xm[q] + 8 * E + 2; a1m[q] = Sm[q] + E; a2m[q] = a1m[q] + kTowerH; base += dice_main_lds(E); }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) { xu[q] = base; Su[q] = xu[q] + 2 * E; a1u[q] = Su[q] + E; a2u[q] = a1u[q] + dH; base += dice_ui_lds(E); }
+    for (int q = 0; q < 4; ++q) { xu[q] = base; Su[q] = xu[q] + 2 * E; a1u[q] = Su[q] + E; a2u[q] = a1u[q] + kTowerH; base += dice_ui_lds(E); }
     float* t64 = base;
-    float* dxs = t64 + dH;
+    float* dxs = t64 + kTowerH;
     float* acc = dxs + 8 * E;   // [6, E]: user_int | user_con | photo_int pos | photo_con pos | photo_int neg | photo_con neg
-    long row = order ? (long)order[r0 + i] : r0 + i;
-    const bool bad_row = row < 0 || row >= n_rows;   // an index outside the data set: no read there, the step's loss becomes NaN
-    if (bad_row) row = 0;
+    bool bad_row;
+    const long row = step_row(order, r0, i, n_rows, bad_row);
     const long idp[4] = {(long)c.uid_int[row], (long)c.uid_con[row], (long)c.pid_int[row], (long)c.pid_con[row]};
     const long idn[4] = {idp[0], idp[1], (long)c.pid_int_neg[row], (long)c.pid_con_neg[row]};
     int32_t fp[4], fn[4];
@@ -216,35 +153,25 @@ __global__ __launch_bounds__(256) void dice_rows_kernel(cirs_dice_cfg cfg, const
     }
     // ---- backward of the six forwards; the embedding rows one key receives from several forwards are added here, in this order ----
     const size_t nn = (size_t)n;
-    dice_tower_backward(P, L.main, 8, E, Km, dyp, lane, (size_t)i, xm[0], Sm[0], a1m[0], a2m[0], t64, dxs, o.m);
+    tower_backward(P, L.main, 8, E, Km, dyp, lane, (size_t)i, xm[0], Sm[0], a1m[0], a2m[0], t64, dxs, o.m);
     for (int e = lane; e < 4 * E; e += CIRS_WAVE) acc[e] = dxs[e];                        // user_int, user_con, photo_int pos, photo_con pos
-    for (int q = 0; q < 4; ++q) {
-        const int fid = fp[q];
-        for (int e = lane; e < E + 1; e += CIRS_WAVE)   // padding_idx = 0: the embedding row gets no gradient, the 1-d weight does
-            o.CF[((size_t)i * 4 + q) * (E + 1) + e] = e < E ? (fid == 0 ? 0.f : dxs[(4 + q) * E + e]) : dyp;
-        if (lane == 0) o.KF[(size_t)i * 4 + q] = fid;
-    }
+    write_feat_contrib(o.CF, o.KF, (size_t)i, E, fp, dxs, 4, dyp, lane);
     __builtin_amdgcn_wave_barrier();
-    dice_tower_backward(P, L.main, 8, E, Km, dyn, lane, nn + i, xm[1], Sm[1], a1m[1], a2m[1], t64, dxs, o.m);
+    tower_backward(P, L.main, 8, E, Km, dyn, lane, nn + i, xm[1], Sm[1], a1m[1], a2m[1], t64, dxs, o.m);
     for (int e = lane; e < 2 * E; e += CIRS_WAVE) { acc[e] += dxs[e]; acc[4 * E + e] = dxs[2 * E + e]; }
-    for (int q = 0; q < 4; ++q) {
-        const int fid = fn[q];
-        for (int e = lane; e < E + 1; e += CIRS_WAVE)
-            o.CF[((nn + i) * 4 + q) * (E + 1) + e] = e < E ? (fid == 0 ? 0.f : dxs[(4 + q) * E + e]) : dyn;
-        if (lane == 0) o.KF[(nn + i) * 4 + q] = fid;
-    }
+    write_feat_contrib(o.CF, o.KF, nn + i, E, fn, dxs, 4, dyn, lane);
     if (lane == 0) { o.DUR[i] = dp; o.DUR[nn + i] = dn; }
     __builtin_amdgcn_wave_barrier();
-    dice_tower_backward(P, L.ui, 2, E, Ku, -dyi, lane, (size_t)i, xu[0], Su[0], a1u[0], a2u[0], t64, dxs, o.u);
+    tower_backward(P, L.ui, 2, E, Ku, -dyi, lane, (size_t)i, xu[0], Su[0], a1u[0], a2u[0], t64, dxs, o.u);
     for (int e = lane; e < E; e += CIRS_WAVE) { acc[e] += dxs[e]; acc[2 * E + e] += dxs[E + e]; }
     __builtin_amdgcn_wave_barrier();
-    dice_tower_backward(P, L.ui, 2, E, Ku, dyi, lane, nn + i, xu[1], Su[1], a1u[1], a2u[1], t64, dxs, o.u);
+    tower_backward(P, L.ui, 2, E, Ku, dyi, lane, nn + i, xu[1], Su[1], a1u[1], a2u[1], t64, dxs, o.u);
     for (int e = lane; e < E; e += CIRS_WAVE) { acc[e] += dxs[e]; acc[4 * E + e] += dxs[E + e]; }
     __builtin_amdgcn_wave_barrier();
-    dice_tower_backward(P, L.ui, 2, E, Ku, -dyc, lane, 2 * nn + i, xu[2], Su[2], a1u[2], a2u[2], t64, dxs, o.u);
+    tower_backward(P, L.ui, 2, E, Ku, -dyc, lane, 2 * nn + i, xu[2], Su[2], a1u[2], a2u[2], t64, dxs, o.u);
     for (int e = lane; e < E; e += CIRS_WAVE) { acc[E + e] += dxs[e]; acc[3 * E + e] += dxs[E + e]; }
     __builtin_amdgcn_wave_barrier();
-    dice_tower_backward(P, L.ui, 2, E, Ku, dyc, lane, 3 * nn + i, xu[3], Su[3], a1u[3], a2u[3], t64, dxs, o.u);
+    tower_backward(P, L.ui, 2, E, Ku, dyc, lane, 3 * nn + i, xu[3], Su[3], a1u[3], a2u[3], t64, dxs, o.u);
     for (int e = lane; e < E; e += CIRS_WAVE) { acc[E + e] += dxs[e]; acc[5 * E + e] += dxs[E + e]; }
     __builtin_amdgcn_wave_barrier();
     // contribution rows: [d embedding row | d linear_main weight | d linear_ui weight]
@@ -265,26 +192,12 @@ __global__ __launch_bounds__(256) void dice_rows_kernel(cirs_dice_cfg cfg, const
     }
 }
 
-// batch loss terms: fixed-order sums of the per-sample terms -> {loss, loss_y, bpr_click, bpr_con, bpr_int}
+// batch loss terms -> {loss, loss_y, bpr_click, bpr_con, bpr_int}
 __global__ __launch_bounds__(256) void dice_loss_kernel(const float* __restrict__ LP, int n, float* __restrict__ loss_out) {
-    __shared__ float sh[4][256];
-    const int tid = threadIdx.x;
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < n; i += 256)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[q] += LP[(size_t)i * 4 + q];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) sh[q][tid] = a[q];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) sh[q][tid] += sh[q][tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const float inv = 1.0f / (float)n;
-        const float ly = sh[0][0] * inv, click = sh[1][0] * inv, con = sh[2][0] * inv, in = sh[3][0] * inv;
+    float m[4];
+    loss_means4(LP, n, m);
+    if (threadIdx.x == 0) {
+        const float ly = m[0], click = m[1], con = m[2], in = m[3];
         loss_out[0] = ((ly + click) + con) + in;
         loss_out[1] = ly; loss_out[2] = click; loss_out[3] = con; loss_out[4] = in;
     }
@@ -301,7 +214,7 @@ __global__ __launch_bounds__(256) void dice_forward_kernel(cirs_dice_cfg cfg, co
     const long i = (long)blockIdx.x * 4 + wv;
     if (i >= n) return;
     float* x = smem + (size_t)wv * dice_main_lds(E);
-    float *S = x + 8 * E + 2, *a1 = S + E, *a2 = a1 + dH;
+    float *S = x + 8 * E + 2, *a1 = S + E, *a2 = a1 + kTowerH;
     long u = uid[i], p = pid[i];
     int32_t f4[4];
 #pragma unroll
@@ -320,55 +233,42 @@ __global__ __launch_bounds__(256) void dice_forward_kernel(cirs_dice_cfg cfg, co
     if (lane == 0) out[i] = bad ? __builtin_nanf("") : y;
 }
 
-static size_t dice_partial_floats(long n, int E) {
-    const size_t a = dwg_partial_floats(2 * n, dH, 8 * E + 1), b = dwg_partial_floats(4 * n, dH, dH > 2 * E ? dH : 2 * E);
-    return a > b ? a : b;
-}
-
-static size_t dice_ws_floats(const cirs_dice_cfg* cfg, long n) {
-    const long E = cfg->emb_dim, Km = 8 * E + 1, Ku = 2 * E, Rm = 2 * n, Ru = 4 * n;
-    size_t f = 0;
-    f += (size_t)Rm * Km + 4 * (size_t)Rm * dH + 2 * (size_t)Rm;       // main X, H1, H2, DA1, DA2, DY, DUR
-    f += (size_t)Ru * Ku + 4 * (size_t)Ru * dH + (size_t)Ru;           // ui X, H1, H2, DA1, DA2, DY
-    f += 6 * (size_t)n * (E + 2) + 8 * (size_t)n * (E + 1);            // CUI, CUC, CPI, CPC, CF
-    f += 6 * (size_t)n + 8 * (size_t)n;                                // keys
-    f += 4 * (size_t)n + 64;                                           // LP
-    f += dice_partial_floats(n, (int)E) + 64;
-    f += kRegBlocks + 64;
-    f += train_sort_bytes(8 * n) / 4 + 64;
-    return f + 64 * 32;
+// the workspace of a step on n samples: the size query runs this carve without a base pointer, the launch on the caller's workspace
+struct DiceWs { DiceOut o; StepScratch x; };
+static DiceWs dice_carve(Bump& w, int E, size_t n) {
+    const size_t Rm = 2 * n, Ru = 4 * n;
+    const int Km = 8 * E + 1, Ku = 2 * E;
+    DiceWs t;
+    DiceOut& o = t.o;
+    o.m = tower_rows(w, Rm, Km); o.DUR = w.take(Rm);
+    o.u = tower_rows(w, Ru, Ku);
+    o.CUI = w.take(n * (E + 2)); o.CUC = w.take(n * (E + 2)); o.CPI = w.take(Rm * (E + 2)); o.CPC = w.take(Rm * (E + 2));
+    o.CF = w.take(8 * n * (E + 1));
+    o.KUI = (int32_t*)w.take(n); o.KUC = (int32_t*)w.take(n); o.KPI = (int32_t*)w.take(Rm); o.KPC = (int32_t*)w.take(Rm);
+    o.KF = (int32_t*)w.take(8 * n);
+    o.LP = w.take(4 * n + 8);
+    const size_t pm = tower_partial_floats(Rm, Km), pu = tower_partial_floats(Ru, Ku);
+    t.x = step_scratch(w, pm > pu ? pm : pu, 8 * n);
+    return t;
 }
 
 static int dice_check_cfg(const cirs_dice_cfg* cfg) {
-    if (cfg->hidden != dH) return fail(CIRS_E_UNSUPPORTED, "dice: hidden == 64 only");
+    if (cfg->hidden != kTowerH) return fail(CIRS_E_UNSUPPORTED, "dice: hidden == 64 only");
     if (cfg->emb_dim != 8 && cfg->emb_dim != 16 && cfg->emb_dim != 32) return fail(CIRS_E_UNSUPPORTED, "dice: emb_dim must be 8, 16 or 32");
     CIRS_REQUIRE(cfg->n_user_vocab >= 1 && cfg->n_item_vocab >= 1 && cfg->n_feat_vocab >= 1, "dice: empty vocabulary");
     return CIRS_OK;
 }
 
-struct DiceHyper { float l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps; };
-
 // the launches of one step on the n samples order[r0 .. r0 + n) of the columns (rows r0 .. r0 + n - 1 when order is null)
 static int dice_launch_step(const cirs_dice_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t step_before,
-                            const DiceCols& c, const int64_t* order, long r0, long n_rows, int n, const DiceHyper& h, float* loss_out,
+                            const DiceCols& c, const int64_t* order, long r0, long n_rows, int n, const TableHyper& h, float* loss_out,
                             void* workspace, hipStream_t s) {
     const int E = cfg->emb_dim, Km = 8 * E + 1, Ku = 2 * E, Rm = 2 * n, Ru = 4 * n;
     const DiceLayout L = dice_layout(*cfg);
-    float* p = (float*)workspace;
-    auto take = [&](size_t cnt) { float* r = p; p += (cnt + 3) & ~(size_t)3; return r; };
-    DiceOut o;
-    o.m.X = take((size_t)Rm * Km); o.m.H1 = take((size_t)Rm * dH); o.m.H2 = take((size_t)Rm * dH); o.m.DA1 = take((size_t)Rm * dH);
-    o.m.DA2 = take((size_t)Rm * dH); o.m.DY = take(Rm); o.DUR = take(Rm);
-    o.u.X = take((size_t)Ru * Ku); o.u.H1 = take((size_t)Ru * dH); o.u.H2 = take((size_t)Ru * dH); o.u.DA1 = take((size_t)Ru * dH);
-    o.u.DA2 = take((size_t)Ru * dH); o.u.DY = take(Ru);
-    o.CUI = take((size_t)n * (E + 2)); o.CUC = take((size_t)n * (E + 2)); o.CPI = take((size_t)Rm * (E + 2)); o.CPC = take((size_t)Rm * (E + 2));
-    o.CF = take((size_t)8 * n * (E + 1));
-    o.KUI = (int32_t*)take(n); o.KUC = (int32_t*)take(n); o.KPI = (int32_t*)take(Rm); o.KPC = (int32_t*)take(Rm); o.KF = (int32_t*)take((size_t)8 * n);
-    o.LP = take((size_t)4 * n + 8);
-    float* partial = take(dice_partial_floats(n, E) + 64);
-    float* regp = take(kRegBlocks + 8);
-    const size_t sort_bytes = train_sort_bytes(8L * n);
-    void* sort_ws = (void*)take(sort_bytes / 4 + 64);
+    Bump w{(float*)workspace};
+    const DiceWs ws = dice_carve(w, E, n);
+    const DiceOut& o = ws.o;
+    float* partial = ws.x.partial;
     // the data gradient is written sparsely (touched table rows, dense layers): start from zero
     CIRS_HIP(hipMemsetAsync(grads, 0, sizeof(float) * (size_t)L.total, s));
     const size_t shmem = sizeof(float) * 4 * (size_t)dice_wave_lds(E);
@@ -376,15 +276,11 @@ static int dice_launch_step(const cirs_dice_cfg* cfg, float* params, float* grad
     CIRS_CHECK_LAUNCH("dice_rows_kernel");
     hipLaunchKernelGGL(dice_loss_kernel, dim3(1), dim3(256), 0, s, (const float*)o.LP, n, loss_out);
     // dense layers: dW = dY^T X over the 2n main rows and the 4n ui rows
-    launch_dw_gemm(o.m.DA1, dH, o.m.X, Km, Rm, dH, Km, grads + L.main.w1, grads + L.main.b1, partial, s);
-    launch_dw_gemm(o.m.DA2, dH, o.m.H1, dH, Rm, dH, dH, grads + L.main.w2, grads + L.main.b2, partial, s);
-    launch_dw_gemm(o.m.DY, 1, o.m.H2, dH, Rm, 1, dH, grads + L.main.last, grads + L.main.out, partial, s);
+    launch_tower_dw(o.m, Rm, Km, grads, L.main, true, partial, s);
     launch_dw_gemm(o.m.DY, 1, o.DUR, 1, Rm, 1, 1, grads + L.lm_dense, nullptr, partial, s);
-    launch_dw_gemm(o.u.DA1, dH, o.u.X, Ku, Ru, dH, Ku, grads + L.ui.w1, grads + L.ui.b1, partial, s);
-    launch_dw_gemm(o.u.DA2, dH, o.u.H1, dH, Ru, dH, dH, grads + L.ui.w2, grads + L.ui.b2, partial, s);
     // out_ui.bias is in both forwards of every BPR difference: its data gradient is identically zero (the reference's cancels exactly),
     // so it is not summed from rounded terms -- Adam would turn that noise into +-lr steps
-    launch_dw_gemm(o.u.DY, 1, o.u.H2, dH, Ru, 1, dH, grads + L.ui.last, nullptr, partial, s);
+    launch_tower_dw(o.u, Ru, Ku, grads, L.ui, false, partial, s);
     CIRS_CHECK_LAUNCH("dice train dW");
     // table rows; linear_ui's two tables take the int pass, then the con pass on top of it
     const int U = cfg->n_user_vocab, I = cfg->n_item_vocab;
@@ -393,26 +289,18 @@ static int dice_launch_step(const cirs_dice_cfg* cfg, float* params, float* grad
     ScatterDst dpi{{grads + L.emb_photo_int, grads + L.lm_photo_int, grads + L.lu_photo}, {E, 1, 1}, {0, 0, 0}};
     ScatterDst dpc{{grads + L.emb_photo_con, grads + L.lm_photo_con, grads + L.lu_photo}, {E, 1, 1}, {0, 0, 1}};
     ScatterDst df{{grads + L.emb_feat, grads + L.lm_feat, nullptr}, {E, 1, 0}, {0, 0, 0}};
-    if (int rc = train_scatter(o.KUI, o.CUI, n, E + 2, U, dui, sort_ws, sort_bytes, s)) return rc;
-    if (int rc = train_scatter(o.KUC, o.CUC, n, E + 2, U, duc, sort_ws, sort_bytes, s)) return rc;
-    if (int rc = train_scatter(o.KPI, o.CPI, Rm, E + 2, I, dpi, sort_ws, sort_bytes, s)) return rc;
-    if (int rc = train_scatter(o.KPC, o.CPC, Rm, E + 2, I, dpc, sort_ws, sort_bytes, s)) return rc;
-    if (int rc = train_scatter(o.KF, o.CF, 8 * n, E + 1, cfg->n_feat_vocab, df, sort_ws, sort_bytes, s)) return rc;
-    // regulariser + Adam (torch.optim.Adam, bias corrections from the step count)
+    if (int rc = train_scatter(o.KUI, o.CUI, n, E + 2, U, dui, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KUC, o.CUC, n, E + 2, U, duc, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KPI, o.CPI, Rm, E + 2, I, dpi, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KPC, o.CPC, Rm, E + 2, I, dpc, ws.x.sort, ws.x.sort_bytes, s)) return rc;
+    if (int rc = train_scatter(o.KF, o.CF, 8 * n, E + 1, cfg->n_feat_vocab, df, ws.x.sort, ws.x.sort_bytes, s)) return rc;
     L2Segs segs;
     segs.n = 3;
     for (int q = 0; q < 6; ++q) { segs.end[q] = L.total; segs.c[q] = h.l2_linear + h.l2_all; }
     segs.end[0] = L.lm_user_int;  segs.c[0] = h.l2_embedding + h.l2_all;   // embedding_dict.*            (core/user_model.py:57)
     segs.end[1] = L.unused;       segs.c[1] = h.l2_all;                      // linear_main, linear_ui, both towers (user_model_DICE.py:94)
     segs.end[2] = L.total;        segs.c[2] = h.l2_linear + h.l2_all;      // linear_model.* (unused in forward, still decays; :58)
-    const double t = (double)(step_before + 1);
-    const float step_size = (float)((double)h.lr / (1.0 - pow((double)h.beta1, t)));
-    const float bc2s = (float)sqrt(1.0 - pow((double)h.beta2, t));
-    hipLaunchKernelGGL(adam_l2_kernel, dim3(kRegBlocks), dim3(256), 0, s, params, grads, adam_m, adam_v, L.total, segs, h.beta1, h.beta2, h.eps,
-                       step_size, bc2s, regp);
-    hipLaunchKernelGGL(reg_final_kernel, dim3(1), dim3(256), 0, s, (const float*)regp, loss_out, 5);
-    CIRS_CHECK_LAUNCH("adam_l2_kernel");
-    return CIRS_OK;
+    return table_adam_step(params, grads, adam_m, adam_v, L.total, segs, h, step_before, ws.x.regp, loss_out, 5, s);
 }
 
 }  // namespace cirs
@@ -424,7 +312,9 @@ extern "C" int64_t cirs_dice_train_param_count(const cirs_dice_cfg* cfg) {
 
 extern "C" int64_t cirs_dice_train_workspace_bytes(const cirs_dice_cfg* cfg, int32_t n) {
     if (!cfg || n <= 0) return 0;
-    return (int64_t)cirs::dice_ws_floats(cfg, n) * 4;
+    cirs::Bump w{nullptr};
+    cirs::dice_carve(w, cfg->emb_dim, n);
+    return (int64_t)(w.used * sizeof(float));
 }
 
 extern "C" int cirs_dice_train_epoch(const cirs_dice_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t step_before,
@@ -439,7 +329,7 @@ extern "C" int cirs_dice_train_epoch(const cirs_dice_cfg* cfg, float* params, fl
     if (int rc = dice_check_cfg(cfg)) return rc;
     const int64_t bmax = batch_size < n_order ? batch_size : n_order;
     const DiceCols c{uid_int, uid_con, pid_int, pid_con, feats_pos, dur_pos, pid_int_neg, pid_con_neg, feats_neg, dur_neg, y, score};
-    const DiceHyper h{l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
+    const TableHyper h{l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps};
     return tstep::run_steps(params, grads, adam_m, adam_v, losses_out, workspace,
                             uid_int && uid_con && pid_int && pid_con && feats_pos && dur_pos && pid_int_neg && pid_con_neg && feats_neg && dur_neg &&
                                 y && score, "null data column",

@@ -1,18 +1,33 @@
 // table_step.h -- the back half of an optimiser step over embedding tables, shared by the Kuaishou trainers (deepfm_train.hip: the
-// pairwise / IPS / PD DeepFM; dice_train.hip: the DICE model).  Each trainer keeps its own row kernel and per-row contribution tables;
-// what follows them exists once, here:
+// pairwise / IPS / PD DeepFM; dice_train.hip: the DICE model).  Each trainer keeps its own row kernel and per-row contribution tables
+// (the tower both row kernels run is in deepfm_tower.h); what follows them exists once, here:
+//   Bump                the workspace as a bump allocator: a trainer writes its carve once and runs it without a base pointer for the
+//                       size query and on the real pointer for the launches.
 //   train_scatter       stable radix sort of (key, row) + ordered segment sums (no float atomics) of a contribution table [R, W] into up
 //                       to three destination tables, each taking a column range of the contribution row; a destination either takes the
 //                       segment sum (the gradient buffer starts from zero) or, marked `add`, adds it to what an earlier pass left.
 //   adam_l2_kernel      g += 2 * l2_c * p (the regulariser is dense: every row of every table decays), Adam, and the regulariser's
-//                       value as per-workgroup partials; reg_final_kernel sums them in index order into one slot of the loss vector.
+//                       value as per-workgroup partials; reg_final_kernel sums them in index order into one slot of the loss vector;
+//                       table_adam_step launches the pair with the bias corrections of the step count.
 // Every sum has a fixed order: two runs give identical bits.
 #pragma once
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
+#include "train_step.h"
 
 namespace cirs {
+// ---- the workspace: floats handed out in order, each buffer a multiple of 16 bytes; base == nullptr only counts ----
+struct Bump {
+    float* base;
+    size_t used = 0;
+    float* take(size_t cnt) {
+        float* r = base ? base + used : nullptr;
+        used += (cnt + 3) & ~(size_t)3;
+        return r;
+    }
+};
+
 // ---- sorted scatter: contributions [R, W] keyed by row id -> up to three destination tables -----------------------
 static __global__ __launch_bounds__(256) void train_keys_kernel(const int32_t* __restrict__ keys, int R, int n_table, uint32_t* __restrict__ k_out,
                                                          int32_t* __restrict__ rows) {
@@ -130,6 +145,32 @@ static __global__ __launch_bounds__(256) void reg_final_kernel(const float* __re
         __syncthreads();
     }
     if (tid == 0) loss_out[slot] = sh[0];
+}
+
+// what both trainers carve behind their row kernel's outputs: the dW slab partials, the regulariser partials, the sort scratch of the
+// largest key space
+struct StepScratch { float *partial, *regp; void* sort; size_t sort_bytes; };
+inline StepScratch step_scratch(Bump& w, size_t partial_floats, long max_keys) {
+    StepScratch t;
+    t.partial = w.take(partial_floats + 64);
+    t.regp = w.take(kRegBlocks + 8);
+    t.sort_bytes = train_sort_bytes(max_keys);
+    t.sort = (void*)w.take(t.sort_bytes / 4 + 64);
+    return t;
+}
+
+struct TableHyper { float l2_embedding, l2_linear, l2_all, lr, beta1, beta2, eps; };
+
+// regulariser + Adam (torch.optim.Adam, bias corrections from the step count) over the `total` parameters; the regulariser's value goes
+// to loss_out[reg_slot].  regp: kRegBlocks floats
+static int table_adam_step(float* params, float* grads, float* adam_m, float* adam_v, long total, const L2Segs& segs, const TableHyper& h,
+                           int64_t step_before, float* regp, float* loss_out, int reg_slot, hipStream_t s) {
+    const tstep::AdamArgs a = tstep::adam_args(h.lr, h.beta1, h.beta2, h.eps, h.l2_linear, h.l2_all, step_before);
+    hipLaunchKernelGGL(adam_l2_kernel, dim3(kRegBlocks), dim3(256), 0, s, params, grads, adam_m, adam_v, total, segs, a.beta1, a.beta2, a.eps,
+                       a.step_size, a.bc2s, regp);
+    hipLaunchKernelGGL(reg_final_kernel, dim3(1), dim3(256), 0, s, (const float*)regp, loss_out, reg_slot);
+    CIRS_CHECK_LAUNCH("adam_l2_kernel");
+    return CIRS_OK;
 }
 
 }  // namespace cirs
