@@ -114,6 +114,7 @@ __device__ __forceinline__ long step_row(const int64_t* __restrict__ order, long
 
 // means over the n samples of the four per-sample loss terms LP [n,4] by one workgroup of 256: fixed-order sums; m valid in thread 0
 __device__ __forceinline__ void loss_means4(const float* __restrict__ LP, int n, float* m) {
+    // (four sums share the nine barriers of one tree in block_sum's order: as four block_sum calls the DICE epoch took 1531 us per step against 1524 us, profiles/r09_optim_refactor_ab.md)
     __shared__ float sh[4][256];
     const int tid = threadIdx.x;
     float a[4] = {0.f, 0.f, 0.f, 0.f};

@@ -17,6 +17,7 @@
 // logits in the backward kernel) on the fp32 MFMA pipe (157 TF peak).  HBM traffic is Wa (2.7 MB) + dWa partials
 // (n_row_blocks x 2.7 MB) + dH2 partials (n_chunks x mb x 256 B = 22 MB): MFMA-bound.
 #include "internal.h"
+#include "optim.h"
 #include "bf16x6.h"
 #include "small_gemm.h"
 #include "permutation.h"
@@ -133,9 +134,9 @@ __global__ __launch_bounds__(256) void compact_obs_kernel(cirs_traj traj, cirs_p
 }
 
 // single workgroup, fixed-order float64 reductions
-// (one workgroup of 1024 threads; red: 1024 doubles of LDS, s_mean: one more)
+// (one workgroup of 1024 threads; red: 1024 doubles of LDS)
 __device__ __forceinline__ void returns_block(const cirs_ppo_cfg& cfg, const double* __restrict__ unnorm_ret, int N, double* __restrict__ rms_state,
-                                              float* __restrict__ ret_out, double* red, double& s_mean) {
+                                              float* __restrict__ ret_out, double* red) {
     const int tid = threadIdx.x;
     double acc = 0.0;
     // eight loads in flight per pass, added in the same (index) order as a plain loop
@@ -147,15 +148,7 @@ __device__ __forceinline__ void returns_block(const cirs_ppo_cfg& cfg, const dou
         for (int u = 0; u < 8; ++u)
             if (i0 + u * 1024 < N) acc += x8[u];
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) s_mean = red[0] / (double)N;
-    __syncthreads();
-    const double mean = s_mean;
+    const double mean = block_sum<1024>(acc, red) / (double)N;
     acc = 0.0;
     for (int i0 = tid; i0 < N; i0 += 8 * 1024) {
         double x8[8];
@@ -165,14 +158,7 @@ __device__ __forceinline__ void returns_block(const cirs_ppo_cfg& cfg, const dou
         for (int u = 0; u < 8; ++u)
             if (i0 + u * 1024 < N) { const double d = x8[u] - mean; acc += d * d; }
     }
-    __syncthreads();
-    red[tid] = acc;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double var = red[0] / (double)N;  // np.var: population variance
+    const double var = block_sum<1024>(acc, red) / (double)N;  // np.var: population variance
     const double scale = cfg.rew_norm ? sqrt(rms_state[1] + 1e-8) : 1.0;  // OLD variance (a2c.py:101-103)
     for (int i0 = tid; i0 < N; i0 += 8 * 1024) {
         double x8[8];
@@ -195,8 +181,7 @@ __global__ __launch_bounds__(1024) void returns_kernel(cirs_ppo_cfg cfg, const d
                                                        double* __restrict__ rms_state, float* __restrict__ ret_out,
                                                        const int32_t* __restrict__ n_dev = nullptr) {
     __shared__ double red[1024];
-    __shared__ double s_mean;
-    returns_block(cfg, unnorm_ret, n_dev ? *n_dev : N_arg, rms_state, ret_out, red, s_mean);
+    returns_block(cfg, unnorm_ret, n_dev ? *n_dev : N_arg, rms_state, ret_out, red);
 }
 // process_fn's last launch (cirs_ppo_prepare_async): three independent jobs behind gae_kernel on disjoint workgroups of 1024 threads -- the return
 // normalisation (workgroup 0: returns_kernel's code), the compaction of the observations (compact_obs_kernel's, 1024 elements per workgroup) and, n_perm > 0,
@@ -206,10 +191,9 @@ __global__ __launch_bounds__(1024) void prepare_tail_kernel(cirs_ppo_cfg cfg, ci
                                                             double* __restrict__ rms_state, const int32_t* __restrict__ n_dev, int B, int S, int n_compact,
                                                             PermKeys keys, int n_perm, long perm_upper, int32_t* __restrict__ perm_out) {
     __shared__ double red[1024];
-    __shared__ double s_mean;
     const int N = *n_dev;
     const int b = blockIdx.x;
-    if (b == 0) { returns_block(cfg, unnorm_ret, N, rms_state, out.ret, red, s_mean); return; }
+    if (b == 0) { returns_block(cfg, unnorm_ret, N, rms_state, out.ret, red); return; }
     if (b <= n_compact) { compact_obs_elem(traj, out, (long)(b - 1) * 1024 + threadIdx.x, N, B, S); return; }
     const long g = (long)(b - 1 - n_compact) * 1024 + threadIdx.x;
     const int c = (int)(g / perm_upper);
@@ -372,7 +356,6 @@ __host__ inline MbView carve(void* ws, int n_pad, int I, int S) {
 // normalisation is off).
 __device__ __forceinline__ void adv_stats_block(const float* __restrict__ adv_flat, const int32_t* __restrict__ idx, int m,
                                                 int enable, float* __restrict__ red, float* sh /* [256] */) {
-    __shared__ float s_mean;
     const int tid = threadIdx.x;
     if (!enable) {
         if (tid == 0) { red[0] = 0.f; red[1] = 1.f; }
@@ -380,28 +363,14 @@ __device__ __forceinline__ void adv_stats_block(const float* __restrict__ adv_fl
     }
     float acc = 0.f;
     for (int i = tid; i < m; i += 256) acc += adv_flat[idx[i]];
-    sh[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) s_mean = sh[0] / (float)m;
-    __syncthreads();
-    const float mean = s_mean;
+    const float mean = block_sum<256>(acc, sh) / (float)m;
     acc = 0.f;
     for (int i = tid; i < m; i += 256) {
         const float d = adv_flat[idx[i]] - mean;
         acc += d * d;
     }
-    __syncthreads();
-    sh[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) { red[0] = mean; red[1] = sqrtf(sh[0] / (float)(m - 1)); }
+    const float ssq = block_sum<256>(acc, sh);
+    if (tid == 0) { red[0] = mean; red[1] = sqrtf(ssq / (float)(m - 1)); }
 }
 
 // One minibatch row's loss terms and backward coefficients (ppo.py:183-212) from its logit statistics: z = logit of the taken action,
@@ -2045,18 +2014,13 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(float* __restrict__ 
             acc += (e < n_trunk ? 2.0f : 1.0f) * x * x;
         }
     }
-    sh[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = sh[0];
+    acc = block_sum<256>(acc, sh);
+    if (tid == 0) partial[blockIdx.x] = acc;
 }
 // stage 2: one workgroup: norm, clip coefficient, entropy mean, total loss
 // loss partials of this rank: {clip, vf, ent} already divided by the global minibatch size -> grads tail
-__device__ __forceinline__ void loss_partials_block(int mb, int mb_norm, const MbView& v, float* __restrict__ tail, float* sh3) {
-    const int tid = threadIdx.x;  // blockDim.x == 256, sh3 = float[3][256]
+__device__ __forceinline__ void loss_partials_block(int mb, int mb_norm, const MbView& v, float* __restrict__ tail, float* sh) {
+    const int tid = threadIdx.x;  // blockDim.x == 256, sh = float[256]
     float e = 0.f, c = 0.f, f = 0.f;
     // (round 6: the first 2048 rows' terms requested in one batch -- a loop with a run-time trip count is one round trip per iteration, and this workgroup's chain
     // ended adam_next_kernel 0.9 us after the T workgroups'; same order of additions)
@@ -2072,24 +2036,26 @@ __device__ __forceinline__ void loss_partials_block(int mb, int mb_norm, const M
             if (tid + 256 * q < mb) { e += e8[q]; c += c8[q]; f += f8[q]; }
     }
     for (int r = tid + 2048; r < mb; r += 256) { e += v.ent_row[r]; c += v.clip_row[r]; f += v.vf_row[r]; }
-    sh3[tid] = c; sh3[256 + tid] = f; sh3[512 + tid] = e;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { sh3[tid] += sh3[tid + s]; sh3[256 + tid] += sh3[256 + tid + s]; sh3[512 + tid] += sh3[512 + tid + s]; }
-        __syncthreads();
-    }
+    c = block_sum<256>(c, sh); f = block_sum<256>(f, sh); e = block_sum<256>(e, sh);
     if (tid == 0) {
         const float inv = 1.0f / (float)mb_norm;
-        tail[0] = sh3[0] * inv; tail[1] = sh3[256] * inv; tail[2] = sh3[512] * inv; tail[3] = 0.f;
+        tail[0] = c * inv; tail[1] = f * inv; tail[2] = e * inv; tail[3] = 0.f;
     }
-    __syncthreads();
 }
 __global__ __launch_bounds__(256) void loss_partials_kernel(int mb, int mb_norm, MbView v, float* __restrict__ tail) {
-    __shared__ float sh3[768];
-    loss_partials_block(mb, mb_norm, v, tail, sh3);
+    __shared__ float sh[256];
+    loss_partials_block(mb, mb_norm, v, tail, sh);
+}
+// the step's loss row from its three terms
+__device__ __forceinline__ void write_loss_row(float* __restrict__ loss_out, const cirs_ppo_cfg& cfg, float clip, float vf, float ent) {
+    loss_out[0] = clip + cfg.vf_coef * vf - cfg.ent_coef * ent;
+    loss_out[1] = clip; loss_out[2] = vf; loss_out[3] = ent;
 }
 
-// torch.optim.Adam (_single_tensor_adam): lerp_, mul_/addcmul_, bias corrections from the step count
+// torch.optim.Adam (_single_tensor_adam).  The bias corrections of a step (adam_bias), the torch-exact element update (adam_update: what
+// adam_kernel / cirs_adam_step run), the clip coefficient (clip_coef) and the block sum of the norm's tree are optim.h's; here are the
+// learner's segments and its fast element update.  Every learner mode -- adam_next_kernel, adam2_kernel, shard_adam_kernel -- takes its
+// step through adam_elem / adam_elem_seg and its coefficient through norm_coef.
 struct AdamSeg { int n_sub; int scale_pow; float step_size0, bc2s0, step_size1, bc2s1; float rbc2s0, rbc2s1; /* 1 / bc2s (adam_next_kernel) */ };
 
 // torch's update p -= step_size * m / (sqrt(v) / sqrt(1 - beta2^t) + eps) with the hardware's 1-ulp square root and reciprocal (v_sqrt_f32,
@@ -2110,6 +2076,33 @@ __device__ __forceinline__ void adam_elem(float& pi, float& mi, float& vi, float
         pi = pi - ss * (mi * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vi) * rb2 + eps));
     }
 }
+// an element whose segment is known at run time only: the trunk's two sub-steps or the heads' one
+__device__ __forceinline__ void adam_elem_seg(float& pi, float& mi, float& vi, float gi, const AdamSeg& sg, float c, float beta1, float beta2, float eps) {
+    if (sg.n_sub == 2) adam_elem<2, 2>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
+    else adam_elem<1, 1>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
+}
+// clip_grad_norm_ stage 2 in every workgroup (256 threads): the same fixed tree over the same slots -> the same coefficient everywhere
+__device__ __forceinline__ float norm_coef(float sumsq, const cirs_ppo_cfg& cfg, float& total_norm) {
+    total_norm = sqrtf(sumsq);
+    return cfg.max_grad_norm > 0.f ? clip_coef(total_norm, cfg.max_grad_norm) : 1.0f;
+}
+__device__ __forceinline__ float norm_coef_block(float part_a, float part_b, const cirs_ppo_cfg& cfg, float* sh, float& total_norm) {
+    static_assert(kNormBlocks == 256 && kWaSumBlocks <= 256, "each thread folds one slot of each kind");
+    // block_sum's tree written out: its closing barrier, in the A0 workgroups the T workgroups of adam_next_kernel wait for, cost the minibatch step
+    // 0.36 us (profiles/r09_optim_refactor_ab.md).  sh is not reused by the callers before their next barrier
+    const int tid = threadIdx.x;
+    sh[tid] = part_a + part_b;      // slot tid of sumsq_partial_kernel / the F workgroups + slot tid of the wa|ba slab-sum workgroups
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) sh[tid] += sh[tid + s];
+        __syncthreads();
+    }
+    return norm_coef(sh[0], cfg, total_norm);
+}
+__device__ __forceinline__ float norm_coef_block(const float* __restrict__ partial, const cirs_ppo_cfg& cfg, float* sh, float& total_norm) {
+    const int tid = threadIdx.x;
+    return norm_coef_block(partial[tid], (partial[kNormBlocks + tid] + partial[2 * kNormBlocks + tid]) + partial[3 * kNormBlocks + tid], cfg, sh, total_norm);
+}
 // one launch over the whole flat buffer: elements [0, n_first) use segment a (trunk), the rest segment b (heads).
 // clip_grad_norm_ stage 2 rides along: EVERY workgroup sums the kNormBlocks partial sums of squares in the same fixed
 // tree order (identical coefficient everywhere); workgroup 0 also forms the loss terms (mb > 0: single-rank path, the
@@ -2119,38 +2112,26 @@ __global__ __launch_bounds__(256) void adam2_kernel(float* __restrict__ p, const
                                                     float beta2, float eps, cirs_ppo_cfg cfg, const float* __restrict__ partial,
                                                     float* __restrict__ tail, MbView mv, float* __restrict__ loss_out, int mb, int mb_norm) {
     __shared__ float sh[256];
-    __shared__ float sh3[768];
     const int tid = threadIdx.x;
-    if (blockIdx.x == 0 && mb > 0) loss_partials_block(mb, mb_norm, mv, tail, sh3);
-    static_assert(kNormBlocks == 256 && kWaSumBlocks <= 256, "each thread folds one slot of each kind");
-    sh[tid] = partial[tid] + (tid < kWaSumBlocks ? partial[kNormBlocks + tid] : 0.f);
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const float total_norm = sqrtf(sh[0]);
-    float c = 1.0f;
-    if (cfg.max_grad_norm > 0.f) c = fminf(cfg.max_grad_norm / (total_norm + 1e-6f), 1.0f);
+    if (blockIdx.x == 0 && mb > 0) loss_partials_block(mb, mb_norm, mv, tail, sh);
+    float total_norm;      // (this launch's wa|ba slots are the first kWaSumBlocks of the second kind)
+    const float c = norm_coef_block(partial[tid], tid < kWaSumBlocks ? partial[kNormBlocks + tid] : 0.f, cfg, sh, total_norm);
     if (blockIdx.x == 0 && tid == 0) {
         mv.red[4] = c;
         mv.red[5] = total_norm;
-        const float clip = tail[0], vf = tail[1], ent = tail[2];
-        loss_out[0] = clip + cfg.vf_coef * vf - cfg.ent_coef * ent;
-        loss_out[1] = clip; loss_out[2] = vf; loss_out[3] = ent;
+        write_loss_row(loss_out, cfg, tail[0], tail[1], tail[2]);
     }
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= n) return;
     const AdamSeg sg = i < n_first ? sa : sb;
     float gi = g[i];
     float pi = p[i], mi = m[i], vi = v[i];
-    if (sg.n_sub == 2) adam_elem<2, 2>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);      // (the arithmetic of adam_next_kernel: every learner mode takes the same step)
-    else adam_elem<1, 1>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
+    adam_elem_seg(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
     p[i] = pi; m[i] = mi; v[i] = vi;
 }
 
 // ---- the optimiser launch of a single-rank minibatch step (round 5) ---------------------------------------------------------------
-// adam2_kernel's arithmetic (adam_elem / norm_coef_block are the same statements, so the same bits), re-tiled so that the launch can also do
+// adam2_kernel's arithmetic (the same adam_elem / norm_coef_block, so the same bits), re-tiled so that the launch can also do
 // the three jobs trunk_adv_kernel did at the head of the NEXT step -- that launch (8 us, all of it latency on the critical path of every
 // minibatch step) disappears from cirs_ppo_learn's loop:
 //   [0, n_a0)           A0: Adam on [trunk | wc | bc], one element per thread, the parameters written through + an arrival count (what T waits for)
@@ -2172,25 +2153,6 @@ struct AdamNext {
     cirs_ppo_batch bt; int n_env;
     TrunkRowOut out;
 };
-// clip_grad_norm_ stage 2 in every workgroup (256 threads): the same fixed tree over the same slots -> the same coefficient everywhere
-__device__ __forceinline__ float norm_coef_block(float part_a, float part_b, const cirs_ppo_cfg& cfg, float* sh, float& total_norm) {
-    const int tid = threadIdx.x;
-    static_assert(kNormBlocks == 256 && kWaSumBlocks <= 256, "each thread folds one slot of each kind");
-    sh[tid] = part_a + part_b;      // slot tid of sumsq_partial_kernel / the F workgroups + slot tid of the wa|ba slab-sum workgroups
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    total_norm = sqrtf(sh[0]);
-    float c = 1.0f;
-    if (cfg.max_grad_norm > 0.f) c = fminf(cfg.max_grad_norm / (total_norm + 1e-6f), 1.0f);
-    return c;
-}
-__device__ __forceinline__ float norm_coef_block(const float* __restrict__ partial, const cirs_ppo_cfg& cfg, float* sh, float& total_norm) {
-    const int tid = threadIdx.x;
-    return norm_coef_block(partial[tid], (partial[kNormBlocks + tid] + partial[2 * kNormBlocks + tid]) + partial[3 * kNormBlocks + tid], cfg, sh, total_norm);
-}
 constexpr int kTrunkQ2 = 13;         // 256 x 13 float2 >= 64 (S + 66) floats, S <= 32: the trunk's parameters, two elements per thread and pass
 constexpr int kTrunkRowsPerWg = kTileM;   // rows of a T workgroup: one MFMA row tile
 struct AdamArgs {
@@ -2412,6 +2374,7 @@ __device__ __forceinline__ void adam_next_trunk_params(const AdamArgs& a, const 
     float total_norm;
     const float c = norm_coef_block(a.partial, a.cfg, l.sh, total_norm);
     if (i < a.L.total) {
+        // (not adam_elem_seg: a per-thread choice between the two by-value segments goes through scratch memory, 1.9 us on every step)
         if (i < a.L.trunk) adam_elem<2, 2>(pi, mi, vi, gi, a.sa, c, a.beta1, a.beta2, a.eps);
         else adam_elem<1, 1>(pi, mi, vi, gi, a.sb, c, a.beta1, a.beta2, a.eps);
         st_sc1(a.p + i, pi);        // (written through: the T workgroups of this launch read it)
@@ -2451,9 +2414,7 @@ __device__ __forceinline__ void adam_next_rest(const AdamArgs& a, const MbView& 
             if (tid < s2) { sh3[tid] += sh3[tid + s2]; sh3[256 + tid] += sh3[256 + tid + s2]; sh3[512 + tid] += sh3[512 + tid + s2]; l.sh[tid] += l.sh[tid + s2]; }
             __syncthreads();
         }
-        total_norm = sqrtf(l.sh[0]);
-        c = 1.0f;
-        if (a.cfg.max_grad_norm > 0.f) c = fminf(a.cfg.max_grad_norm / (total_norm + 1e-6f), 1.0f);
+        c = norm_coef(l.sh[0], a.cfg, total_norm);
         if (tid == 0) {
             const float inv = 1.0f / (float)a.mb_norm;
             lt[0] = sh3[0] * inv; lt[1] = sh3[256] * inv; lt[2] = sh3[512] * inv;
@@ -2466,9 +2427,7 @@ __device__ __forceinline__ void adam_next_rest(const AdamArgs& a, const MbView& 
     if (ba_ == 0 && tid == 0) {
         mv.red[4] = c;
         mv.red[5] = total_norm;
-        const float clip = lt[0], vf = lt[1], ent = lt[2];
-        a.loss_out[0] = clip + a.cfg.vf_coef * vf - a.cfg.ent_coef * ent;
-        a.loss_out[1] = clip; a.loss_out[2] = vf; a.loss_out[3] = ent;
+        write_loss_row(a.loss_out, a.cfg, lt[0], lt[1], lt[2]);
     }
     const long i = a.L.ba + ba_ * 256L + tid;
     if (i < a.L.wc) {
@@ -2506,14 +2465,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         for (int q = 0; q < scale_pow; ++q) gi *= c;  // clip coefficient applied once per occurrence in the param list
     }
     float pi = p[i], mi = m[i], vi = v[i];
-    for (int sub = 0; sub < n_sub; ++sub) {
-        mi = mi + (1.0f - beta1) * (gi - mi);                 // exp_avg.lerp_(grad, 1 - beta1)
-        vi = vi * beta2 + (1.0f - beta2) * gi * gi;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        const float ss = sub == 0 ? step_size0 : step_size1;
-        const float b2 = sub == 0 ? bc2s0 : bc2s1;
-        const float denom = sqrtf(vi) / b2 + eps;
-        pi = pi - ss * (mi / denom);                          // param.addcdiv_(exp_avg, denom, value=-step_size)
-    }
+    for (int sub = 0; sub < n_sub; ++sub)
+        adam_update(pi, mi, vi, gi, sub == 0 ? step_size0 : step_size1, sub == 0 ? bc2s0 : bc2s1, beta1, beta2, eps);
     p[i] = pi; m[i] = mi; v[i] = vi;
 }
 
@@ -2537,13 +2490,8 @@ __global__ __launch_bounds__(256) void shard_sumsq_kernel(const float* __restric
             acc += (gi < n_trunk ? 2.0f : 1.0f) * x * x;
         }
     }
-    sh[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) stats[blockIdx.x] = sh[0];
+    acc = block_sum<256>(acc, sh);
+    if (tid == 0) stats[blockIdx.x] = acc;
     if (blockIdx.x == 0 && tid < 8) {
         const long gi = P + tid;
         stats[kShardNormBlocks + tid] = (tid < 4 && gi >= begin && gi < begin + len) ? g_shard[gi - begin] : 0.f;
@@ -2560,43 +2508,30 @@ __global__ __launch_bounds__(256) void shard_adam_kernel(float* __restrict__ p, 
     float acc = 0.f;
     const int n_part = world * kShardNormBlocks;
     for (int q = tid; q < n_part; q += 256) acc += stats_all[(size_t)(q / kShardNormBlocks) * kShardStatFloats + (q % kShardNormBlocks)];
-    sh[tid] = acc;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    const float total_norm = sqrtf(sh[0]);
-    float c = 1.0f;
-    if (cfg.max_grad_norm > 0.f) c = fminf(cfg.max_grad_norm / (total_norm + 1e-6f), 1.0f);
+    float total_norm;
+    const float c = norm_coef(block_sum<256>(acc, sh), cfg, total_norm);
     if (blockIdx.x == 0 && tid == 0 && loss_out) {
         float t3[3] = {0.f, 0.f, 0.f};
         for (int r = 0; r < world; ++r)
             for (int j = 0; j < 3; ++j) t3[j] += stats_all[(size_t)r * kShardStatFloats + kShardNormBlocks + j];
-        loss_out[0] = t3[0] + cfg.vf_coef * t3[1] - cfg.ent_coef * t3[2];
-        loss_out[1] = t3[0]; loss_out[2] = t3[1]; loss_out[3] = t3[2];
+        write_loss_row(loss_out, cfg, t3[0], t3[1], t3[2]);
     }
     const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (i >= len || begin + i >= P) return;
     const AdamSeg sg = begin + i < n_first ? sa : sb;
     float gi = g[i];
     float pi = p[i], mi = m[i], vi = v[i];
-    if (sg.n_sub == 2) adam_elem<2, 2>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);      // (the arithmetic of adam_next_kernel: every learner mode takes the same step)
-    else adam_elem<1, 1>(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
+    adam_elem_seg(pi, mi, vi, gi, sg, c, beta1, beta2, eps);
     p[i] = pi; m[i] = mi; v[i] = vi;
 }
 
 static int launch_adam(float* p, const float* g, float* m, float* v, long n, long step_before, int n_sub, float lr, float b1,
                        float b2, float eps, const float* grad_scale, int scale_pow, hipStream_t s) {
     CIRS_REQUIRE(n_sub == 1 || n_sub == 2, "n_sub must be 1 or 2");
-    double ss[2] = {0, 0}, bs[2] = {1, 1};
-    for (int q = 0; q < n_sub; ++q) {
-        const double t = (double)(step_before + 1 + q);
-        ss[q] = (double)lr / (1.0 - pow((double)b1, t));
-        bs[q] = sqrt(1.0 - pow((double)b2, t));
-    }
-    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, n, n_sub, b1, b2, eps, (float)ss[0],
-                       (float)bs[0], (float)ss[1], (float)bs[1], grad_scale, scale_pow);
+    AdamBias ab[2] = {{0.f, 1.f, 1.f}, {0.f, 1.f, 1.f}};
+    for (int q = 0; q < n_sub; ++q) ab[q] = adam_bias(lr, b1, b2, step_before + 1 + q);
+    hipLaunchKernelGGL(adam_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, g, m, v, n, n_sub, b1, b2, eps, ab[0].step_size, ab[0].bc2s,
+                       ab[1].step_size, ab[1].bc2s, grad_scale, scale_pow);
     CIRS_CHECK_LAUNCH("adam_kernel");
     return CIRS_OK;
 }
@@ -2851,11 +2786,9 @@ static int launch_trunk_rows(const PpoRun& r, const PpoStep& st, int n_bchunks, 
 static cirs::AdamSeg adam_seg_of(const cirs_ppo_cfg* cfg, long step_before, int n_sub, int scale_pow) {
     cirs::AdamSeg sg{n_sub, scale_pow, 0.f, 1.f, 0.f, 1.f, 1.f, 1.f};
     for (int q = 0; q < n_sub; ++q) {
-        const double t = (double)(step_before + 1 + q);
-        const float ss = (float)((double)cfg->lr / (1.0 - pow((double)cfg->beta1, t)));
-        const float bs = (float)sqrt(1.0 - pow((double)cfg->beta2, t));
-        const float rbs = (float)(1.0 / sqrt(1.0 - pow((double)cfg->beta2, t)));
-        if (q == 0) { sg.step_size0 = ss; sg.bc2s0 = bs; sg.rbc2s0 = rbs; } else { sg.step_size1 = ss; sg.bc2s1 = bs; sg.rbc2s1 = rbs; }
+        const cirs::AdamBias ab = cirs::adam_bias(cfg->lr, cfg->beta1, cfg->beta2, step_before + 1 + q);
+        if (q == 0) { sg.step_size0 = ab.step_size; sg.bc2s0 = ab.bc2s; sg.rbc2s0 = ab.rbc2s; }
+        else { sg.step_size1 = ab.step_size; sg.bc2s1 = ab.bc2s; sg.rbc2s1 = ab.rbc2s; }
     }
     return sg;
 }

@@ -8,7 +8,8 @@
 //                       segment sum (the gradient buffer starts from zero) or, marked `add`, adds it to what an earlier pass left.
 //   adam_l2_kernel      g += 2 * l2_c * p (the regulariser is dense: every row of every table decays), Adam, and the regulariser's
 //                       value as per-workgroup partials; reg_final_kernel sums them in index order into one slot of the loss vector;
-//                       table_adam_step launches the pair with the bias corrections of the step count.
+//                       table_adam_step launches the pair with the bias corrections of the step count.  The corrections, the element
+//                       update and the block sums are optim.h's (adam_bias through tstep::adam_args, adam_update, block_sum).
 // Every sum has a fixed order: two runs give identical bits.
 #pragma once
 #include <hipcub/hipcub.hpp>
@@ -115,22 +116,14 @@ static __global__ __launch_bounds__(256) void adam_l2_kernel(float* __restrict__
 #pragma unroll
         for (int q = 5; q >= 0; --q)
             if (q < segs.n && i < segs.end[q]) c = segs.c[q];
-        const float pi = p[i];
+        float pi = p[i], mi = m[i], vi = v[i];
         reg = __builtin_fmaf(c * pi, pi, reg);
         const float gi = __builtin_fmaf(2.0f * c, pi, g[i]);   // d/dp of c * p^2 joins the data gradient
-        g[i] = gi;
-        const float mi = m[i] + (1.0f - beta1) * (gi - m[i]);
-        const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        p[i] = pi - step_size * (mi / (sqrtf(vi) / bc2s + eps));
+        adam_update(pi, mi, vi, gi, step_size, bc2s, beta1, beta2, eps);
+        g[i] = gi; m[i] = mi; v[i] = vi; p[i] = pi;
     }
-    sh[tid] = reg;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) reg_partial[blockIdx.x] = sh[0];
+    reg = block_sum<256>(reg, sh);
+    if (tid == 0) reg_partial[blockIdx.x] = reg;
 }
 
 static __global__ __launch_bounds__(256) void reg_final_kernel(const float* __restrict__ part, float* __restrict__ loss_out, int slot) {
@@ -138,13 +131,8 @@ static __global__ __launch_bounds__(256) void reg_final_kernel(const float* __re
     const int tid = threadIdx.x;
     float t = 0.f;
     for (int q = tid; q < kRegBlocks; q += 256) t += part[q];
-    sh[tid] = t;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) sh[tid] += sh[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) loss_out[slot] = sh[0];
+    t = block_sum<256>(t, sh);
+    if (tid == 0) loss_out[slot] = t;
 }
 
 // what both trainers carve behind their row kernel's outputs: the dW slab partials, the regulariser partials, the sort scratch of the

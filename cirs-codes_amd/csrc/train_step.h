@@ -11,11 +11,11 @@
 //                       the unused duplicate `linear_model.weight` (no data gradient) and sums the loss / regulariser partials in
 //                       index order into loss_out.
 //   run_steps           the argument checks of the _step / _epoch entries and the back-to-back loop over the batches.
+// The bias corrections (adam_bias) and the block sum (block_sum) are optim.h's; adam_one states optim.h's adam_update on the buffers.
 // Every sum has a fixed order and there are no float atomics.
 #pragma once
-#include <cmath>
-
 #include "common.h"
+#include "optim.h"
 
 namespace cirs {
 namespace tstep {
@@ -24,19 +24,6 @@ constexpr int kThreads = 256;
 constexpr int kRegChunks = 64, kRegBlocks = 8;
 constexpr int kMaxJobs = CIRS_VTB_STATIC_MAX_DNN + 4;   // the larger trainer: hidden layers, experts | gates, two towers, linear_model_task
 constexpr int kMaxLossCols = 2;
-
-// sum of 256 per-thread doubles in a fixed tree; result valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 // regulariser of the current parameters by workgroups first_block .. first_block + kRegBlocks - 1: chunk c covers [c * cs, (c + 1) * cs);
 // red: kThreads doubles of LDS
@@ -52,7 +39,7 @@ __device__ __forceinline__ void reg_chunks(const float* __restrict__ P, int tota
             const double coef = (double)l2_all + (i >= lin_model && i < lin_task ? (double)l2_linear : 0.0);   // linear_model.weight is in both lists
             acc = fma(coef * p, p, acc);
         }
-        const double t = block_sum_f64(acc, red);
+        const double t = block_sum<kThreads>(acc, red);
         if (tid == 0) reg_part[c] = t;
     }
 }
@@ -78,16 +65,17 @@ struct AdamArgs {
     float beta1, beta2, eps, step_size, bc2s, l2_linear, l2_all;
 };
 inline AdamArgs adam_args(float lr, float beta1, float beta2, float eps, float l2_linear, float l2_all, int64_t step_before) {
-    const double t = (double)(step_before + 1);
+    const AdamBias b = adam_bias(lr, beta1, beta2, step_before + 1);
     AdamArgs a;
     a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.l2_linear = l2_linear; a.l2_all = l2_all;
-    a.step_size = (float)((double)lr / (1.0 - pow((double)beta1, t)));
-    a.bc2s = (float)sqrt(1.0 - pow((double)beta2, t));
+    a.step_size = b.step_size; a.bc2s = b.bc2s;
     return a;
 }
 
 __device__ __forceinline__ void adam_one(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int i,
                                          float data_grad, float c2, const AdamArgs& a) {
+    // adam_update's statements (optim.h) on the buffers themselves: through the register form grad_adam_kernel is scheduled differently and the
+    // 100-row epoch of the (128, 128) MMoE trainer took 58.13 us per step against 57.88 us (profiles/r09_optim_refactor_ab.md)
     const float pi = p[i];
     const float gi = __builtin_fmaf(c2, pi, data_grad);   // d/dp of l2 * p^2 joins the data gradient
     const float mi = m[i] + (1.0f - a.beta1) * (gi - m[i]);

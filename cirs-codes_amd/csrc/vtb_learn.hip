@@ -11,7 +11,7 @@
 //                                 gradient through the heads and the Net trunk, per-workgroup gradient partials; dL/dstate per row
 //                                 on the last pass
 //   vtb_learn_adam_kernel         one workgroup: fixed-order reduction of the partials, clip_grad_norm_ (trunk counted twice), Adam
-//                                 (two sub-steps for the trunk), the minibatch's loss record
+//                                 (two sub-steps for the trunk; bias corrections from the host), the minibatch's loss record
 //   vtb_learn_tracker_bwd_kernel  one workgroup per episode: dL/dstate of the obs rows back through decoder, both encoder layers, PE
 //                                 and the input slots into per-episode tracker gradient partials
 //   vtb_learn_tracker_adam_kernel fixed-order reduction over episodes, one Adam step of the tracker
@@ -21,6 +21,7 @@
 // No float atomics: every sum has a fixed order, so two runs from the same snapshot are bit-identical.  fp32 FMA, fp64 for GAE,
 // the return statistics, the advantage moments and the gradient norm.  Parameter images are in torch's [out][in] layout.
 #include "common.h"
+#include "optim.h"
 #include "rng.h"
 #include "vtb_model.h"
 
@@ -465,30 +466,16 @@ __global__ __launch_bounds__(256) void vtb_learn_gae_kernel(cirs_vtb_learn_cfg c
     }
 }
 
-// fixed-order block sum of 256 doubles in lds (result in red[0])
-__device__ __forceinline__ double block_sum_256(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void vtb_learn_rms_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L) {
     __shared__ double red[256];
     const int n = c.n_rows, tid = threadIdx.x;
     const double* tot = (const double*)(b.ws + L.w.total64);
     double s = 0.0;
     for (int i = tid; i < n; i += 256) s += tot[i];
-    const double mu = block_sum_256(s, red) / n;
+    const double mu = block_sum<256>(s, red) / n;
     double q = 0.0;
     for (int i = tid; i < n; i += 256) q += (tot[i] - mu) * (tot[i] - mu);
-    const double s2 = block_sum_256(q, red) / n;
+    const double s2 = block_sum<256>(q, red) / n;
     if (tid == 0) {   // ReturnScale.update: parallel-variance merge of one block
         const double w_old = b.rms[2], w_all = w_old + n, shift = mu - b.rms[0];
         const double var = (b.rms[1] * w_old + s2 * n + shift * shift * (w_old * n / w_all)) / w_all;
@@ -515,13 +502,13 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
     if (c.whiten_adv) {
         double s = 0.0;
         for (int j = tid; j < m; j += kT) s += ws[L.w.adv + perm[j]];
-        const double mu = block_sum_256(s, red) / m;
+        const double mu = block_sum<256>(s, red) / m;
         double q = 0.0;
         for (int j = tid; j < m; j += kT) {
             const double d = ws[L.w.adv + perm[j]] - mu;
             q += d * d;
         }
-        const double var = block_sum_256(q, red) / (m - 1);
+        const double var = block_sum<256>(q, red) / (m - 1);
         if (tid == 0) {
             stat[0] = (float)mu;
             stat[1] = (float)sqrt(var);
@@ -690,20 +677,21 @@ __global__ __launch_bounds__(kT) void vtb_learn_minibatch_kernel(cirs_vtb_learn_
     }
 }
 
-// one Adam step of torch.optim.Adam (single-tensor path): lerp / addcmul moments, bias corrections in fp64
-__device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, long step, float lr, float b1, float b2, float eps) {
+// one Adam step of torch.optim.Adam (single-tensor path) with the step's bias corrections from the host (optim.h: adam_bias).  The second
+// moment is ONE fused multiply-add here, which rounds differently from optim.h's adam_update (a product and a sum): this learner keeps its
+// own three statements so that its results stay what they were.
+__device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, const AdamBias& ab, float b1, float b2, float eps) {
     m = m + (1.0f - b1) * (g - m);
     v = __builtin_fmaf(v, b2, (1.0f - b2) * g * g);
-    const double bc1 = 1.0 - pow((double)b1, (double)step);
-    const double bc2 = 1.0 - pow((double)b2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
-    const float denom = sqrtf(v) / bc2s + eps;
-    p = p + (-step_size) * (m / denom);
+    const float denom = sqrtf(v) / ab.bc2s + eps;
+    p = p + (-ab.step_size) * (m / denom);
 }
 
+// trunk0 / trunk1: the trunk's two sub-steps (the parameter list holds it twice), head: the heads' one
+struct PolicyBias { AdamBias trunk0, trunk1, head; };
+
 __global__ __launch_bounds__(kAdamT) void vtb_learn_adam_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L, int m, int mb,
-                                                                long p_step0) {
+                                                                PolicyBias ab) {
     __shared__ double red[kAdamT];
     __shared__ float coef_s;
     const int tid = threadIdx.x;
@@ -718,15 +706,10 @@ __global__ __launch_bounds__(kAdamT) void vtb_learn_adam_kernel(cirs_vtb_learn_c
         const double gd = g;
         sq += (q < L.p.trunk_end ? 2.0 : 1.0) * gd * gd;
     }
-    red[tid] = sq;
-    __syncthreads();
-    for (int s = kAdamT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
+    sq = block_sum<kAdamT>(sq, red);
     if (tid == 0) {
-        const float tn = (float)sqrt(red[0]);
-        coef_s = c.has_max_norm ? fminf(c.max_norm / (tn + 1e-6f), 1.0f) : 1.0f;
+        const float tn = (float)sqrt(sq);
+        coef_s = c.has_max_norm ? clip_coef(tn, c.max_norm) : 1.0f;
         const double* ls = (const double*)(ws + L.w.lslab);
         double sg = 0.0, se = 0.0, sn = 0.0;
         for (int k = 0; k < nwg; ++k) {
@@ -749,11 +732,11 @@ __global__ __launch_bounds__(kAdamT) void vtb_learn_adam_kernel(cirs_vtb_learn_c
         float p = b.pparams[q], mm = b.p_m[q], vv = b.p_v[q];
         if (q < L.p.trunk_end) {
             if (c.has_max_norm) g = (g * coef) * coef;
-            adam_one(p, mm, vv, g, 2 * p_step0 + 2 * mb + 1, c.lr, c.beta1, c.beta2, c.eps);
-            adam_one(p, mm, vv, g, 2 * p_step0 + 2 * mb + 2, c.lr, c.beta1, c.beta2, c.eps);
+            adam_one(p, mm, vv, g, ab.trunk0, c.beta1, c.beta2, c.eps);
+            adam_one(p, mm, vv, g, ab.trunk1, c.beta1, c.beta2, c.eps);
         } else {
             if (c.has_max_norm) g = g * coef;
-            adam_one(p, mm, vv, g, p_step0 + mb + 1, c.lr, c.beta1, c.beta2, c.eps);
+            adam_one(p, mm, vv, g, ab.head, c.beta1, c.beta2, c.eps);
         }
         b.pparams[q] = p;
         b.p_m[q] = mm;
@@ -1051,14 +1034,14 @@ __global__ __launch_bounds__(kT) void vtb_learn_tracker_redraw_kernel(cirs_vtb_l
 }
 #undef LEARN_KEEP
 
-__global__ __launch_bounds__(256) void vtb_learn_tracker_adam_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L, long step) {
+__global__ __launch_bounds__(256) void vtb_learn_tracker_adam_kernel(cirs_vtb_learn_cfg c, cirs_vtb_learn_bufs b, Lay L, AdamBias ab) {
     const long P = L.t.total;
     const float* slab = b.ws + L.w.tslab;
     for (long q = blockIdx.x * (long)blockDim.x + threadIdx.x; q < P; q += (long)gridDim.x * blockDim.x) {
         float g = 0.f;
         for (int e = 0; e < L.n_wg; ++e) g += slab[(long)e * P + q];
         float p = b.tparams[q], m = b.t_m[q], v = b.t_v[q];
-        adam_one(p, m, v, g, step, c.t_lr, c.t_beta1, c.t_beta2, c.t_eps);
+        adam_one(p, m, v, g, ab, c.t_beta1, c.t_beta2, c.t_eps);
         b.tparams[q] = p;
         b.t_m[q] = m;
         b.t_v[q] = v;
@@ -1144,7 +1127,9 @@ int update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, bool red
             const int m = e - a;
             hipLaunchKernelGGL(vtb_learn_minibatch_kernel, dim3(cdiv(m, kRows)), dim3(kT), 0, s, c, *b, L, perm + a, m, pass == repeat - 1 ? 1 : 0);
             CIRS_CHECK_LAUNCH("vtb_learn_minibatch_kernel");
-            hipLaunchKernelGGL(vtb_learn_adam_kernel, dim3(1), dim3(kAdamT), 0, s, c, *b, L, m, mb, (long)p_step0);
+            const PolicyBias ab = {adam_bias(c.lr, c.beta1, c.beta2, 2 * p_step0 + 2 * mb + 1), adam_bias(c.lr, c.beta1, c.beta2, 2 * p_step0 + 2 * mb + 2),
+                                   adam_bias(c.lr, c.beta1, c.beta2, p_step0 + mb + 1)};
+            hipLaunchKernelGGL(vtb_learn_adam_kernel, dim3(1), dim3(kAdamT), 0, s, c, *b, L, m, mb, ab);
             CIRS_CHECK_LAUNCH("vtb_learn_adam_kernel");
         }
     }
@@ -1158,7 +1143,8 @@ int update(const cirs_vtb_learn_cfg* cfg, const cirs_vtb_learn_bufs* b, bool red
     }
     CIRS_CHECK_LAUNCH("vtb_learn_tracker_bwd_kernel");
     const int g = cdiv(L.t.total, 256);
-    hipLaunchKernelGGL(vtb_learn_tracker_adam_kernel, dim3(g < 1024 ? g : 1024), dim3(256), 0, s, c, *b, L, (long)t_step0 + 1);
+    hipLaunchKernelGGL(vtb_learn_tracker_adam_kernel, dim3(g < 1024 ? g : 1024), dim3(256), 0, s, c, *b, L,
+                       adam_bias(c.t_lr, c.t_beta1, c.t_beta2, t_step0 + 1));
     CIRS_CHECK_LAUNCH("vtb_learn_tracker_adam_kernel");
     return CIRS_OK;
 }
