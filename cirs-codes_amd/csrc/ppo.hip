@@ -681,10 +681,13 @@ __device__ unsigned long long g_step_prof[64];
 // per-tile stage timestamps of workgroup (0, 0) / wave 0 at its third tile (probe builds only: tools/probes/head_prof.py)
 __device__ unsigned long long g_head_prof[64];
 #define CIRS_HSTAMP(K) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0 && it == 2) g_head_prof[K] = __builtin_amdgcn_s_memtime(); } while (0)
+// (the two-role form: role B's first thread, one iteration later = the same tile)
+#define CIRS_HSTAMPB(K) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 256 && it == 3) g_head_prof[K] = __builtin_amdgcn_s_memtime(); } while (0)
 #define CIRS_TSTAMP(B, K) do { if ((int)blockIdx.x == (B) && threadIdx.x == 0) g_head_prof[K] = __builtin_amdgcn_s_memtime(); } while (0)
 #define CIRS_SSTAMP(K) do { if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_head_prof[K] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CIRS_HSTAMP(K) do { } while (0)
+#define CIRS_HSTAMPB(K) do { } while (0)
 #define CIRS_TSTAMP(B, K) do { } while (0)
 #define CIRS_SSTAMP(K) do { } while (0)
 #endif
@@ -861,109 +864,15 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
 // kernels: a 6.5 us launch on the critical path of every minibatch step becomes ~1.5 us of prologue.  The item-sharded learner keeps the
 // merge kernel (its statistics cross the ranks first).
 // kZin: the tile's logits come from the slab head_stats_kernel<true> left one launch earlier (kZTileF4: the same accumulator bits, so both forms give the
-// same results) instead of a second pass over the R planes: no `za` / bias reads, no logits MFMAs (24 of the tile's 72), half the plane staging (the C planes
-// only), no `hz` operand.  The tile's 16 values per lane are requested one tile ahead.  The previous tile's dWa sum, which hides behind the logits MFMAs in
-// the recompute form, sits behind the dH2 MFMAs here.  The recompute form stays for same-box A/B runs and the bit-identity test (CIRS_PPO_HEAD_RECOMPUTE=1).
+// same results) instead of a second pass over the R planes: no `za` / bias reads, no logits MFMAs, half the plane staging (the C planes only), no `hz`
+// operand.  That form is head_bwd_roles below (two wave roles per row tile, twice the threads); the body of head_bwd_fused_kernel itself is the recompute
+// form (kZin = false), which stays for same-box A/B runs and as the reference of the bit-identity tests (CIRS_PPO_HEAD_RECOMPUTE=1).
 struct HeadMergeArgs { cirs_ppo_cfg cfg; cirs_ppo_batch b; const int32_t* idx; int mb_norm, n_schunks; ActorPartialView pv; };
-template <bool kEnt, bool kMerge, bool kZin>
-__global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I, int mb, int n_pad, int tiles_per_chunk,
-                                                                         const uint4* __restrict__ planes,
-                                                                         const float* __restrict__ ba, MbView v,
-                                                                         float* __restrict__ dwap, HeadMergeArgs ma) {
-    constexpr int kThreads = kBwdWaves * 64;
-    static_assert(kThreads == 256, "the plane staging maps one 16-byte unit per thread and plane");
-    constexpr int kCOff = kZin ? 0 : 3 * kRPlaneB;      // kZin: the C planes only
-    __shared__ __attribute__((aligned(16))) unsigned char sW[2][kCOff + 3 * kCPlaneB];
-    __shared__ __attribute__((aligned(16))) float sB[2][kTileN];   // 16-byte aligned: the accumulator init reads 4 consecutive biases as one ds_read_b128
-    __shared__ __attribute__((aligned(16))) float sT[kBwdWaves][kTileN * kTStride];
-    __shared__ __attribute__((aligned(16))) float sR[2][kBwdWaves][kRSize];   // double-buffered: the sum of tile t runs inside iteration t + 1
-    const int tid = threadIdx.x;
-    CIRS_SSTAMP(30);
-    if (blockIdx.x == 0 && blockIdx.y == 0) {      // arrival flags of this step's trunk-backward / optimiser launches
-        v.sync[tid] = 0;
-        if (tid < kSyncInts - 256) v.sync[256 + tid] = 0;
-    }
-    const int lane = tid & 63, wv = tid >> 6;
-    const int hi = lane >> 5, lo = lane & 31;
-    const int row0 = (blockIdx.y * kBwdWaves + wv) * kTileM;
-    const bool wave_ok = row0 < n_pad;   // all waves take part in the staging, barriers and the slab reduction
-    const int chunk = blockIdx.x;
-    // gridDim.x is padded to a multiple of 8: workgroups are dealt round-robin to the 8 XCDs, so linear id % 8 = chunk % 8
-    // and the row blocks that walk the same chunk share one L2 (the Wa planes of a tile leave HBM / MALL once, not 8 times)
-    if (chunk * tiles_per_chunk * kTileN >= I) return;
-    const int jr = wave_ok ? row0 + lo : 0;
-    // The wave's 32 x 64 tile of H2 is 8 KB of consecutive memory: read coalesced (8 x 1 KB per wave) and handed to the lanes through
-    // LDS -- a lane reading its own 256-byte row costs 64 cache lines per load instruction (the prologue was 6.1 k of the kernel's
-    // 77 k ticks).  The row scalars are requested first; they travel while the tile does.
-    const float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-    const int act = v.act[jr];
-    HPl hz[4];      // B operand of ZT: this lane's row of H2, element j of k-step s = column 16 s + 8 hi + j
-    HPl hb[2][2];   // B operand of the dWa product: element j of k-step t = H2[row acc_row(8 t + j, hi)][32 c + lo]
-    {   // both pre-split by trunk_adv_kernel in register order: 24 coalesced 16-byte loads per lane (the LDS round trip + 8 split8 of
-        // the round-2 prologue were 4.4 k of the kernel's 78 k ticks)
-        const size_t tb = (size_t)((wave_ok ? row0 : 0) >> 5) * 12 * 64 + lane;
-        const uint4* zp = v.h2z + tb;
-        const uint4* bp = v.h2b + tb;
-        if (!kZin) {
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                HPL_SET(hz[s4], zp[(3 * s4) * 64], zp[(3 * s4 + 2) * 64]);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                HPL_SET(hb[c][t], bp[(3 * (2 * c + t)) * 64], bp[(3 * (2 * c + t) + 2) * 64]);
-            }
-    }
-    const bool row_ok = wave_ok && jr < mb;
-    f32x16 dh0, dh1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { dh0[r] = 0.f; dh1[r] = 0.f; }
-    float ent = 0.f;  // clamp correction of the entropy (see below)
-    const float eps = 1.1920928955078125e-7f;
-    const float kLogEps = -15.942385152878742f, kLog1mEps = -1.1920929665620834e-7f;
-    if (!wave_ok) {
-        for (int q = lane; q < kRSize; q += 64) { sR[0][wv][q] = 0.f; sR[1][wv][q] = 0.f; }
-    }
-
-    const int first_tile = chunk * tiles_per_chunk * kTileN;
-    const int n_tiles = max(0, min(tiles_per_chunk, (I - first_tile + kTileN - 1) / kTileN));
-    // staging: unit `tid` of each of the six planes; destination offsets inside a buffer
-    const int dst_r = (tid >> 3) * kRowB + (tid & 7) * 16;
-    const int dst_c = kCOff + (tid >> 2) * kColB + (tid & 3) * 16;
-    uint4 gr0, gr2, gc0, gc2;
-    float gb = 0.f;
-#define CIRS_ISSUE(TILE0)                                                                                  \
-    do {                                                                                                   \
-        const uint4* src_ = planes + (size_t)((TILE0) / kTileN) * kPlaneTileU4 + tid;                      \
-        if (!kZin) { gr0 = src_[0]; gr2 = src_[512]; }                                                     \
-        gc0 = src_[768]; gc2 = src_[1280];                                                                 \
-        if (!kZin && tid < kTileN) gb = ((TILE0) + tid) < I ? kScZ * ba[(TILE0) + tid] : 0.f;   /* the accumulators hold kScZ z */ \
-    } while (0)
-#define CIRS_COMMIT(BUF)                                                                                   \
-    do {                                                                                                   \
-        unsigned char* base_ = sW[BUF];                                                                    \
-        if (!kZin) {                                                                                       \
-            *reinterpret_cast<uint4*>(base_ + dst_r) = gr0;                                                \
-            *reinterpret_cast<uint4*>(base_ + 2 * kRPlaneB + dst_r) = gr2;                                 \
-        }                                                                                                  \
-        *reinterpret_cast<uint4*>(base_ + dst_c) = gc0;                                                    \
-        \
-        *reinterpret_cast<uint4*>(base_ + 2 * kCPlaneB + dst_c) = gc2;                                     \
-        if (!kZin && tid < kTileN) sB[BUF][tid] = gb;                                                      \
-    } while (0)
-    // kZin: this wave's tiles of the logit slab, [q][lane] float4 each; `zn` holds the tile requested one iteration ahead
-    const float4* zsl = v.zslab + ((size_t)(first_tile / kTileN) * (n_pad / kTileM) + (wave_ok ? row0 / kTileM : 0)) * kZTileF4 + lane;
-    const size_t zstep = (size_t)(n_pad / kTileM) * kZTileF4;
-    float4 zn[4];
-    if (kZin) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) zn[q] = zsl[q * 64];
-    }
-    // the first tile's planes and the H2 planes above are on their way while the row statistics are merged
-    if (n_tiles > 0) CIRS_ISSUE(first_tile);
+// The row's backward coefficients: read from the merge kernel's arrays (!kMerge), or merged here from the head-statistics partials (kMerge; the
+// workgroups of chunk 0 store what later kernels read).  Every wave of a row tile computes them for its own rows; `jr` is 0 for an idle wave.
+struct HeadRowCoef { float lse, c_logp, c_ent, h_ent; };
+template <bool kEnt, bool kMerge>
+__device__ __forceinline__ HeadRowCoef head_row_coef(const MbView& v, const HeadMergeArgs& ma, int n_pad, int mb, bool wave_ok, int jr, int hi) {
     float lse, c_logp, c_ent, h_ent;
     if (!kMerge) {
         lse = v.lse[jr]; c_logp = v.c_logp[jr]; c_ent = kEnt ? v.c_ent[jr] : 0.f; h_ent = kEnt ? v.h_ent[jr] : 0.f;
@@ -1035,6 +944,397 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             v.h_ent[jr] = real ? rt.h_ent : 0.f;       // the reported entropy (dh2_sum_kernel: ent_row = h_ent + clamp correction)
         }
     }
+    return HeadRowCoef{lse, c_logp, c_ent, h_ent};
+}
+// ---- the hand-over form (kZin = true): two wave roles per SIMD ---------------------------------------------------
+// One wave alone issues a vector instruction every 4 cycles at best, and the tile's ~800 non-MFMA instructions, not its 48 MFMAs, bounded the
+// one-role form.  Here 2 kBwdWaves waves run, wave w and wave w + kBwdWaves on the same SIMD and on the same row tile w, and the tile's stream is cut
+// where dZ already crosses LDS:
+//   role A (waves 0 .. kBwdWaves-1): row coefficients, slab loads one tile ahead, dZ / action / entropy corrections, transposed store of dZ (sT),
+//                                    split + dH2 MFMAs; owns dh0 / dh1 / ent and the d h2 / entropy slabs;
+//   role B (the other kBwdWaves):    plane staging, transposed read of dZ, db, split + dWa MFMAs against its H2 planes, partial tile -> sR, the wave-order
+//                                    sum + slab stores of the tile before.
+// Iteration `it` runs A on tile it, B's product on tile it - 1 and B's sum on tile it - 2; sT, sR and sW are double-buffered and every buffer written
+// in an iteration was last read one workgroup barrier earlier.  EVERY wave -- both roles, idle row tiles included -- executes n_tiles + 1 loop
+// barriers.  Every output keeps the operation sequence of the one-role form (same MFMA order per accumulator, same wave order in the dWa sum).
+constexpr int kBwdRoleThreads = 2 * kBwdWaves * 64;
+template <bool kEnt, bool kMerge>
+__device__ __forceinline__ void head_bwd_roles(int I, int mb, int n_pad, int tiles_per_chunk, const uint4* __restrict__ planes, const MbView& v,
+                                               float* __restrict__ dwap, const HeadMergeArgs& ma) {
+    constexpr int kStage = kBwdWaves * 64;      // threads of one role: the plane staging maps one 16-byte unit per role-B thread and plane
+    static_assert(kStage == 256, "the plane staging maps one 16-byte unit per thread and plane");
+    static_assert(kSyncInts <= kBwdRoleThreads, "one thread per arrival flag");
+    __shared__ __attribute__((aligned(16))) unsigned char sW[2][3 * kCPlaneB];               // the C planes only
+    __shared__ __attribute__((aligned(16))) float sT[2][kBwdWaves][kTileN * kTStride];       // dZ^T of tile it (A writes) / it - 1 (B reads)
+    __shared__ __attribute__((aligned(16))) float sR[2][kBwdWaves][kRSize];                  // partial dWa tiles of tile it - 1 (B writes) / it - 2 (B sums)
+    __shared__ float s_cmax[kBwdWaves];
+    static_assert(sizeof(sW) + sizeof(sT) + sizeof(sR) + sizeof(s_cmax) <= 160 * 1024, "LDS of one CU");
+    const int tid = threadIdx.x;
+    CIRS_SSTAMP(30);
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid < kSyncInts) v.sync[tid] = 0;      // arrival flags of this step's trunk-backward / optimiser launches
+    const int lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: the role and row-tile branches below are wave-uniform)
+    const bool role_b = wid >= kBwdWaves;
+    const int wv = wid & (kBwdWaves - 1), btid = tid & (kStage - 1);
+    const int hi = lane >> 5, lo = lane & 31;
+    const int row0 = (blockIdx.y * kBwdWaves + wv) * kTileM;
+    const bool wave_ok = row0 < n_pad;
+    const int chunk = blockIdx.x;
+    if (chunk * tiles_per_chunk * kTileN >= I) return;      // (the whole workgroup: the grid's x is padded to a multiple of 8)
+    const int jr = wave_ok ? row0 + lo : 0;
+    const bool row_ok = wave_ok && jr < mb;
+    const float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+    const float eps = 1.1920928955078125e-7f;
+    const float kLog1mEps = -1.1920929665620834e-7f;
+    const int first_tile = chunk * tiles_per_chunk * kTileN;
+    const int n_tiles = min(tiles_per_chunk, (I - first_tile + kTileN - 1) / kTileN);      // >= 1
+    // role B's staging: unit `btid` of the C planes H and L
+    const int dst_c = (btid >> 2) * kColB + (btid & 3) * 16;
+    uint4 gc0, gc2;
+#define CIRS_ISSUE(TILE0)                                                                                  \
+    do {                                                                                                   \
+        const uint4* src_ = planes + (size_t)((TILE0) / kTileN) * kPlaneTileU4 + btid;                     \
+        gc0 = src_[768]; gc2 = src_[1280];                                                                 \
+    } while (0)
+#define CIRS_COMMIT(BUF)                                                                                   \
+    do {                                                                                                   \
+        unsigned char* base_ = sW[BUF];                                                                    \
+        *reinterpret_cast<uint4*>(base_ + dst_c) = gc0;                                                    \
+        *reinterpret_cast<uint4*>(base_ + 2 * kCPlaneB + dst_c) = gc2;                                     \
+    } while (0)
+    // role A: this wave's tiles of the logit slab, [q][lane] float4 each; `zn` holds the tile requested one iteration ahead
+    const float4* zsl = v.zslab + ((size_t)(first_tile / kTileN) * (n_pad / kTileM) + (wave_ok ? row0 / kTileM : 0)) * kZTileF4 + lane;
+    const size_t zstep = (size_t)(n_pad / kTileM) * kZTileF4;
+    float4 zn[4];
+    int act = 0;
+    float lse = 0.f, c_logp = 0.f, c_ent = 0.f, h_ent = 0.f;
+    HPl hb[2][2];   // role B: B operand of the dWa product: element j of k-step t = H2[row acc_row(8 t + j, hi)][32 c + lo]
+    if (!role_b) {
+        act = v.act[jr];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) zn[q] = zsl[q * 64];
+        const HeadRowCoef rc = head_row_coef<kEnt, kMerge>(v, ma, n_pad, mb, wave_ok, jr, hi);
+        lse = rc.lse; c_logp = rc.c_logp; c_ent = rc.c_ent; h_ent = rc.h_ent;
+        // f16x3: dZ is formed ALREADY SCALED by a power of two per workgroup (see head_bwd_recompute)
+        const float cm = wave_max_f32_dpp(fabsf(c_logp) + 16.0f * fabsf(c_ent));
+        if (lane == 0) s_cmax[wv] = cm;
+    } else {
+        CIRS_ISSUE(first_tile);
+        const uint4* bp = v.h2b + (size_t)((wave_ok ? row0 : 0) >> 5) * 12 * 64 + lane;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                HPL_SET(hb[c][t], bp[(3 * (2 * c + t)) * 64], bp[(3 * (2 * c + t) + 2) * 64]);
+            }
+        if (!wave_ok) {     // idle row tile (padding of the last row block): its partial tiles are zero, its wave stages and sums
+            for (int q = lane; q < kRSize; q += 64) { sR[0][wv][q] = 0.f; sR[1][wv][q] = 0.f; }
+        }
+        CIRS_COMMIT(0);
+    }
+    CIRS_SSTAMP(31);
+    __syncthreads();
+    CIRS_SSTAMP(32);
+    float dz_scale = 1.0f, dz_inv = 1.0f;
+    {
+        float cm = s_cmax[0];
+#pragma unroll
+        for (int q = 1; q < kBwdWaves; ++q) cm = fmaxf(cm, s_cmax[q]);
+        int ex = 0;
+        if (cm > 0.f) { (void)frexpf(cm, &ex); ex = max(ex, -80); dz_scale = ldexpf(1.0f, 14 - ex); dz_inv = ldexpf(1.0f, ex - 14); }
+        c_logp *= dz_scale; c_ent *= dz_scale;
+    }
+    const float dw_unscale = dz_inv * (1.0f / kScH2), dh_unscale = dz_inv * (1.0f / kScWa);      // (exact powers of two)
+
+    if (!role_b) {
+        // ================= role A =================
+        f32x16 dh0, dh1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { dh0[r] = 0.f; dh1[r] = 0.f; }
+        float ent = 0.f;  // clamp correction of the entropy
+        const float nlse2 = -(lse * kLog2e), ncl = -c_logp;   // p = exp2(z log2e - lse log2e); padded rows: lse = 1e30 -> p = 0
+        // one item tile; kLast: the catalogue's last, partial tile (items beyond I are masked) -- the arithmetic of the one-role form, see there
+        auto a_tile = [&](auto last_c, int it) {
+            constexpr bool last_tile = decltype(last_c)::value;
+            const int buf = it & 1;
+            const int tile0 = first_tile + it * kTileN;
+            const unsigned char* tw = sW[buf];
+            CIRS_HSTAMP(0);
+            HPl cb[2][2];
+            f32x16 acc;      // the logits' accumulator sum (kScZ z) from the slab, then dZ in place
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { acc[4 * q] = zn[q].x; acc[4 * q + 1] = zn[q].y; acc[4 * q + 2] = zn[q].z; acc[4 * q + 3] = zn[q].w; }
+            {   // the next tile's values are requested at once -- unconditionally, with a clamped tile number
+                const float4* zp = zsl + (size_t)min(it + 1, n_tiles - 1) * zstep;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) zn[q] = zp[q * 64];
+            }
+            CIRS_HSTAMP(1);
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const unsigned char* bp = tw + (32 * c + lo) * kColB + (16 * t + 8 * hi) * 2;
+                    HPL_SET(cb[c][t], *reinterpret_cast<const uint4*>(bp), *reinterpret_cast<const uint4*>(bp + 2 * kCPlaneB));
+                }
+            CIRS_HSTAMP(2);
+            float* tt = sT[buf][wv];
+            f32x16 tk;
+            float pmax = 0.f, elo = 0.f;
+            f32x2_b elo2 = {0.f, 0.f};
+            const float kTEps = -23.0f;
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const float t0 = __builtin_fmaf(acc[r], kLog2e * kScZi, nlse2), t1 = __builtin_fmaf(acc[r + 1], kLog2e * kScZi, nlse2);
+                const float p0 = __builtin_amdgcn_exp2f(t0), p1 = __builtin_amdgcn_exp2f(t1);
+                tk[r] = t0; tk[r + 1] = t1;
+                pmax = __builtin_fmaxf(__builtin_fmaxf(pmax, p0), p1);      // v_max3_f32
+                if (!last_tile) {    // two independent partial sums as one packed subtract + packed fma (the max has no packed form)
+                    const f32x2_b d2 = f32x2_b{kTEps, kTEps} - f32x2_b{t0, t1};
+                    const f32x2_b w2 = {__builtin_fmaxf(d2.x, 0.f), __builtin_fmaxf(d2.y, 0.f)};
+                    elo2 = f32x2_b{p0, p1} * w2 + elo2;
+                }
+                if (kEnt) {   // + c_ent p (z - lse + H)
+                    acc[r] = __builtin_fmaf(c_ent * p0, __builtin_fmaf(t0, kLn2, h_ent), ncl * p0);
+                    acc[r + 1] = __builtin_fmaf(c_ent * p1, __builtin_fmaf(t1, kLn2, h_ent), ncl * p1);
+                } else {
+                    acc[r] = ncl * p0; acc[r + 1] = ncl * p1;
+                }
+            }
+            if (__any(act >= tile0 && act < tile0 + kTileN)) {      // rare: some row's action lies in this tile
+                const int rel = act - tile0 - 4 * hi;     // accumulator register r holds item (r & 3) + 8 (r >> 2) + 4 hi of the tile
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] += (rel == (r & 3) + 8 * (r >> 2)) ? c_logp : 0.f;
+            }
+            if (last_tile) {     // items beyond I (zero weights -> finite z): no gradient, no entropy term
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool in = tile0 + acc_row(r, hi) < I;
+                    acc[r] = in ? acc[r] : 0.f;
+                    elo += in ? __builtin_amdgcn_exp2f(tk[r]) * __builtin_fmaxf(kTEps - tk[r], 0.f) : 0.f;
+                }
+            }
+            ent -= kLn2 * (elo + (elo2.x + elo2.y));      // padded rows: p = 0 exactly (lse = 1e30), so they add nothing
+            CIRS_HSTAMP(3);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) tt[acc_row(r, hi) * kTStride + lo] = acc[r];   // transposed exchange: T[item][row], read by role B one barrier later
+            if (__any(row_ok && pmax > 1.0f - eps)) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = __builtin_amdgcn_exp2f(tk[r]);
+                    const bool ok = row_ok && (!last_tile || tile0 + acc_row(r, hi) < I);
+                    ent -= (ok && p > 1.0f - eps) ? p * (kLog1mEps - tk[r] * kLn2) : 0.f;
+                }
+            }
+            CIRS_HSTAMP(4);
+            const HPl a0 = hsplit8(acc, 0), a1 = hsplit8(acc, 8);   // element j: dZ[row lo][item acc_row(8 t + j, hi)]
+            hmfma_pair(a0, cb[0][0], cb[1][0], dh0, dh1);
+            hmfma_pair(a1, cb[0][1], cb[1][1], dh0, dh1);
+            CIRS_HSTAMP(5);
+        };
+        if (wave_ok) {
+            for (int it = 0; it + 1 < n_tiles; ++it) { a_tile(std::false_type{}, it); lds_barrier(); CIRS_HSTAMP(10); }
+            if (first_tile + n_tiles * kTileN > I) a_tile(std::true_type{}, n_tiles - 1);
+            else a_tile(std::false_type{}, n_tiles - 1);
+            lds_barrier();
+            lds_barrier();      // role B's product of the last tile
+            CIRS_SSTAMP(33);
+            float* hslab = v.dh2p + (size_t)chunk * n_pad * kH;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = row0 + acc_row(r, hi);
+                hslab[(size_t)row * kH + lo] = dh0[r] * dh_unscale;
+                hslab[(size_t)row * kH + 32 + lo] = dh1[r] * dh_unscale;
+            }
+            ent += __shfl_xor(ent, 32, CIRS_WAVE);
+            if (hi == 0) v.entp[(size_t)chunk * n_pad + jr] = ent;
+            CIRS_SSTAMP(35);
+        } else {
+            for (int it = 0; it <= n_tiles; ++it) lds_barrier();
+        }
+    } else {
+        // ================= role B =================
+        float* slab = dwap + (size_t)blockIdx.y * dwa_slab_stride(I);
+        // sum of the kBwdWaves partial dWa tiles of one item tile in wave order -> slab of this row block (coalesced float4 stores), in two halves so
+        // that the matrix work sits between them: the LDS reads of all partial tiles, then the adds + stores
+        constexpr int kRedQ = (kTileN * kH / 4) / kStage;
+        struct RedRegs { f32x4 t[kRedQ][kBwdWaves]; float b[kBwdWaves]; };
+        auto reduce_load = [&](int rb, RedRegs& rg) {
+#pragma unroll
+            for (int q = 0; q < kRedQ; ++q)
+#pragma unroll
+                for (int w2 = 0; w2 < kBwdWaves; ++w2) rg.t[q][w2] = reinterpret_cast<const f32x4*>(sR[rb][w2])[btid + kStage * q];
+            if (wv == 0) {    // the bias partials are 64 floats per wave (two half-wave sums per item), lanes 0..31 combine them
+#pragma unroll
+                for (int w2 = 0; w2 < kBwdWaves; ++w2) rg.b[w2] = sR[rb][w2][kTileN * kH + lo] + sR[rb][w2][kTileN * kH + kTileN + lo];
+            }
+        };
+        auto reduce_store = [&](const RedRegs& rg, int t0) {
+            const bool full = t0 + kTileN <= I;     // wave-uniform: only the catalogue's last tile masks its stores per lane
+#pragma unroll
+            for (int q = 0; q < kRedQ; ++q) {
+                const int f = btid + kStage * q;  // float4 index within the 32 x 64 tile
+                f32x4 t = rg.t[q][0];
+#pragma unroll
+                for (int w2 = 1; w2 < kBwdWaves; ++w2) t += rg.t[q][w2];
+                t *= dw_unscale;
+                if (full || t0 + (f >> 4) < I) *reinterpret_cast<f32x4*>(slab + (size_t)t0 * kH + 4 * f) = t;
+            }
+            if (wv == 0) {
+                float t = rg.b[0];
+#pragma unroll
+                for (int w2 = 1; w2 < kBwdWaves; ++w2) t += rg.b[w2];
+                if (hi == 0 && (full || t0 + lo < I)) slab[(size_t)I * kH + t0 + lo] = t * dz_inv;
+            }
+        };
+        // iteration `it`; kSteady: all three parts run (2 <= it < n_tiles - 1), no conditions left
+        auto b_iter = [&](auto steady_c, int it) {
+            constexpr bool kSteady = decltype(steady_c)::value;
+            const bool issue = kSteady || it + 1 < n_tiles, mma = kSteady || it >= 1, red = kSteady || it >= 2;
+            CIRS_HSTAMPB(11);
+            if (issue) CIRS_ISSUE(first_tile + (it + 1) * kTileN);      // the next tile's planes: global loads in flight during the MFMAs below
+            const int pb = (it & 1) ^ 1;                                // buffers of tile it - 1; tile it - 2 sits in buffer it & 1
+            const bool prod = wave_ok && mma;
+            f32x16 dzt;  // lane owns item lo; register r' = row acc_row(r', hi)
+            if (prod) {
+                const float* tt = sT[pb][wv];
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 t4 = *reinterpret_cast<const float4*>(&tt[lo * kTStride + 8 * g + 4 * hi]);
+                    dzt[4 * g] = t4.x; dzt[4 * g + 1] = t4.y; dzt[4 * g + 2] = t4.z; dzt[4 * g + 3] = t4.w;
+                }
+            }
+            RedRegs rg;
+            if (red) reduce_load(it & 1, rg);
+            CIRS_HSTAMPB(12);
+            f32x16 dw0, dw1;
+            float db = 0.f;
+            if (prod) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { dw0[r] = 0.f; dw1[r] = 0.f; db += dzt[r]; }
+                const HPl b0 = hsplit8(dzt, 0), b1 = hsplit8(dzt, 8);   // element j: dZ[row acc_row(8 t + j, hi)][item lo]
+                hmfma_pair(b0, hb[0][0], hb[1][0], dw0, dw1);
+                hmfma_pair(b1, hb[0][1], hb[1][1], dw0, dw1);
+            }
+            CIRS_HSTAMPB(13);
+            // next tile's planes -> the other LDS buffer (role A read it last in iteration it - 1, one barrier ago); no store of this iteration has been
+            // issued yet, so the wait is for loads only
+            if (issue) CIRS_COMMIT(pb);
+            if (red) reduce_store(rg, first_tile + (it - 2) * kTileN);
+            CIRS_HSTAMPB(14);
+            if (prod) {
+                float* rr = sR[pb][wv];    // this buffer was last read in iteration it - 1 (the sum of tile it - 3), one barrier ago
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int il = acc_row(r, hi);
+                    rr[il * kH + lo] = dw0[r];
+                    rr[il * kH + 32 + lo] = dw1[r];
+                }
+                rr[kTileN * kH + lane] = db;     // slot 32 hi + lo: the reducer adds the two halves
+            }
+            CIRS_HSTAMPB(15);
+        };
+        for (int it = 0; it <= n_tiles; ++it) {
+            if (it >= 2 && it + 1 < n_tiles) b_iter(std::true_type{}, it);
+            else b_iter(std::false_type{}, it);
+            lds_barrier();
+        }
+        RedRegs rg;
+        reduce_load((n_tiles - 1) & 1, rg);
+        reduce_store(rg, first_tile + (n_tiles - 1) * kTileN);
+    }
+#undef CIRS_ISSUE
+#undef CIRS_COMMIT
+}
+template <bool kEnt, bool kMerge, bool kZin>
+__global__ __launch_bounds__(kZin ? kBwdRoleThreads : kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I, int mb, int n_pad, int tiles_per_chunk,
+                                                                                                  const uint4* __restrict__ planes,
+                                                                                                  const float* __restrict__ ba, MbView v,
+                                                                                                  float* __restrict__ dwap, HeadMergeArgs ma) {
+    if constexpr (kZin) { head_bwd_roles<kEnt, kMerge>(I, mb, n_pad, tiles_per_chunk, planes, v, dwap, ma); return; }
+    constexpr int kThreads = kBwdWaves * 64;
+    static_assert(kThreads == 256, "the plane staging maps one 16-byte unit per thread and plane");
+    constexpr int kCOff = 3 * kRPlaneB;      // the C planes follow the R planes
+    __shared__ __attribute__((aligned(16))) unsigned char sW[2][kCOff + 3 * kCPlaneB];
+    __shared__ __attribute__((aligned(16))) float sB[2][kTileN];   // 16-byte aligned: the accumulator init reads 4 consecutive biases as one ds_read_b128
+    __shared__ __attribute__((aligned(16))) float sT[kBwdWaves][kTileN * kTStride];
+    __shared__ __attribute__((aligned(16))) float sR[2][kBwdWaves][kRSize];   // double-buffered: the sum of tile t runs inside iteration t + 1
+    const int tid = threadIdx.x;
+    CIRS_SSTAMP(30);
+    if (blockIdx.x == 0 && blockIdx.y == 0) {      // arrival flags of this step's trunk-backward / optimiser launches
+        v.sync[tid] = 0;
+        if (tid < kSyncInts - 256) v.sync[256 + tid] = 0;
+    }
+    const int lane = tid & 63, wv = tid >> 6;
+    const int hi = lane >> 5, lo = lane & 31;
+    const int row0 = (blockIdx.y * kBwdWaves + wv) * kTileM;
+    const bool wave_ok = row0 < n_pad;   // all waves take part in the staging, barriers and the slab reduction
+    const int chunk = blockIdx.x;
+    // gridDim.x is padded to a multiple of 8: workgroups are dealt round-robin to the 8 XCDs, so linear id % 8 = chunk % 8
+    // and the row blocks that walk the same chunk share one L2 (the Wa planes of a tile leave HBM / MALL once, not 8 times)
+    if (chunk * tiles_per_chunk * kTileN >= I) return;
+    const int jr = wave_ok ? row0 + lo : 0;
+    // The wave's 32 x 64 tile of H2 is 8 KB of consecutive memory: read coalesced (8 x 1 KB per wave) and handed to the lanes through
+    // LDS -- a lane reading its own 256-byte row costs 64 cache lines per load instruction (the prologue was 6.1 k of the kernel's
+    // 77 k ticks).  The row scalars are requested first; they travel while the tile does.
+    const float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
+    const int act = v.act[jr];
+    HPl hz[4];      // B operand of ZT: this lane's row of H2, element j of k-step s = column 16 s + 8 hi + j
+    HPl hb[2][2];   // B operand of the dWa product: element j of k-step t = H2[row acc_row(8 t + j, hi)][32 c + lo]
+    {   // both pre-split by trunk_adv_kernel in register order: 24 coalesced 16-byte loads per lane (the LDS round trip + 8 split8 of
+        // the round-2 prologue were 4.4 k of the kernel's 78 k ticks)
+        const size_t tb = (size_t)((wave_ok ? row0 : 0) >> 5) * 12 * 64 + lane;
+        const uint4* zp = v.h2z + tb;
+        const uint4* bp = v.h2b + tb;
+#pragma unroll
+        for (int s4 = 0; s4 < 4; ++s4) {
+            HPL_SET(hz[s4], zp[(3 * s4) * 64], zp[(3 * s4 + 2) * 64]);
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                HPL_SET(hb[c][t], bp[(3 * (2 * c + t)) * 64], bp[(3 * (2 * c + t) + 2) * 64]);
+            }
+    }
+    const bool row_ok = wave_ok && jr < mb;
+    f32x16 dh0, dh1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dh0[r] = 0.f; dh1[r] = 0.f; }
+    float ent = 0.f;  // clamp correction of the entropy (see below)
+    const float eps = 1.1920928955078125e-7f;
+    const float kLogEps = -15.942385152878742f, kLog1mEps = -1.1920929665620834e-7f;
+    if (!wave_ok) {
+        for (int q = lane; q < kRSize; q += 64) { sR[0][wv][q] = 0.f; sR[1][wv][q] = 0.f; }
+    }
+
+    const int first_tile = chunk * tiles_per_chunk * kTileN;
+    const int n_tiles = max(0, min(tiles_per_chunk, (I - first_tile + kTileN - 1) / kTileN));
+    // staging: unit `tid` of each of the six planes; destination offsets inside a buffer
+    const int dst_r = (tid >> 3) * kRowB + (tid & 7) * 16;
+    const int dst_c = kCOff + (tid >> 2) * kColB + (tid & 3) * 16;
+    uint4 gr0, gr2, gc0, gc2;
+    float gb = 0.f;
+#define CIRS_ISSUE(TILE0)                                                                                  \
+    do {                                                                                                   \
+        const uint4* src_ = planes + (size_t)((TILE0) / kTileN) * kPlaneTileU4 + tid;                      \
+        gr0 = src_[0]; gr2 = src_[512];                                                                    \
+        gc0 = src_[768]; gc2 = src_[1280];                                                                 \
+        if (tid < kTileN) gb = ((TILE0) + tid) < I ? kScZ * ba[(TILE0) + tid] : 0.f;   /* the accumulators hold kScZ z */ \
+    } while (0)
+#define CIRS_COMMIT(BUF)                                                                                   \
+    do {                                                                                                   \
+        unsigned char* base_ = sW[BUF];                                                                    \
+        *reinterpret_cast<uint4*>(base_ + dst_r) = gr0;                                                    \
+        *reinterpret_cast<uint4*>(base_ + 2 * kRPlaneB + dst_r) = gr2;                                     \
+        *reinterpret_cast<uint4*>(base_ + dst_c) = gc0;                                                    \
+        \
+        *reinterpret_cast<uint4*>(base_ + 2 * kCPlaneB + dst_c) = gc2;                                     \
+        if (tid < kTileN) sB[BUF][tid] = gb;                                                      \
+    } while (0)
+    // the first tile's planes and the H2 planes above are on their way while the row statistics are merged
+    if (n_tiles > 0) CIRS_ISSUE(first_tile);
+    const HeadRowCoef rc = head_row_coef<kEnt, kMerge>(v, ma, n_pad, mb, wave_ok, jr, hi);
+    float lse = rc.lse, c_logp = rc.c_logp, c_ent = rc.c_ent, h_ent = rc.h_ent;
     // f16x3: dZ is formed ALREADY SCALED by a power of two per workgroup -- its 128 rows' largest |c_logp| + 16 |c_ent| (a bound on |dZ|) lands in [2^13, 2^14) --
     // so that its fp16 pieces are normal numbers; dH2 / dWa / dba are unscaled exactly where they leave the kernel.
     float dz_scale = 1.0f, dz_inv = 1.0f;
@@ -1110,34 +1410,23 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             HPl cb[2][2];
             f32x16 acc;      // the logits' accumulator sum (kScZ z), then dZ in place
             RedRegs rg;
-            if (kZin) {
-                // the values head_stats_kernel formed for this (item tile, row tile); the next tile's are requested at once -- unconditionally, with a
-                // clamped tile number (the chunk's last iteration reads its own tile again)
+            HPl za[4];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) { acc[4 * q] = zn[q].x; acc[4 * q + 1] = zn[q].y; acc[4 * q + 2] = zn[q].z; acc[4 * q + 3] = zn[q].w; }
-                const float4* zp = zsl + (size_t)min(it + 1, n_tiles - 1) * zstep;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) zn[q] = zp[q * 64];
-                CIRS_HSTAMP(1);
-            } else {
-                HPl za[4];
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) {
-                    const unsigned char* ap = tw + lo * kRowB + (16 * s4 + 8 * hi) * 2;
-                    HPL_SET(za[s4], *reinterpret_cast<const uint4*>(ap), *reinterpret_cast<const uint4*>(ap + 2 * kRPlaneB));
-                }
-                f32x16 acc1, acc2;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { acc[r] = sB[buf][acc_row(r, hi)]; acc1[r] = 0.f; acc2[r] = 0.f; }
-                CIRS_HSTAMP(1);
-                // (acc: bias + the h*h terms, acc1 / acc2: the cross terms -- same split as head_stats_kernel, so that p = exp(z - lse) sums to one)
-                hmfma_split2(za[0], hz[0], za[1], hz[1], acc, acc1, acc2);
-                if (it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the second logits MFMA group
-                hmfma_split2(za[2], hz[2], za[3], hz[3], acc, acc1, acc2);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] += acc1[r] + acc2[r];      // = head_stats_kernel's acc + (accs + acct)
-                if (it > 0) reduce_store(rg, tile0 - kTileN);
+            for (int s4 = 0; s4 < 4; ++s4) {
+                const unsigned char* ap = tw + lo * kRowB + (16 * s4 + 8 * hi) * 2;
+                HPL_SET(za[s4], *reinterpret_cast<const uint4*>(ap), *reinterpret_cast<const uint4*>(ap + 2 * kRPlaneB));
             }
+            f32x16 acc1, acc2;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[r] = sB[buf][acc_row(r, hi)]; acc1[r] = 0.f; acc2[r] = 0.f; }
+            CIRS_HSTAMP(1);
+            // (acc: bias + the h*h terms, acc1 / acc2: the cross terms -- same split as head_stats_kernel, so that p = exp(z - lse) sums to one)
+            hmfma_split2(za[0], hz[0], za[1], hz[1], acc, acc1, acc2);
+            if (it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: their LDS round trip hides behind the second logits MFMA group
+            hmfma_split2(za[2], hz[2], za[3], hz[3], acc, acc1, acc2);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] += acc1[r] + acc2[r];      // = head_stats_kernel's acc + (accs + acct)
+            if (it > 0) reduce_store(rg, tile0 - kTileN);
             // the B planes of the dH2 product are requested only now: the A planes of the logits are dead (the two sets never coexist:
             // the kernel runs at the 256-VGPR limit and every value beyond it costs an AGPR copy per use) and the dZ arithmetic below
             // covers their LDS latency
@@ -1225,10 +1514,8 @@ __global__ __launch_bounds__(kBwdWaves * 64, 1) void head_bwd_fused_kernel(int I
             if (it + 1 < n_tiles) CIRS_COMMIT(buf ^ 1);
             {
                 const HPl a0 = hsplit8(acc, 0), a1 = hsplit8(acc, 8);   // element j: dZ[row lo][item acc_row(8 t + j, hi)]
-                if (kZin && it > 0) reduce_load(buf ^ 1, rg);      // the previous tile's partial dWa tiles: LDS round trip, adds and stores behind the dH2 MFMAs
                 hmfma_pair(a0, cb[0][0], cb[1][0], dh0, dh1);
                 hmfma_pair(a1, cb[0][1], cb[1][1], dh0, dh1);
-                if (kZin && it > 0) reduce_store(rg, tile0 - kTileN);
             }
             CIRS_HSTAMP(5);
             CIRS_HSTAMP(6);
@@ -1286,6 +1573,8 @@ __host__ inline HeadBwdFn head_bwd_fn(bool ent, bool merge, bool zin) {
     default: return head_bwd_fused_kernel<true, true, true>;
     }
 }
+// (the hand-over form runs two wave roles per row tile: twice the threads)
+__host__ inline int head_bwd_threads(bool zin) { return zin ? kBwdRoleThreads : kBwdWaves * 64; }
 // CIRS_PPO_HEAD_RECOMPUTE=1: the head backward forms the logits itself instead of reading head_stats_kernel's from the slab (read per call: the bit-identity
 // test and same-box A/B runs toggle it; not a tuning knob -- both forms give the same bits)
 __host__ inline bool head_recompute_env() {
@@ -2708,7 +2997,7 @@ static int launch_head(const PpoRun& r, const PpoStep& st, int* n_bchunks_out, b
     // chunking of the backward kernel: all workgroups co-resident (1 per CU) with equal tile counts -> no tail round
     const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
     const int n_bchunks = cdiv(n_item_tiles, tpc);  // <= n_chunks: the d h2 / entropy partial slabs fit
-    const dim3 bgrid((n_bchunks + 7) & ~7, n_slabs), bblock(kBwdWaves * 64);
+    const dim3 bgrid((n_bchunks + 7) & ~7, n_slabs), bblock(head_bwd_threads(!r.head_recompute));
     const HeadBwdFn bwd_fn = head_bwd_fn(r.cfg->ent_coef != 0.f, !r.merge_launch, !r.head_recompute);
     CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL(bwd_fn, bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)r.w.ba, v, v.dwap, hma));
     CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
@@ -3054,7 +3343,8 @@ extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, flo
         const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
         const int n_bchunks = cdiv(n_item_tiles, tpc);
         const HeadMergeArgs no_merge{};    // the row coefficients come from head_stats_merge_kernel above (statistics of every shard)
-        hipLaunchKernelGGL(head_bwd_fn(cfg->ent_coef != 0.f, false, !head_recompute_env()), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(kBwdWaves * 64), 0, s, I,
+        const bool zin = !head_recompute_env();
+        hipLaunchKernelGGL(head_bwd_fn(cfg->ent_coef != 0.f, false, zin), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(head_bwd_threads(zin)), 0, s, I,
                            (int)mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)w.ba, v, v.dwap, no_merge);
         CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
         CIRS_HIP(hipMemsetAsync(red_slots, 0, sizeof(float) * (size_t)world * kWaSumBlocks, s));

@@ -17,9 +17,11 @@ wl = bench.WORKLOADS["c3"]
 eng, _ = bench.build_engine(wl, 0, 1, torch.device("cuda:0"))
 eng.collect(); eng.update(1024, 1)
 lib = C.CDLL(abi.LIB_PATH)
-names = {0: "tile start", 1: "LDS operand reads (za, bias)", 2: "logits MFMAs (24) + dWa sum of the previous tile", 3: "dZ (exp2, coefficients, mask)",
-         4: "dZ^T -> LDS (+ branch-free clamp correction)", 5: "cb planes, split + dH2 MFMAs (24)", 6: "fence + dZ^T read back", 7: "split + dWa MFMAs (24)",
-         9: "partial-tile writes + plane commit", 10: "the tile's one barrier"}
+# the two-role form (the default): role A = wave 0, role B = wave 4 one iteration later, both at the workgroup's third tile
+names = {0: "A: tile start", 1: "A: slab values -> acc, next tile requested", 2: "A: C-plane operand reads", 3: "A: dZ (exp2, coefficients, action, mask)",
+         4: "A: dZ^T -> LDS (+ high-side clamp correction)", 5: "A: split + dH2 MFMAs (12)", 10: "A: the tile's one barrier",
+         11: "B: iteration start (one iteration later)", 12: "B: plane request, dZ^T read, partial tiles of the tile before", 13: "B: db, split + dWa MFMAs (12)",
+         14: "B: plane commit, wave-order sum + slab stores", 15: "B: partial-tile writes"}
 acc = None
 for rep in range(8):
     bench.hip_event_kernel_time(eng, wl, reps=2)
@@ -36,7 +38,7 @@ for k in sorted(names):
     print(f"  {names[k]:36s} {t[k] - prev:9.0f}   (cum {t[k] - t[0]:9.0f})")
     prev = t[k]
 
-ks = {30: "kernel entry", 31: "H2 operands loaded + split (hz, hb), row scalars", 32: "first planes tile staged + barrier", 33: "all tiles", 34: "last tile's dWa sum",
+ks = {30: "kernel entry", 31: "row coefficients (merge prologue)", 32: "barrier (first planes tile staged by role B)", 33: "all tiles",
       35: "dH2 / entropy partial stores"}
 print("head_bwd_fused_kernel, workgroup (0,0) thread 0, whole kernel:")
 prev = t[30]
