@@ -340,6 +340,10 @@ SIGNATURES = {
     "cirs_deepfm_validate": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
     "cirs_dice_validate_workspace_bytes": (C.c_int64, [C.POINTER(DiceCfg), C.c_int64]),
     "cirs_dice_validate": (C.c_int, [C.POINTER(DiceCfg), _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P]),
+    "cirs_linucb_update": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "cirs_linucb_solve": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "cirs_linucb_score": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "cirs_linucb_predict": (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     "cirs_mmoe_train_param_count": (C.c_int64, [C.POINTER(MmoeTrainCfg)]),
     "cirs_mmoe_train_workspace_bytes": (C.c_int64, [C.POINTER(MmoeTrainCfg), C.c_int32]),
     "cirs_mmoe_train_step": (C.c_int, [C.POINTER(MmoeTrainCfg), _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int32, _P, _P, C.c_int64, _P]),

@@ -53,14 +53,27 @@ def load_static_validate_data_kuaishou(entity_dim, feature_dim, datapath=None):
     return dataset_val
 
 
-def _training_log(entity_dim, feature_dim, datapath):
-    """The part the three training-set loaders share: big_matrix.csv joined with the item categories, the feature columns, and the
-    positive pair columns next to one sampled negative per row.  -> (big, list_feat, x_columns, y_columns, pos_x, pos_y, x_all)"""
+def _big_log(datapath):
+    """big_matrix.csv joined with the item categories, durations in seconds, the watch ratio clipped at 5 -> (big, list_feat, df_feat)."""
     big = pd.read_csv(os.path.join(datapath, "big_matrix.csv"), usecols=["user_id", "photo_id", "timestamp", "watch_ratio", "photo_duration"])
     big["photo_duration"] /= 1000
     list_feat, df_feat = item_feature_table(datapath)
     big = big.join(df_feat, on=["photo_id"], how="left")
     big.loc[big["watch_ratio"] > 5, "watch_ratio"] = 5
+    return big, list_feat, df_feat
+
+
+def load_log_kuaishou(datapath=None):
+    """The training log as the LinUCB baseline reads it (core/policy/linucb.py: linucb_trainer's df_x, df_y): the seven columns
+    [user_id, photo_id, feat0..3, photo_duration] of every row of big_matrix.csv and its watch ratio; no negatives, no exposure."""
+    big, _, _ = _big_log(DATAPATH if datapath is None else datapath)
+    return big[USER_COLS + ITEM_COLS], big[["watch_ratio"]]
+
+
+def _training_log(entity_dim, feature_dim, datapath):
+    """The part the three training-set loaders share: big_matrix.csv joined with the item categories, the feature columns, and the
+    positive pair columns next to one sampled negative per row.  -> (big, list_feat, x_columns, y_columns, pos_x, pos_y, x_all)"""
+    big, list_feat, df_feat = _big_log(datapath)
     x_columns = feature_columns(big["user_id"].max() + 1, big["photo_id"].max() + 1, df_feat.max().max() + 1, entity_dim, feature_dim)
     y_columns = [DenseFeat("y", 1)]
     pos_x, pos_y = big[USER_COLS + ITEM_COLS], big[["watch_ratio"]]

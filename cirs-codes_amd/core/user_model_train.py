@@ -165,6 +165,40 @@ def train_dice_kuaishou(datapath, save_root=".", callbacks=None, rl_test=None, m
     return SimpleNamespace(model=model, history=history, paths=paths, train_set=train_set, val_set=val_set, lbe_user=lbe_user, lbe_photo=lbe_photo)
 
 
+LINUCB_DEFAULTS = dict(env="KuaishouEnv-v0", model_name="LinUCB", message="LinUCB", alpha=0.25, epoch=5, feature_dim=8, num_leave_compute=1,
+                       leave_threshold=0, max_turn=100)
+
+
+def train_linucb_kuaishou(datapath, save_root=".", logger=None, metric_fun=None, **overrides):
+    """The run of the LinUCB baseline (core/policy/linucb.py; the reference ships the module without a script, so the steps are those of
+    the other Kuaishou baselines): KuaiRec files -> the training log as df_x (the seven columns [user, photo, feat0..3, duration]) and
+    df_y (the watch ratio), the validation set and the evaluation env -> linucb_policy with one arm per env item, d = 2 + the width of
+    df_photo_env -> linucb_trainer on the device: per epoch one ordered accumulation over the log, the validation metrics of
+    metric_fun (default: the scripts' mae and mse) and evaluation.test_kuaishou, one log line each.  `logger`: anything with
+    .info(str); default: lines are kept only in the returned history.
+    Returns SimpleNamespace(model, history, val_set, lbe_user, lbe_photo), history = linucb_trainer's per-epoch result dicts."""
+    from core.policy.linucb import linucb_policy, linucb_trainer
+    from core.user_data import load_log_kuaishou
+    from core.user_model import metric_mae, metric_mse
+    a = SimpleNamespace(**{**LINUCB_DEFAULTS, **overrides})
+    model_dir = os.path.join(save_root, "saved_models", a.env, a.model_name)
+    os.makedirs(os.path.join(model_dir, "logs"), exist_ok=True)
+
+    mat, lbe_user, lbe_photo, list_feat, df_photo_env, df_dist_small = KuaishouEnv.load_mat(datapath)
+    df_x, df_y = load_log_kuaishou(datapath)
+    val_set = load_static_validate_data_kuaishou(a.feature_dim, a.feature_dim, datapath)
+    env = KuaishouEnv(mat, lbe_user, lbe_photo, list_feat, df_photo_env, df_dist_small, num_leave_compute=a.num_leave_compute,
+                      leave_threshold=a.leave_threshold, max_turn=a.max_turn)
+
+    model = linucb_policy(len(val_set.df_photo_env), 2 + val_set.df_photo_env.shape[1], a.alpha)
+    if logger is None:
+        logger = SimpleNamespace(info=lambda msg: None)
+    if metric_fun is None:
+        metric_fun = {"mae": metric_mae, "mse": metric_mse}
+    history = linucb_trainer(model, env, a.epoch, df_x, df_y, val_set, logger, metric_fun)
+    return SimpleNamespace(model=model, history=history, val_set=val_set, lbe_user=lbe_user, lbe_photo=lbe_photo)
+
+
 TAOBAO_DEFAULTS = dict(env="VirtualTB-v0", user_model_name="MLP", message="UM", tau=0.01, feature_dim=8, dnn=(64, 64), batch_size=100,
                        epoch=5, seed=2022)
 

@@ -2,6 +2,7 @@
 
   get_feat_dominate_dict   evaluation.py:10-77  ("ifeat_feat": share of recommendations carrying a dominating category)
   Callback_Coverage_Count  evaluation.py:286-371 (CV, CV_turn and ifeat_* for the FB / NX_0 / NX_k test collectors)
+  test_kuaishou            evaluation.py:179-234  (the per-epoch evaluation loop of the LinUCB baseline, core/policy/linucb.py)
   test_taobao              evaluation.py:238-282  (the VirtualTaobao static baselines: MLP-taobao.py, MLP-epsilonGreedy-taobao.py)
 
 The reference walks the replay buffers on the host (buffer.prev / buffer.next); here each collector's buffer carries the
@@ -156,6 +157,47 @@ def test_static_model_in_RL_env(model, env, dataset_val, is_softmax=True, epsilo
 
 
 test_static_model_in_RL_env.__test__ = False  # not a pytest test
+
+
+def test_kuaishou(model, env, dataset_val, is_softmax=True, epsilon=0, is_ucb=False, *, users=None, num_trajectory=200):
+    """reference evaluation.py:179-234 for a model that keeps the device LinUCB state (core.policy.linucb.linucb_policy): the
+    num_trajectory trajectories in LOCK-STEP.  The model does not change during the loop, so a trajectory recommends the same item at
+    every step until the env's exit rule ends it: one scoring launch gives every trajectory user its item and the predicted reward
+    (recommend_k_item for all of them at once), then one cirs_rollout_static plays the trajectories, the item handed over as a [B, I]
+    indicator matrix of scores.  click_loss comes from the returned means against the trajectory rewards in float64.  Same result
+    dict.  `users` (env numbering) can be supplied; the reference draws them inside env.reset() with the unseeded `random`."""
+    from cirs_hip.static_policy import StaticRollout
+    state = getattr(model, "device_state", None)
+    if state is None:
+        raise TypeError("test_kuaishou plays a model with the device LinUCB state (core.policy.linucb.linucb_policy)")
+    if epsilon != 0 or is_ucb:
+        raise ValueError("test_kuaishou: the LinUCB policy explores through its own upper confidence bound: epsilon must be 0 and is_ucb False")
+    df_item_val = dataset_val.df_photo_env
+    item_index = df_item_val.index.to_numpy()
+    assert np.array_equal(item_index, np.asarray(env.lbe_photo.classes_)), "df_photo_env must be in env item order (lbe_photo.classes_)"
+    I = len(item_index)
+    if users is None:
+        users = np.random.randint(0, env.mat.shape[0], int(num_trajectory))
+    users = np.asarray(users)
+    B = len(users)
+    raw_users = np.asarray(env.lbe_user.classes_)[users]
+    best, mean = state.score(raw_users.astype(np.float64), df_item_val.to_numpy())       # [B] arm (= env item id), [B] theta^T x
+    dev_env = env.build_device_env(B)
+    scores = torch.zeros((B, I), dtype=torch.float32, device=dev_env.device)
+    scores[torch.arange(B, device=dev_env.device), best.to(dev_env.device)] = 1.0
+    ro = StaticRollout(dev_env)
+    ro.run(torch.as_tensor(users), scores, softmax=False)
+    valid = ro.act >= 0
+    total_turns = int(valid.sum())
+    cumulative_reward = float((ro.rew * valid).sum())
+    total_click_loss = float(((mean.to(ro.rew.device)[None, :] - ro.rew).abs() * valid).sum())
+    hit_item, n_acts, _ = CoverageCounter(I, device=ro.act.device).count(ro.act, None)
+    test_kuaishou.last_rollout = ro
+    return {"click_loss": total_click_loss / total_turns, "CV": f"{hit_item / I:.5f}", "CV_turn": f"{hit_item / n_acts:.5f}",
+            "ctr": cumulative_reward / total_turns, "len_tra": total_turns / B, "R_tra": cumulative_reward / B}
+
+
+test_kuaishou.__test__ = False  # not a pytest test
 
 
 def test_taobao(model, env, epsilon=0, *, device=None, num_trajectory=100, seed=0):

@@ -728,6 +728,36 @@ int cirs_dice_validate(const cirs_dice_cfg* cfg, const float* params, const int6
                        const float* dur, const double* y, int64_t n, float* pred_out, double* sums_out, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* ---- the disjoint-arm LinUCB baseline (csrc/linucb.hip) --------------------------------------------------------------
+ * replaces  core/policy/linucb.py (paths relative to the reference root).  Everything is float64.  n_arms arms keep A [n_arms, d, d]
+ * (identity at start) and b [n_arms, d] (zero at start); 2 <= d <= 16, anything else is refused with CIRS_E_UNSUPPORTED.
+ *
+ * cirs_linucb_update replaces the per-row loop of linucb_trainer (:168-180) and linucb_disjoint_arm.reward_update (:59-68):
+ *   x [n_rows, ld >= d], y [n_rows]: the log;  order [m]: row indices grouped by arm and, inside an arm, in log order;
+ *   seg [n_arms + 1]: arm a owns order[seg[a] .. seg[a + 1]).  Every element of A_a and b_a is owned by one lane, which walks the
+ *   arm's rows in that order with a rounded product and then a rounded sum: A and b are bit-identical to the reference's loop.
+ *   It continues from the A and b it is given (epochs accumulate).  m == 0 or n_arms == 0: nothing is launched, 0 is returned.
+ *   An entry of order outside [0, n_rows) adds nothing.
+ * cirs_linucb_solve replaces the A_inv and theta properties (:33-40): A_inv [n_arms, d, d] = inv(A_a), theta [n_arms, d] = inv(A_a) b_a
+ *   for every arm (arms == NULL) or for arms[0 .. n_listed) only; Cholesky plus iterative refinement with the residual in twice the
+ *   working precision.
+ * cirs_linucb_score replaces calc_UCB / calc_reward (:28-57) inside the loops of recommend_k_item (:133-159) and select_arm (:77-103):
+ *   x_fixed == NULL: for every user u < n_users and arm a, x = [users[u], a, item_feats[a, 0 .. d - 2)] (item_feats [n_arms, d - 2]);
+ *   x_fixed [d]: the one x of select_arm / forward scored against every arm (n_users is ignored, one output row).
+ *   mean = theta_a^T x, ucb = mean + alpha sqrt(x^T A_inv_a x).  best_arm [rows] int64 = the first arg-max of ucb over the arms,
+ *   best_mean [rows] = that arm's mean; ucb_out / mean_out / var_out [rows, n_arms] or NULL each (var = x^T A_inv_a x).
+ * cirs_linucb_predict replaces the per-row loop of evaluate_data (:120-126): y_pred[r] = theta[arm[r]]^T x[r] (x [n, ld >= d]),
+ *   0 where arm[r] lies outside [0, n_arms). */
+int cirs_linucb_update(double* A, double* b, int32_t n_arms, int32_t d, const double* x, int64_t ld, int64_t n_rows, const double* y,
+                       const int64_t* order, int64_t m, const int64_t* seg, void* stream);
+int cirs_linucb_solve(const double* A, const double* b, int32_t n_arms, int32_t d, const int32_t* arms, int32_t n_listed, double* A_inv,
+                      double* theta, void* stream);
+int cirs_linucb_score(const double* A_inv, const double* theta, int32_t n_arms, int32_t d, const double* users, int32_t n_users,
+                      const double* item_feats, const double* x_fixed, double alpha, int64_t* best_arm, double* best_mean,
+                      double* ucb_out, double* mean_out, double* var_out, void* stream);
+int cirs_linucb_predict(const double* theta, int32_t n_arms, int32_t d, const double* x, int64_t ld, const int64_t* arm, int64_t n,
+                        double* y_pred, void* stream);
+
 /* ---- user-model dataset preparation ---------------------------------------------------------------
  * cirs_exposure_history replaces compute_exposure_each_user / the per-user loop of compute_exposure_effect_kuaishouRec
  * (reference core/util.py:56-76,135-169): rows are the logged interactions in file order, a user's rows contiguous;
