@@ -247,6 +247,8 @@ SIGNATURES = {
     "cirs_vtb_rollout_collect_redraw": (C.c_int, [C.POINTER(VtbRolloutCfg), C.POINTER(VtbPolicyWeights), C.POINTER(VtbCfg),
                                                   C.POINTER(VtbWeights), C.POINTER(VtbState), C.POINTER(VtbTraj), _P, C.c_uint64, C.c_uint32,
                                                   _P]),
+    "cirs_vtb_rollout_collect_greedy": (C.c_int, [C.POINTER(VtbRolloutCfg), C.POINTER(VtbPolicyWeights), C.POINTER(VtbCfg),
+                                                  C.POINTER(VtbWeights), C.POINTER(VtbState), C.POINTER(VtbTraj), _P, _P]),
     "cirs_vtb_learn_redraw_sizes": (C.c_int, [C.POINTER(VtbLearnCfg), _P]),
     "cirs_vtb_learn_prepare_redraw": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P]),
     "cirs_vtb_learn_update_redraw": (C.c_int, [C.POINTER(VtbLearnCfg), C.POINTER(VtbLearnBufs), _P, C.c_int32, C.c_int32, C.c_int32,
@@ -258,6 +260,11 @@ SIGNATURES = {
     "cirs_policy_workspace_bytes": (C.c_int64, [C.POINTER(PolicyCfg), C.c_int32]),
     "cirs_actor_sample": (C.c_int, [C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), _P, C.c_int64, C.c_int32, _P,
                                     C.c_uint64, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "cirs_actor_greedy": (C.c_int, [C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), _P, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P, _P,
+                                    C.c_int64, _P]),
+    "cirs_actor_topk_workspace_bytes": (C.c_int64, [C.POINTER(PolicyCfg), C.c_int32, C.c_int32]),
+    "cirs_actor_topk": (C.c_int, [C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                  _P, C.c_int64, _P]),
     "cirs_critic_values": (C.c_int, [C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_rollout_steps": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState),
                                      C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState),
@@ -267,6 +274,14 @@ SIGNATURES = {
                                        C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState),
                                        C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32,
                                        _P, C.c_uint64, C.c_uint32, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_rollout_steps_greedy": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState),
+                                            C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState),
+                                            C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32,
+                                            C.c_int32, C.c_int32, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_rollout_collect_greedy": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState),
+                                              C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState),
+                                              C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32,
+                                              _P, _P, C.c_int32, _P, C.c_int64, _P]),
     "cirs_rollout_steps_redraw": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState),
                                             C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState),
                                             C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32,

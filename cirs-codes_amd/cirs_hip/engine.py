@@ -167,7 +167,16 @@ class CirsEngine:
         self._user_rng = np.random.RandomState(seed * 1000003 + rank)
 
     # ---- rollout ------------------------------------------------------------------------------------------------
-    def collect(self, users: Optional[torch.Tensor] = None, sync_every: Optional[int] = None):
+    def collect(self, users: Optional[torch.Tensor] = None, sync_every: Optional[int] = None, greedy: bool = False):
+        """greedy: every action is the arg-max of the masked logits (deterministic evaluation, cirs_rollout_collect_greedy) -- one rank,
+        precomputed reward table, position-keyed dropout only."""
+        if greedy:
+            if self.world != 1:
+                raise NotImplementedError("greedy collect runs on one rank (multi-rank engines are out of scope)")
+            if self.dropout_redraw:
+                raise NotImplementedError("the exact-redraw rollout has no greedy mode")
+            if self.rollout.online is not None:
+                raise NotImplementedError("the online-reward rollout has no greedy mode")
         if users is None:
             # pinned double buffer + asynchronous upload: the host does not block on the stream (it is usually one whole
             # update ahead of the GPU here), so the rollout launches queue behind the update without a bubble
@@ -190,7 +199,8 @@ class CirsEngine:
             self.users = users.to(self.device, torch.int32)
         rng_base = (self.collect_count * self.max_turn) & 0xFFFFFFFF
         # RNG key = (seed, rank) so ranks draw independent noise; counter = (item, local env id, step)
-        self.lengths = self.rollout.collect(self.users, seed=(self.seed << 8) + self.rank, rng_base=rng_base, sync_every=sync_every)
+        self.lengths = self.rollout.collect(self.users, seed=(self.seed << 8) + self.rank, rng_base=rng_base, sync_every=sync_every,
+                                            **({"greedy": True} if greedy else {}))
         self.collect_count += 1
         return self.lengths
 

@@ -29,6 +29,7 @@ class DevicePolicy:
         self.w = weights_struct(params)
         self._lib = abi.lib()
         self._ws = None
+        self._topk_ws = None
         self.n_items = n_items
 
     def refresh_weights(self):
@@ -69,3 +70,36 @@ class DevicePolicy:
                                               abi.ptr(skip), act.data_ptr(), logp.data_ptr(), value.data_ptr(),
                                               ws.data_ptr(), ws.numel(), self._stream()), "cirs_actor_sample")
         return act, logp, value
+
+    def greedy(self, state, *, state_stride=None, n=None, env_ids=None, visited=None, skip=None, act_out=None, logp_out=None, value_out=None):
+        """`sample` without noise (cirs_actor_greedy): the unmasked item of largest logit per row, ties to the lowest id -- what the
+        reference's forward takes in eval mode under deterministic_eval (core/policy/ppo.py:149-151)."""
+        n = state.shape[0] if n is None else n
+        state_stride = state.stride(0) if state_stride is None else state_stride
+        dev = self.device
+        act = act_out if act_out is not None else torch.empty(n, dtype=torch.int64, device=dev)
+        logp = logp_out if logp_out is not None else torch.empty(n, dtype=torch.float32, device=dev)
+        value = value_out if value_out is not None else torch.empty(n, dtype=torch.float32, device=dev)
+        ws = self.workspace(n)
+        abi.check(self._lib.cirs_actor_greedy(C.byref(self.cfg), C.byref(self.w), state.data_ptr(), state_stride, n, abi.ptr(env_ids),
+                                              abi.ptr(visited), abi.ptr(skip), act.data_ptr(), logp.data_ptr(), value.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), self._stream()), "cirs_actor_greedy")
+        return act, logp, value
+
+    def topk(self, state, k, env_ids=None, visited=None, skip=None):
+        """(ids [n, k] int64, logp [n, k] float32): the k unmasked items of largest logit per row in descending order, ties to the lower
+        id first; -1 / -inf where fewer than k items are left or the row is skipped (cirs_actor_topk).  k = 1 is `greedy`."""
+        k = int(k)
+        if not 1 <= k <= 32:
+            raise ValueError(f"k must lie in 1..32, got {k}")
+        n = state.shape[0]
+        ids = torch.empty((n, k), dtype=torch.int64, device=self.device)
+        logp = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        need = self._lib.cirs_actor_topk_workspace_bytes(C.byref(self.cfg), n, k)
+        if self._topk_ws is None or self._topk_ws.numel() < need:
+            self._topk_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._topk_ws
+        abi.check(self._lib.cirs_actor_topk(C.byref(self.cfg), C.byref(self.w), state.data_ptr(), state.stride(0), n, k, abi.ptr(env_ids),
+                                            abi.ptr(visited), abi.ptr(skip), ids.data_ptr(), logp.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            self._stream()), "cirs_actor_topk")
+        return ids, logp

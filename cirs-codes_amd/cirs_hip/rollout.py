@@ -99,8 +99,22 @@ class DeviceRollout:
         B, S = self.env.n_env, self.tracker.dim_state
         self.tracker.init(users, out=self.traj.obs[0], out_stride=S)
 
-    def run_steps(self, t_begin, t_end, seed, rng_base, gumbel=None):
+    def _check_greedy(self, gumbel):
+        if gumbel is not None:
+            raise ValueError("greedy=True draws no noise: it cannot be combined with gumbel=")
+        if self.online is not None:
+            raise NotImplementedError("the online-reward rollout has no greedy mode (out of scope: precompute the reward table)")
+
+    def run_steps(self, t_begin, t_end, seed, rng_base, gumbel=None, greedy=False):
         ws = self.policy.workspace(self.env.n_env)
+        if greedy:      # the arg-max action (deterministic_eval in eval mode): seed / rng_base are not used
+            self._check_greedy(gumbel)
+            abi.check(self._lib.cirs_rollout_steps_greedy(
+                C.byref(self.env.cfg), C.byref(self.env._tab), C.byref(self.env._st), C.byref(self.tracker.cfg),
+                C.byref(self.tracker.w), C.byref(self.tracker.st), C.byref(self.policy.cfg), C.byref(self.policy.w),
+                C.byref(self.traj.struct), self.env.n_env, t_begin, t_end, abi.ptr(self.visited), self.force_length,
+                ws.data_ptr(), ws.numel(), self._stream()), "cirs_rollout_steps_greedy")
+            return
         if gumbel is not None:      # harness-supplied sampler noise (parity fixtures recorded from the reference)
             assert self.online is None and gumbel.dtype == torch.float32 and gumbel.is_contiguous()
             assert tuple(gumbel.shape) == (self.env.max_turn, self.env.n_env, self.policy.n_items)
@@ -124,10 +138,14 @@ class DeviceRollout:
             C.byref(self.traj.struct), self.env.n_env, t_begin, t_end, seed, rng_base, abi.ptr(self.visited),
             self.force_length, ws.data_ptr(), ws.numel(), self._stream()), "cirs_rollout_steps")
 
-    def collect(self, users: torch.Tensor, *, seed=0, rng_base=0, sync_every: Optional[int] = None, gumbel=None):
+    def collect(self, users: torch.Tensor, *, seed=0, rng_base=0, sync_every: Optional[int] = None, gumbel=None, greedy=False):
         """One `collect(n_episode = n_env)`: all envs run to the end of their episode.  Returns (n_steps, lengths).
         sync_every: poll the live-env count every that many steps to stop early (None: run all max_turn steps
-        without any host sync; idle steps of finished envs are no-ops)."""
+        without any host sync; idle steps of finished envs are no-ops).
+        greedy: every action is the arg-max of the masked logits (cirs_rollout_collect_greedy); seed / rng_base then only key the
+        tracker's dropout."""
+        if greedy:
+            self._check_greedy(gumbel)
         if self.tracker.cfg.dropout_p > 0:   # fresh masks per collect (the reference draws fresh dropout noise at every call)
             self.tracker.set_dropout_key(seed >> 8 if self.dropout_key_from_high_bits else seed, rng_base, self.dropout_env_base)
         T = self.env.max_turn
@@ -138,6 +156,14 @@ class DeviceRollout:
             if self.visited is not None:
                 self.visited.zero_()
             ws = self.policy.workspace(self.env.n_env)
+            self._users_keepalive = users_d
+            if greedy:
+                abi.check(self._lib.cirs_rollout_collect_greedy(
+                    C.byref(self.env.cfg), C.byref(self.env._tab), C.byref(self.env._st), C.byref(self.tracker.cfg),
+                    C.byref(self.tracker.w), C.byref(self.tracker.st), C.byref(self.policy.cfg), C.byref(self.policy.w),
+                    C.byref(self.traj.struct), self.env.n_env, users_d.data_ptr(), abi.ptr(self.visited), self.force_length,
+                    ws.data_ptr(), ws.numel(), self._stream()), "cirs_rollout_collect_greedy")
+                return self.env.turn.clone()
             abi.check(self._lib.cirs_rollout_collect(
                 C.byref(self.env.cfg), C.byref(self.env._tab), C.byref(self.env._st), C.byref(self.tracker.cfg),
                 C.byref(self.tracker.w), C.byref(self.tracker.st), C.byref(self.policy.cfg), C.byref(self.policy.w),
@@ -151,12 +177,12 @@ class DeviceRollout:
             self.run_steps(0, T, seed, rng_base, gumbel=gumbel)
             self._gumbel_keep = gumbel
         elif sync_every is None:
-            self.run_steps(0, T, seed, rng_base)
+            self.run_steps(0, T, seed, rng_base, greedy=greedy)
         else:
             t = 0
             while t < T:
                 t2 = min(T, t + sync_every)
-                self.run_steps(t, t2, seed, rng_base)
+                self.run_steps(t, t2, seed, rng_base, greedy=greedy)
                 t = t2
                 if t < T and bool(self.env.done.all()):
                     break

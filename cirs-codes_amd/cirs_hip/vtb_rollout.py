@@ -96,8 +96,9 @@ class DeviceVtbRollout:
 
     dropout_p = property(lambda self: self.model.dropout_p)
 
-    def collect(self, seed, collect_id, dropout_seed=0, force_length=None):
-        """One collect of every env; returns the episode lengths (numpy, the only synchronisation)."""
+    def collect(self, seed, collect_id, dropout_seed=0, force_length=None, greedy=False):
+        """One collect of every env; returns the episode lengths (numpy, the only synchronisation).
+        greedy: act = mu, no Gaussian draw (cirs_vtb_rollout_collect_greedy: deterministic_eval in eval mode); seed / collect_id are unused."""
         if force_length is not None:
             self.cfg.force_length = int(force_length)
         self.cfg.model.dropout_p = self.dropout_p
@@ -106,7 +107,10 @@ class DeviceVtbRollout:
         self.pack()
         args = (C.byref(self.cfg), C.byref(self._w), C.byref(self.vtb.cfg), C.byref(self.vtb._wst), C.byref(self.vtb._st), C.byref(self._tr))
         key = (u64(seed), int(collect_id) & 0xFFFFFFFF, stream(self.device))
-        if self.dropout_redraw:
+        if greedy:
+            abi.check(self._lib.cirs_vtb_rollout_collect_greedy(*args, abi.ptr(self._redraw_ws) if self.dropout_redraw else None, key[2]),
+                      "cirs_vtb_rollout_collect_greedy")
+        elif self.dropout_redraw:
             abi.check(self._lib.cirs_vtb_rollout_collect_redraw(*args, self._redraw_ws.data_ptr(), *key), "cirs_vtb_rollout_collect_redraw")
         else:
             abi.check(self._lib.cirs_vtb_rollout_collect(*args, *key), "cirs_vtb_rollout_collect")

@@ -134,7 +134,10 @@ class Collector:
             users = self.env.draw_users(self.env_num)
         users_t = torch.as_tensor(np.asarray(users))
         T = ro.env.max_turn
-        lengths = ro.collect(users_t, seed=self.sampler_seed(), rng_base=(self._collect_count * T) & 0xFFFFFFFF, gumbel=gumbel).cpu().numpy()
+        # deterministic_eval (reference core/policy/ppo.py:56,149-151): in eval mode the policy's arg-max action, no sampler noise
+        greedy = bool(getattr(self.policy, "_deterministic_eval", False) and not self.policy.training)
+        lengths = ro.collect(users_t, seed=self.sampler_seed(), rng_base=(self._collect_count * T) & 0xFFFFFFFF, gumbel=gumbel,
+                             greedy=greedy).cpu().numpy()
         self._collect_count += 1
         self.buffer.fill_from_trajectory(ro.traj, lengths)
         self.buffer._rollout, self.buffer._users = ro, users_t  # policy.update() consumes them with the buffer

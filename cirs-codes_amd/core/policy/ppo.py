@@ -41,7 +41,8 @@ class PPOPolicy(nn.Module):
                  action_bound_method="clip", action_space=None, lr_scheduler=None, deterministic_eval=False, **kwargs):
         super().__init__()
         assert dual_clip is None or dual_clip > 1.0, "Dual-clip PPO parameter should greater than 1.0."   # reference ppo.py:79-80
-        assert not deterministic_eval, "the reference never enables deterministic_eval for KuaishouEnv (SURVEY Q10)"
+        # reference ppo.py:56,149-151: in eval mode forward takes logits_masked.argmax(-1) instead of a sample (the discrete rule)
+        self._deterministic_eval = bool(deterministic_eval)
         if not reward_normalization:
             assert not value_clip, "value clip is available only when `reward_normalization` is True"
         self.actor, self.critic = actor, critic
@@ -157,6 +158,23 @@ class PPOPolicy(nn.Module):
         buffer exactly like core/policy/utils.py:7-27 does (walk `buffer.prev` from the last index of every unfinished sub-buffer)
         and masked through the sampler's visited bitmap (the reference drops them from the probability vector and renormalises,
         :30-58 -- the same distribution).  Rows are the live envs in ascending order, as in the reference."""
+        obs, env_ids, visited = self._rows(batch, buffer, remove_recommended_ids)
+        if self._deterministic_eval and not self.training:      # reference ppo.py:149-151: logits_masked.argmax(-1); no noise, no counter
+            act, logp, value = self._dev_policy.greedy(obs, env_ids=env_ids, visited=visited)
+            return Batch(logits=None, act=act, state=None, dist=None, policy=Batch(logp=logp, value=value))
+        self._step_counter = getattr(self, "_step_counter", 0) + 1
+        act, logp, value = self._dev_policy.sample(obs, seed=self.seed, rng_step=self._step_counter & 0xFFFFFFFF, env_ids=env_ids, visited=visited)
+        return Batch(logits=None, act=act, state=None, dist=None, policy=Batch(logp=logp, value=value))
+
+    def topk(self, batch, k, buffer=None, remove_recommended_ids=False):
+        """The policy's top-k list for every row of `batch`: Batch(act [n, k] item ids by descending logit (ties: the lower id first),
+        policy=Batch(logp [n, k])); -1 / -inf where fewer than k items are left.  remove_recommended_ids masks as in forward."""
+        obs, env_ids, visited = self._rows(batch, buffer, remove_recommended_ids)
+        ids, logp = self._dev_policy.topk(obs, k, env_ids=env_ids, visited=visited)
+        return Batch(act=ids, policy=Batch(logp=logp))
+
+    def _rows(self, batch, buffer, remove_recommended_ids):
+        """(obs on the device, env_ids, visited bitmap) of a per-step call."""
         obs = batch.obs
         obs = obs if isinstance(obs, torch.Tensor) else torch.as_tensor(np.asarray(obs), dtype=torch.float32)
         obs = obs.to(self.flat.device, torch.float32).contiguous()
@@ -178,9 +196,7 @@ class PPOPolicy(nn.Module):
                 idx = prv
             visited = torch.as_tensor(bm.view(np.int32)).to(self.flat.device)
             env_ids = torch.arange(n, dtype=torch.int32, device=self.flat.device)   # bitmap rows = batch rows
-        self._step_counter = getattr(self, "_step_counter", 0) + 1
-        act, logp, value = self._dev_policy.sample(obs, seed=self.seed, rng_step=self._step_counter & 0xFFFFFFFF, env_ids=env_ids, visited=visited)
-        return Batch(logits=None, act=act, state=None, dist=None, policy=Batch(logp=logp, value=value))
+        return obs, env_ids, visited
 
     def _get_learner(self, n_env, max_turn):
         if self._learner is None or self._learner.n_env != n_env or self._learner.max_turn != max_turn:

@@ -108,14 +108,13 @@ class DeviceVtbCollector:
         assert n_step is None and n_episode is not None, "the CIRS scripts collect whole episodes (n_episode)"
         if n_episode != self.env_num:
             raise ValueError("n_episode must equal the number of envs (finished envs are not reset, SURVEY Q4)")
-        if self.policy._deterministic_eval and not self.policy.training:
-            raise NotImplementedError("deterministic_eval is not supported by the device rollout")
+        greedy = bool(self.policy._deterministic_eval and not self.policy.training)      # the mean action (core/policy/ppo.py:152-153)
         self.reset()
         clock = time.time()
         ro = self.rollout()
         cid = self._collect_count
         seed, dseed = self.keys(cid)
-        lens = ro.collect(seed, cid, dropout_seed=dseed)
+        lens = ro.collect(seed, cid, dropout_seed=dseed, greedy=greedy)
         self._collect_count += 1
         self.last_collect = (seed, cid, dseed)
         tr = {k: ro.traj[k].cpu() for k in ("obs0", "obs", "rew", "done", "ctr", "act", "state")}

@@ -77,6 +77,24 @@ __global__ __launch_bounds__(256) void actor_pick_kernel(PickArgs a, int n, cons
     if (logp_out) logp_out[j] = cand_logp(r);
 }
 
+// top-k list of n rows (one wavefront per row) from the no-noise head's partials and its logit store
+__global__ __launch_bounds__(256) void actor_topk_kernel(int n, int n_pad, int n_chunks, int n_tiles, ActorPartialView pv, const float* __restrict__ zfull,
+                                                         const uint8_t* __restrict__ skip, int k, int64_t* __restrict__ ids_out,
+                                                         float* __restrict__ logp_out) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n) return;
+    if (skip && skip[j]) {
+        for (int r = lane; r < k; r += CIRS_WAVE) {
+            ids_out[(size_t)j * k + r] = -1;
+            if (logp_out) logp_out[(size_t)j * k + r] = -INFINITY;
+        }
+        return;
+    }
+    const Cand c = actor_merge_chunks(j, lane, n_pad, n_chunks, pv, nullptr);
+    actor_topk_wave(j, lane, n_pad, n_tiles, zfull, c.m, c.s, k, ids_out, logp_out);
+}
+
 // cross-rank merge of W shard tuples per env row, in RANK ORDER (fixed): candidate with the highest noisy score (ties -> lowest
 // global id), running (max, sum-exp) folded rank by rank; logp of the winner with Categorical's clamp (as actor_merge_wave)
 __global__ __launch_bounds__(256) void actor_merge_shards_kernel(const float* __restrict__ tuples, int n_shards, int n,
@@ -187,11 +205,82 @@ extern "C" int cirs_actor_sample(const cirs_policy_cfg* cfg, const cirs_policy_w
         return CIRS_OK;
     }
     const dim3 grid(hg.grid_x, hg.n_row_blocks);
-    hipLaunchKernelGGL(actor_head_kernel, grid, dim3(256), 0, s, *cfg, w->wa, w->ba, h2, n, gumbel, seed,
+    hipLaunchKernelGGL(actor_head_kernel<kNoiseHarness>, grid, dim3(256), 0, s, *cfg, w->wa, w->ba, h2, n, gumbel, seed,
                        rng_step, env_ids, visited, skip, pv, n_pad, hg.tiles_per_chunk);
     CIRS_CHECK_LAUNCH("actor_head_kernel");
     hipLaunchKernelGGL(actor_merge_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, n, n_pad, n_chunks, pv, skip, act_out, logp_out);
     CIRS_CHECK_LAUNCH("actor_merge_kernel");
+    return CIRS_OK;
+}
+
+namespace cirs {
+// trunk + no-noise head for n rows; zfull non-null: the head also keeps the masked logits
+static int greedy_head(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, const float* state, int64_t state_stride, int32_t n,
+                       const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, float* value_out, void* workspace, float* zfull,
+                       hipStream_t s) {
+    float* h2 = (float*)workspace;
+    const int n_pad = n_pad_of(n);
+    const HeadGrid hg = sampler_grid(cfg->n_items, n_pad);
+    ActorPartialView pv = partial_view(workspace, n, cfg->n_items);
+    hipLaunchKernelGGL(trunk_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, *cfg, *w, state, (long)state_stride, n, skip, h2, value_out, nullptr);
+    CIRS_CHECK_LAUNCH("trunk_kernel");
+    const dim3 grid(hg.grid_x, hg.n_row_blocks);
+    if (zfull)
+        hipLaunchKernelGGL((actor_head_kernel<kNoiseNone, true>), grid, dim3(256), 0, s, *cfg, w->wa, w->ba, (const float*)h2, n, (const float*)nullptr,
+                           (uint64_t)0, 0u, env_ids, visited, skip, pv, n_pad, hg.tiles_per_chunk, 0, 0, zfull);
+    else
+        hipLaunchKernelGGL((actor_head_kernel<kNoiseNone, false>), grid, dim3(256), 0, s, *cfg, w->wa, w->ba, (const float*)h2, n, (const float*)nullptr,
+                           (uint64_t)0, 0u, env_ids, visited, skip, pv, n_pad, hg.tiles_per_chunk, 0, 0, (float*)nullptr);
+    CIRS_CHECK_LAUNCH("actor_head_kernel (no noise)");
+    return CIRS_OK;
+}
+static inline int64_t topk_store_offset(const cirs_policy_cfg* cfg, int32_t n) { return (cirs_policy_workspace_bytes(cfg, n) + 255) & ~(int64_t)255; }
+}  // namespace cirs
+
+// deterministic_eval of a discrete actor (reference core/policy/ppo.py:149-151: act = logits_masked.argmax(-1) in eval mode): cirs_actor_sample without noise
+extern "C" int cirs_actor_greedy(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, const float* state, int64_t state_stride, int32_t n,
+                                 const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, int64_t* act_out, float* logp_out,
+                                 float* value_out, void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cirs;
+    if (int rc = validate_policy(cfg, w)) return rc;
+    if (n <= 0) return CIRS_OK;
+    CIRS_REQUIRE(state && act_out && workspace, "null state/act/workspace");
+    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
+    CIRS_REQUIRE(workspace_bytes >= cirs_policy_workspace_bytes(cfg, n), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = greedy_head(cfg, w, state, state_stride, n, env_ids, visited, skip, value_out, workspace, nullptr, s)) return rc;
+    const int n_pad = n_pad_of(n);
+    hipLaunchKernelGGL(actor_merge_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, n, n_pad, sampler_grid(cfg->n_items, n_pad).n_chunks,
+                       partial_view(workspace, n, cfg->n_items), skip, act_out, logp_out);
+    CIRS_CHECK_LAUNCH("actor_merge_kernel");
+    return CIRS_OK;
+}
+
+extern "C" int64_t cirs_actor_topk_workspace_bytes(const cirs_policy_cfg* cfg, int32_t n, int32_t k) {
+    using namespace cirs;
+    if (!cfg || n <= 0 || k < 1 || k > CIRS_TOPK_MAX) return 0;
+    // the sampler scratch of cirs_actor_greedy, then the masked logits [item tiles][n_pad][32]
+    return topk_store_offset(cfg, n) + (int64_t)cdiv(cfg->n_items, kTileN) * n_pad_of(n) * kTileN * 4;
+}
+
+// the k unmasked items of largest logit per row, the same pass over the catalogue as the arg-max of core/policy/ppo.py:149-151
+extern "C" int cirs_actor_topk(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, const float* state, int64_t state_stride, int32_t n, int32_t k,
+                               const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, int64_t* ids_out, float* logp_out,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cirs;
+    if (int rc = validate_policy(cfg, w)) return rc;
+    CIRS_REQUIRE(k >= 1 && k <= CIRS_TOPK_MAX, "k must lie in 1..32");
+    if (n <= 0) return CIRS_OK;
+    CIRS_REQUIRE(state && ids_out && workspace, "null state/ids/workspace");
+    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
+    CIRS_REQUIRE(workspace_bytes >= cirs_actor_topk_workspace_bytes(cfg, n, k), "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    float* zfull = (float*)((char*)workspace + topk_store_offset(cfg, n));
+    if (int rc = greedy_head(cfg, w, state, state_stride, n, env_ids, visited, skip, nullptr, workspace, zfull, s)) return rc;
+    const int n_pad = n_pad_of(n);
+    hipLaunchKernelGGL(actor_topk_kernel, dim3(cdiv(n, 4)), dim3(256), 0, s, n, n_pad, sampler_grid(cfg->n_items, n_pad).n_chunks,
+                       cdiv(cfg->n_items, kTileN), partial_view(workspace, n, cfg->n_items), (const float*)zfull, skip, k, ids_out, logp_out);
+    CIRS_CHECK_LAUNCH("actor_topk_kernel");
     return CIRS_OK;
 }
 

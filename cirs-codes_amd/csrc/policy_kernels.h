@@ -157,6 +157,13 @@ constexpr int kSamplerWgsPerCu = 3;
 struct HeadGrid { int tiles_per_chunk, n_chunks, grid_x, n_row_blocks; };
 constexpr int kLdsStride = 68;  // row stride (floats) of a staged 32 x 64 tile: ds_read_b128 of 16 lanes x 16 rows -> 64 banks
 
+// Noise mode (compile time): harness-supplied Gumbel noise, the counter-based generator, or none.  With kNoiseNone the running best is the fp32 logit itself
+// -- the arg-max of the masked logits (reference core/policy/ppo.py:149-151, deterministic_eval) -- and everything else is the sampler's: fp32 MFMA logits,
+// online log-sum-exp, visited mask, skip, chunk partials, actor_merge_kernel.  Ties go to the lowest item id in every mode: a lane's items ascend under a
+// strict >, and the half-wave exchange, cand_fold and best_fold all break equal scores by the lower id.
+// kStore (kNoiseNone only): the masked logits (-inf: visited or past the catalogue) are also kept, [item tile][n_pad][32] floats at zfull, for the top-k selection.
+enum HeadNoise { kNoiseHarness = 0, kNoiseCounter = 1, kNoiseNone = 2 };
+template <int kNoise, bool kStore = false>
 static __global__ __launch_bounds__(256, 2) void actor_head_kernel(cirs_policy_cfg cfg, const float* __restrict__ wa,
                                                             const float* __restrict__ ba,
                                                             const float* __restrict__ h2, int n,
@@ -165,7 +172,8 @@ static __global__ __launch_bounds__(256, 2) void actor_head_kernel(cirs_policy_c
                                                             const uint32_t* __restrict__ visited,
                                                             const uint8_t* __restrict__ skip, ActorPartialView pv,
                                                             int n_pad, int tiles_per_chunk, int item_base = 0,
-                                                            int n_items_total = 0) {
+                                                            int n_items_total = 0, float* __restrict__ zfull = nullptr) {
+    static_assert(!kStore || kNoise == kNoiseNone, "the logit store belongs to the no-noise head");
     // Column-sharded head (BASELINE configs[4]): wa / ba / cfg.n_items describe THIS rank's item shard, whose first item has the
     // global id item_base (a multiple of 32); noise counters, the visited bitmap, harness noise and the returned candidate ids use
     // GLOBAL item ids (n_items_total = size of the whole catalogue), so a shard computes exactly what the full kernel computes
@@ -277,7 +285,7 @@ static __global__ __launch_bounds__(256, 2) void actor_head_kernel(cirs_policy_c
                     for (int g = 0; g < 4; ++g) {
                         const int i0 = tile0 + 8 * g + 4 * hi;
                         float g4[4];
-                        if (!gumbel) {
+                        if constexpr (kNoise == kNoiseCounter) {
                             const u32x4 rr = philox4x32_10((uint32_t)(item_base + i0) >> 2, (uint32_t)e, rng_step, CIRS_RNG_STREAM_ACTOR,
                                                            (uint32_t)seed, (uint32_t)(seed >> 32));
                             g4[0] = gumbel_from_bits(rr.x); g4[1] = gumbel_from_bits(rr.y);
@@ -291,13 +299,20 @@ static __global__ __launch_bounds__(256, 2) void actor_head_kernel(cirs_policy_c
                             zt[4 * g + q] = valid ? z : -INFINITY;
                             tmax = fmaxf(tmax, zt[4 * g + q]);
                             if (valid) {
-                                const float gn = gumbel ? gumbel[(size_t)jr * I_tot + item_base + item] : g4[q];
-                                const float sc = z + gn;
+                                float sc = z;      // kNoiseNone: the logit itself
+                                if constexpr (kNoise == kNoiseHarness) sc = z + gumbel[(size_t)jr * I_tot + item_base + item];
+                                else if constexpr (kNoise == kNoiseCounter) sc = z + g4[q];
                                 if (sc > best_score) {  // items ascend within a lane: strict > keeps the lowest id on ties
                                     best_score = sc; best_idx = item_base + item; best_z = z;
                                 }
                             }
                         }
+                    }
+                    if constexpr (kStore) {      // this lane's 16 masked logits of the tile: four 16-byte stores into its row's 128 bytes
+                        float* zr = zfull + ((size_t)((item_base + tile0) >> 5) * n_pad + jr) * kTileN + 4 * hi;
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+                            *reinterpret_cast<float4*>(zr + 8 * g) = make_float4(zt[4 * g], zt[4 * g + 1], zt[4 * g + 2], zt[4 * g + 3]);
                     }
                     if (tmax > -INFINITY) {
                         const float mn = fmaxf(run_m, tmax);
@@ -1028,6 +1043,48 @@ __device__ __forceinline__ float cand_logp(const Cand& r) {
     const float eps = 1.1920928955078125e-7f;
     p = fminf(fmaxf(p, eps), 1.0f - eps);
     return __logf(p);
+}
+
+// ---- top-k list of one env row (one wavefront) ---------------------------------------------------------------------------------
+// zfull: the masked logits the no-noise head kept ([item tile][n_pad][32], -inf = masked); (m, s): the row's merged log-sum-exp (actor_merge_chunks: the very
+// Cand cirs_actor_greedy's merge forms, so k = 1 returns its id and logp bit for bit).  Items are ranked by (logit descending, id ascending) -- a strict total
+// order, so the list does not depend on the order of the comparisons.  Lane l owns the items l, l + 64, ...: it keeps its best item that ranks AFTER the last
+// one it has given away; every round the wavefront takes the best of the 64 lane candidates and only the winning lane looks through its items again.
+__device__ __forceinline__ float item_logp(float z, float m, float s) {
+    const float lse = m + __logf(s);
+    float p = __expf(z - lse);
+    const float eps = 1.1920928955078125e-7f;
+    p = fminf(fmaxf(p, eps), 1.0f - eps);  // torch probs_to_logits clamp
+    return __logf(p);
+}
+__device__ __forceinline__ void actor_topk_wave(int j, int lane, int n_pad, int n_tiles, const float* __restrict__ zfull, float m, float s, int k,
+                                                int64_t* __restrict__ ids_out, float* __restrict__ logp_out) {
+    const int n_slots = n_tiles * kTileN;
+    float last_v = INFINITY;     // this lane's last item given away: (value, id); nothing yet
+    int last_i = -1;
+    Best mine{-INFINITY, 0.f, 0x7FFFFFFF};
+    auto rescan = [&]() {
+        mine = Best{-INFINITY, 0.f, 0x7FFFFFFF};
+        for (int i = lane; i < n_slots; i += CIRS_WAVE) {
+            const float v = zfull[((size_t)(i >> 5) * n_pad + j) * kTileN + (i & 31)];
+            const bool after = v < last_v || (v == last_v && i > last_i);
+            if (v > -INFINITY && after) best_fold(mine, v, i, v);
+        }
+    };
+    rescan();
+    for (int r = 0; r < k; ++r) {
+        const Best w = best_wave_reduce(mine);     // identical in every lane
+        const bool none = w.bi == 0x7FFFFFFF;
+        if (lane == 0) {
+            ids_out[(size_t)j * k + r] = none ? -1 : (int64_t)w.bi;
+            if (logp_out) logp_out[(size_t)j * k + r] = none ? -INFINITY : item_logp(w.bz, m, s);
+        }
+        if (none) continue;        // wave-uniform: the rest of the list is the fill
+        if ((w.bi & (CIRS_WAVE - 1)) == lane) {
+            last_v = w.bs; last_i = w.bi;
+            rescan();
+        }
+    }
 }
 
 // Column-sharded head: this shard's chunk partials of env row j as ONE tuple (score, global id, logit of that candidate, running

@@ -53,7 +53,7 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
                         const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
                         int32_t t_begin, int32_t t_end, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
                         const cirs_online_reward* online, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream,
-                        const cirs_redraw* redraw = nullptr, const int32_t* init_users = nullptr);
+                        const cirs_redraw* redraw = nullptr, const int32_t* init_users = nullptr, bool greedy = false);
 
 // Collector.reset_env + collect(n_episode = n_env) from ONE call (core/collector.py:123-134,147-367): env reset, the tracker's first position (from the packed
 // weight image, the first step's trunk in its launch), the max_turn vector steps.  Every trajectory entry [t][env] is written (finished envs: act -1, done 1,
@@ -91,6 +91,34 @@ extern "C" int cirs_rollout_steps_noise(const cirs_env_cfg* env_cfg, const cirs_
                         force_length, nullptr, gumbel, workspace, workspace_bytes, stream);
 }
 
+// deterministic_eval (reference core/policy/ppo.py:149-151: act = logits_masked.argmax(-1) in eval mode): the fused two-launch sequence with the no-noise
+// head kernel in place of the sampler and the step kernel's tail merging its partials -- the form the harness-noise rollout runs.  visited, force_length,
+// env step, tracker decode and trunk are the sampled rollout's.  No noise is drawn: there is no seed / rng_base.
+extern "C" int cirs_rollout_steps_greedy(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                         const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w, cirs_tracker_state* trk_st,
+                                         const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                         int32_t t_begin, int32_t t_end, uint32_t* visited, int32_t force_length, void* workspace,
+                                         int64_t workspace_bytes, void* stream) {
+    CIRS_REQUIRE(env_tab != nullptr, "cirs_rollout_steps_greedy: null argument");
+    CIRS_REQUIRE(env_tab->pred_online == nullptr, "greedy rollout: the online-reward loop has no greedy mode (tables with pred_online are refused)");
+    return rollout_impl(env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w, traj, n_env, t_begin, t_end, 0, 0, visited, force_length,
+                        nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, nullptr, true);
+}
+
+// cirs_rollout_collect with the arg-max action of core/policy/ppo.py:149-151 (see cirs_rollout_steps_greedy)
+extern "C" int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                           const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w, cirs_tracker_state* trk_st,
+                                           const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                           const int32_t* users, uint32_t* visited, int32_t force_length, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+    CIRS_REQUIRE(env_cfg && env_tab && env_st && users && workspace && n_env > 0, "cirs_rollout_collect_greedy: null argument");
+    CIRS_REQUIRE(env_tab->pred_online == nullptr, "greedy rollout: the online-reward loop has no greedy mode (tables with pred_online are refused)");
+    CIRS_REQUIRE(workspace_bytes >= (int64_t)sizeof(int64_t) * n_env, "workspace too small");
+    CIRS_REQUIRE(env_st->user && env_st->turn && env_st->done && env_st->hist_action && env_st->cum_reward, "env state has null field");
+    return rollout_impl(env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w, traj, n_env, 0, env_cfg->max_turn, 0, 0, visited, force_length,
+                        nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, users, true);
+}
+
 extern "C" int cirs_rollout_steps(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
                                   const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w,
                                   cirs_tracker_state* trk_st, const cirs_policy_cfg* pol_cfg,
@@ -118,9 +146,11 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
                         const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
                         int32_t t_begin, int32_t t_end, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
                         const cirs_online_reward* online, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream,
-                        const cirs_redraw* redraw, const int32_t* init_users) {
+                        const cirs_redraw* redraw, const int32_t* init_users, bool greedy) {
     using namespace cirs;
     cirs_env_tables tab_local;
+    CIRS_REQUIRE(!greedy || (!online && !redraw && !gumbel), "greedy rollout: not available with online reward, exact redraw or harness noise");
+    const bool merge_tail = gumbel || greedy;     // the head kernel's partials are merged in the step kernel's tail (no pick)
     if (online) {
         CIRS_REQUIRE(env_tab && online->cfg && online->w && online->raw_uid && online->raw_pid && online->item_feats && online->item_dur &&
                      online->pred_minmax && online->uid_buf && online->pid_buf && online->feat_buf && online->dur_buf && online->pred_buf,
@@ -189,7 +219,7 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
     float* img = (float*)((char*)workspace + ((workspace_bytes - kTrkImgBytes) & ~(int64_t)255));
     // ... the fp16 planes of the actor head for the chunk-mass kernels, likewise once per call, and (cirs_rollout_collect) env.reset: one launch
     uint4* rplanes = ws_rplanes(workspace, workspace_bytes, pol_cfg->n_items);
-    if (int rc = pack_tracker_image(trk_cfg, trk_w, pol_w, S, img, s, pol_w->wa, pol_cfg->n_items, gumbel ? nullptr : rplanes, init_users ? env_cfg : nullptr, env_st,
+    if (int rc = pack_tracker_image(trk_cfg, trk_w, pol_w, S, img, s, pol_w->wa, pol_cfg->n_items, merge_tail ? nullptr : rplanes, init_users ? env_cfg : nullptr, env_st,
                                     init_users, n_env, (int64_t*)workspace))
         return rc;
     // sampler scratch at the head of the workspace (the kernels below take the env id of their row 0: always 0 here)
@@ -201,12 +231,12 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
     const int cpw = mass_chunks_per_wg(n_mass_chunks, hg.n_row_blocks);
     // logit store (counter-based sampler, small env counts): behind the sampler scratch
     float* zstore = nullptr;
-    if (!gumbel && ws_zstore_floats(n_env, pol_cfg->n_items) > 0) {
+    if (!merge_tail && ws_zstore_floats(n_env, pol_cfg->n_items) > 0) {
         const char* ev = getenv("CIRS_ROLLOUT_ZSTORE");     // read per call (like CIRS_PPO_MERGE_KERNEL): a test may flip it between collects
         if (ev ? atoi(ev) != 0 : true) zstore = (float*)((char*)workspace + ((sampler_ws_bytes(pol_cfg, n_env) + 255) & ~(int64_t)255));
     }
     const char* ms_ev = getenv("CIRS_ROLLOUT_MASS_SMALL");   // per call as well
-    const bool mass_small = (ms_ev ? atoi(ms_ev) != 0 : true) && !gumbel && n_pad <= 128;
+    const bool mass_small = (ms_ev ? atoi(ms_ev) != 0 : true) && !merge_tail && n_pad <= 128;
     const uint8_t* done_all = (const uint8_t*)env_st->done;
     // Exact-redraw dropout (the reference's procedure, core/state_tracker.py:170-186,243-246): the state of vector step t is NOT the cached decode's -- it is
     // ONE batched causal pass over positions 0 .. t of every env with the masks of build_state call t (cirs_tracker_prefix_states, key = the collect's key with
@@ -258,10 +288,14 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
         double* rew_t = traj->rew + (size_t)t * B;
         uint8_t* done_t = traj->done + (size_t)t * B;
         if (gum_t) {   // harness-supplied noise: plain Gumbel-max over the catalogue (reference-recorded fixtures)
-            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_head_kernel, dim3(hg.grid_x, hg.n_row_blocks), dim3(256), 0, s, *pol_cfg,
+            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_head_kernel<kNoiseHarness>, dim3(hg.grid_x, hg.n_row_blocks), dim3(256), 0, s, *pol_cfg,
                                                       pol_w->wa, pol_w->ba, (const float*)h2, n_env, gum_t, seed,
                                                       rng_base + (uint32_t)t, (const int32_t*)nullptr, (const uint32_t*)visited,
                                                       done_all, pv, n_pad, hg.tiles_per_chunk));
+        } else if (greedy) {   // no noise: the arg-max of the masked logits (core/policy/ppo.py:149-151)
+            CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_head_kernel<kNoiseNone>, dim3(hg.grid_x, hg.n_row_blocks), dim3(256), 0, s, *pol_cfg,
+                                                      pol_w->wa, pol_w->ba, (const float*)h2, n_env, (const float*)nullptr, (uint64_t)0, 0u,
+                                                      (const int32_t*)nullptr, (const uint32_t*)visited, done_all, pv, n_pad, hg.tiles_per_chunk));
         } else if (mass_small) {   // few envs: one workgroup per chunk, one wave per (row tile, item tile)
             CIRS_PROF_LAUNCH(3, s, hipLaunchKernelGGL(actor_mass_small_kernel, dim3(n_mass_chunks), dim3(n_pad / kTileM * 256), 0, s, *pol_cfg, (const uint4*)rplanes,
                                                       pol_w->ba, (const float*)h2, n_env, (const uint32_t*)visited, done_all, pv.m, n_pad, 0, zstore));
@@ -282,7 +316,7 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
         tl.on = 1; tl.cfg = *env_cfg; tl.tab = *env_tab; tl.st = *env_st; tl.n_pad = n_pad; tl.n_chunks = hg.n_chunks; tl.pv = pv;
         tl.env_base = 0;
         tl.visited = visited; tl.force_length = force_length;
-        if (!gum_t) {
+        if (!merge_tail) {
             tl.pick_on = 1;
             tl.pick = PickArgs{pv.m, n_pad, n_mass_chunks, pol_w->wa, pol_w->ba, h2, visited, pol_cfg->n_items, 0, 0, seed, rng_base + (uint32_t)t, zstore};
         }

@@ -260,6 +260,8 @@ __device__ __forceinline__ float encoder_row(const cirs_vtb_model_cfg& m, const 
 // ---- decoder on the encoder's output row h of position t, then the actor ---------------------------------------------------
 // state s_t -> traj.state; unless the env has finished: Net trunk, mu / sigma, act = mu + sigma * z, the mapped action at a compacted
 // position of the next active list
+// GREEDY (deterministic_eval in eval mode, reference core/policy/ppo.py:152-153): act = mu, no z is drawn
+template <bool GREEDY>
 __device__ __forceinline__ void decode_and_act(const cirs_vtb_rollout_cfg& cfg, const cirs_vtb_policy_weights& w, const cirs_vtb_traj& tr,
                                                const WaveLds& sl, float h, int t, int e, int lane, bool finished, uint64_t seed,
                                                uint32_t collect_id) {
@@ -294,8 +296,11 @@ __device__ __forceinline__ void decode_and_act(const cirs_vtb_rollout_cfg& cfg, 
         float sigma;
         if (cfg.model.conditioned_sigma) sigma = expf(fminf(fmaxf(mv(w.sigma_w, w.sigma_b, in, width, kA, lane), -20.f), 2.f));
         else sigma = expf(w.sigma_param[lane]);
-        const float z = gauss_z(seed, collect_id, (uint32_t)e, (uint32_t)t, (uint32_t)lane);
-        const float act = mu + sigma * z;
+        float act = mu;
+        if constexpr (!GREEDY) {
+            const float z = gauss_z(seed, collect_id, (uint32_t)e, (uint32_t)t, (uint32_t)lane);
+            act = mu + sigma * z;
+        }
         float u = act;
         if (cfg.bound_method == 1) u = fminf(fmaxf(act, -1.0f), 1.0f);
         else if (cfg.bound_method == 2) u = tanhf(act);
@@ -318,7 +323,7 @@ __device__ __forceinline__ void decode_and_act(const cirs_vtb_rollout_cfg& cfg, 
 }
 
 // ---- position-keyed mode: one wave per env, K/V-cached decode of position t ------------------------------------------------
-template <bool DROP>
+template <bool DROP, bool GREEDY>
 __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w, cirs_vtb_traj tr,
                                                                        int t, int steps, uint64_t seed, uint32_t collect_id) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -339,7 +344,7 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
         float* vc = tr.vcache + (((size_t)l * B + e) * L) * D;
         h = encoder_row<DROP, true>(cfg.model, w.layer[l], s, dk, l, t, h, kc, vc, lane);
     }
-    decode_and_act(cfg, w, tr, s, h, t, e, lane, finished, seed, collect_id);
+    decode_and_act<GREEDY>(cfg, w, tr, s, h, t, e, lane, finished, seed, collect_id);
 }
 
 // ---- exact-redraw mode (dropout_redraw): one workgroup per env, the whole prefix 0..t again with the masks of call t ----------
@@ -348,6 +353,7 @@ __global__ __launch_bounds__(64 * kWaves) void vtb_policy_step_kernel(cirs_vtb_r
 // rows -- all of them below the top layer, whose outputs are the next layer's input, the last row only in the top layer.  The slots
 // x_0..x_t are kept (they carry no mask).  ws: slots [max_len][n_env][D] | layer outputs [nlayers - 1][n_env][max_len][D].
 constexpr int kRedrawWaves = 8;
+template <bool GREEDY>
 __global__ __launch_bounds__(64 * kRedrawWaves) void vtb_policy_step_redraw_kernel(cirs_vtb_rollout_cfg cfg, cirs_vtb_policy_weights w,
                                                                                    cirs_vtb_traj tr, float* ws, int t, int steps, uint64_t seed,
                                                                                    uint32_t collect_id) {
@@ -401,7 +407,7 @@ __global__ __launch_bounds__(64 * kRedrawWaves) void vtb_policy_step_redraw_kern
         }
         __syncthreads();
     }
-    if (wv == 0) decode_and_act(cfg, w, tr, s, h_top, t, e, lane, finished, seed, collect_id);
+    if (wv == 0) decode_and_act<GREEDY>(cfg, w, tr, s, h_top, t, e, lane, finished, seed, collect_id);
 }
 
 __global__ __launch_bounds__(256) void vtb_gauss_kernel(uint64_t seed, uint32_t collect_id, const int32_t* __restrict__ ids,
@@ -483,7 +489,7 @@ int validate_redraw(const cirs_vtb_rollout_cfg* cfg) {
 
 // redraw_ws == nullptr: the position-keyed mode
 int collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg, const cirs_vtb_weights* vtb_w,
-            cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws, uint64_t seed, uint32_t collect_id, void* stream) {
+            cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws, uint64_t seed, uint32_t collect_id, void* stream, bool greedy = false) {
     const hipStream_t s = (hipStream_t)stream;
     const cirs_vtb_rollout_cfg c = *cfg;
     const cirs_vtb_traj tr = *traj;
@@ -506,12 +512,14 @@ int collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, 
     const bool drop = c.model.dropout_p > 0.f;
     for (int t = 0; t <= steps; ++t) {
         if (redraw_ws) {
-            hipLaunchKernelGGL(vtb_policy_step_redraw_kernel, dim3(B), dim3(64 * kRedrawWaves), kRedrawWaves * wave_lds_bytes, s, c, *pw, tr,
-                               redraw_ws, t, steps, seed, collect_id);
+            const auto kern = greedy ? vtb_policy_step_redraw_kernel<true> : vtb_policy_step_redraw_kernel<false>;
+            hipLaunchKernelGGL(kern, dim3(B), dim3(64 * kRedrawWaves), kRedrawWaves * wave_lds_bytes, s, c, *pw, tr, redraw_ws, t, steps, seed,
+                               collect_id);
             CIRS_CHECK_LAUNCH("vtb_policy_step_redraw_kernel");
         } else {
-            if (drop) hipLaunchKernelGGL(vtb_policy_step_kernel<true>, grid, block, kWaves * wave_lds_bytes, s, c, *pw, tr, t, steps, seed, collect_id);
-            else hipLaunchKernelGGL(vtb_policy_step_kernel<false>, grid, block, kWaves * wave_lds_bytes, s, c, *pw, tr, t, steps, seed, collect_id);
+            const auto kern = drop ? (greedy ? vtb_policy_step_kernel<true, true> : vtb_policy_step_kernel<true, false>)
+                                   : (greedy ? vtb_policy_step_kernel<false, true> : vtb_policy_step_kernel<false, false>);
+            hipLaunchKernelGGL(kern, grid, block, kWaves * wave_lds_bytes, s, c, *pw, tr, t, steps, seed, collect_id);
             CIRS_CHECK_LAUNCH("vtb_policy_step_kernel");
         }
         if (t == steps) break;
@@ -547,6 +555,17 @@ extern "C" int cirs_vtb_rollout_collect_redraw(const cirs_vtb_rollout_cfg* cfg, 
     CIRS_REQUIRE(redraw_ws != nullptr, "dropout_redraw: null workspace (max_len * n_env * dim_model * nlayers floats)");
     // without dropout every call's prefix pass equals the cached decode: run that
     return collect(cfg, pw, vtb_cfg, vtb_w, vtb_st, traj, cfg->model.dropout_p > 0.f ? redraw_ws : nullptr, seed, collect_id, stream);
+}
+
+// deterministic_eval in eval mode (reference core/policy/ppo.py:152-153: act = logits[0], the mean): either collect without the Gaussian draw
+extern "C" int cirs_vtb_rollout_collect_greedy(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                               const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws,
+                                               void* stream) {
+    using namespace cirs;
+    if (redraw_ws) { if (int rc = validate_redraw(cfg)) return rc; }
+    if (int rc = validate_rollout(cfg, pw, vtb_cfg, traj)) return rc;
+    CIRS_REQUIRE(vtb_w && vtb_st, "null env weights / state");
+    return collect(cfg, pw, vtb_cfg, vtb_w, vtb_st, traj, (redraw_ws && cfg->model.dropout_p > 0.f) ? redraw_ws : nullptr, 0, 0, stream, true);
 }
 
 extern "C" int cirs_vtb_rollout_noise(uint64_t seed, uint32_t collect_id, const int32_t* env_ids, const int32_t* ts, int32_t n, int32_t dims,

@@ -66,6 +66,8 @@ def get_args(argv=None):
     p.add_argument("--step-per-epoch", type=int, default=2000)
     p.add_argument("--top_rate", type=float, default=0.8)
     p.add_argument("--dropout", type=float, default=0.1, help="state-tracker dropout (live during rollout and update, like the reference)")
+    p.add_argument("--deterministic-eval", action="store_true",
+                   help="test collectors take the policy's arg-max item instead of a sample (PPOPolicy(deterministic_eval=True))")
     p.add_argument("--n-users", type=int, default=1411)
     p.add_argument("--n-items", type=int, default=3327)
     return p.parse_args(argv)
@@ -115,7 +117,8 @@ def build(args, table_seed=0):
     policy = PPOPolicy(actor, critic, [optim_RL, optim_state], torch.distributions.Categorical, discount_factor=args.gamma,
                        max_grad_norm=args.max_grad_norm, eps_clip=args.eps_clip, vf_coef=args.vf_coef, ent_coef=args.ent_coef,
                        reward_normalization=1, advantage_normalization=1, recompute_advantage=0, value_clip=1,
-                       gae_lambda=args.gae_lambda, action_space=simulatedEnv.action_space, action_bound_method="", action_scaling=False)
+                       gae_lambda=args.gae_lambda, action_space=simulatedEnv.action_space, action_bound_method="", action_scaling=False,
+                       deterministic_eval=args.deterministic_eval)
     # %% 5. collectors (reference :288-292)
     train_collector = Collector(policy, train_envs, VectorReplayBuffer(args.buffer_size, len(train_envs)),
                                 preprocess_fn=state_tracker.build_state)

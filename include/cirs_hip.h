@@ -202,6 +202,25 @@ int cirs_actor_sample(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, 
                       const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, int64_t* act_out,
                       float* logp_out, float* value_out, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* deterministic_eval of a discrete actor (reference core/policy/ppo.py:149-151: in eval mode act = logits_masked.argmax(-1)): cirs_actor_sample
+ * without noise -- the same trunk, fp32 MFMA logits, visited mask, skip and merge; act = the unmasked item of largest logit (ties -> lowest id),
+ * logp = its log-probability under the masked soft-max with cirs_actor_sample's clamp, value as always; skipped rows get act = -1.
+ * workspace: cirs_policy_workspace_bytes(cfg, n). */
+int cirs_actor_greedy(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, const float* state, int64_t state_stride, int32_t n,
+                      const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, int64_t* act_out, float* logp_out,
+                      float* value_out, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The policy's top-k list per row: the k (1..CIRS_TOPK_MAX) unmasked items of largest logit in descending order, ties -> the lower id first
+ * (the arg-max rule of core/policy/ppo.py:149-151 continued down the ranking; the counterpart of UserModel.recommend_k_item for the RL policy).
+ *   ids_out [n, k] i64, logp_out [n, k] f32 (nullable): logp as in cirs_actor_greedy; fewer than k unmasked items left: the tail is -1 / -inf;
+ *   a skipped row is all -1 / -inf.  k = 1 returns cirs_actor_greedy's act and logp bit for bit (the same head kernel and merge).
+ *   workspace: cirs_actor_topk_workspace_bytes(cfg, n, k) (0 for a k outside 1..CIRS_TOPK_MAX): the greedy scratch + the masked logits. */
+#define CIRS_TOPK_MAX 32
+int64_t cirs_actor_topk_workspace_bytes(const cirs_policy_cfg* cfg, int32_t n, int32_t k);
+int cirs_actor_topk(const cirs_policy_cfg* cfg, const cirs_policy_weights* w, const float* state, int64_t state_stride, int32_t n, int32_t k,
+                    const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip, int64_t* ids_out, float* logp_out, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* ---- column-sharded actor head + row-sharded tables (BASELINE configs[4]: catalogue / embedding tables split over the ranks) ----
  * The reference has no counterpart (deepctr_torch/inputs.py:31-33 only prints a notice for use_hash); the spec is SURVEY 8(e):
  * "actor head column-sharded over items with a cross-rank (max, sum-exp, sampled-candidate) reduction", "tables row-sharded by
@@ -297,6 +316,20 @@ int cirs_rollout_steps_noise(const cirs_env_cfg* env_cfg, const cirs_env_tables*
                              const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
                              int32_t n_env, int32_t t_begin, int32_t t_end, const float* gumbel, uint32_t* visited,
                              int32_t force_length, void* workspace, int64_t workspace_bytes, void* stream);
+/* cirs_rollout_steps / cirs_rollout_collect with the arg-max action of a policy built with deterministic_eval and put in eval()
+ * (reference core/policy/ppo.py:149-151: act = logits_masked.argmax(-1)): the no-noise head kernel in place of the sampler, everything else
+ * -- visited, force_length, env step, tracker decode (its dropout included), trunk -- as in the sampled rollout.  No noise is drawn, so there is
+ * no seed / rng_base.  Precomputed reward tables only: the online-reward loop, the exact-redraw rollout and the column-sharded head have no greedy mode. */
+int cirs_rollout_steps_greedy(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                              const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w, cirs_tracker_state* trk_st,
+                              const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                              int32_t n_env, int32_t t_begin, int32_t t_end, uint32_t* visited, int32_t force_length,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w, cirs_tracker_state* trk_st,
+                                const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                                int32_t n_env, const int32_t* users, uint32_t* visited, int32_t force_length, void* workspace,
+                                int64_t workspace_bytes, void* stream);
 /* same, with the predicted reward scored online (env_tab->normed_mat may be NULL) */
 int cirs_rollout_steps_online(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
                               const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w,
@@ -1064,6 +1097,13 @@ typedef struct cirs_vtb_traj { /* device buffers owned by the caller; t = vector
 int cirs_vtb_rollout_collect(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
                              const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, uint64_t seed,
                              uint32_t collect_id, void* stream);
+/* Either collect with the MEAN action of a policy built with deterministic_eval and put in eval() (reference core/policy/ppo.py:152-153:
+ * act = logits[0] for a continuous actor): act = mu, no Gaussian draw; mapping, clipping, compaction and the trajectory as in the sampled collect.
+ * redraw_ws == NULL: the position-keyed collect (cirs_vtb_rollout_collect); non-NULL: the exact-redraw collect (cirs_vtb_rollout_collect_redraw).
+ * The tracker's dropout is untouched (it stays in train() during tests): an evaluation is deterministic given model.dropout_seed. */
+int cirs_vtb_rollout_collect_greedy(const cirs_vtb_rollout_cfg* cfg, const cirs_vtb_policy_weights* pw, const cirs_vtb_cfg* vtb_cfg,
+                                    const cirs_vtb_weights* vtb_w, cirs_vtb_state* vtb_st, cirs_vtb_traj* traj, float* redraw_ws, void* stream);
+
 /* cirs_vtb_rollout_collect with the reference's own dropout procedure (core/state_tracker.py:170-250: the tracker stays in train(), every
  * build_state call runs the whole prefix through the encoder again and nn.Dropout draws fresh masks over it).  Call c of env e (c = 0 on
  * the reset observation, c = len_e after the last step) is ONE causal pass over the input slots 0..c with masks of its own at all five
