@@ -217,6 +217,16 @@ class MlpTrainCfg(C.Structure):     # cirs_mlp_train_cfg
     _fields_ = [("shape", VtbMmoeShape)] + [(k, C.c_float) for k in ("l2_linear", "l2_all", "lr", "beta1", "beta2", "eps")]
 
 
+TOPK_MAX, RANK_NCOL, RANK_NSUM = 32, 11, 8      # CIRS_TOPK_MAX, CIRS_RANK_NCOL, CIRS_RANK_NSUM
+RANK_COLUMNS = ("n_list", "n_rel", "hits", "precision", "recall", "hit", "mrr", "dcg", "idcg", "ndcg", "ild")
+RANK_ERR_ID, RANK_ERR_USER = 1, 2
+
+
+class RankCfg(C.Structure):         # cirs_rank_cfg
+    _fields_ = [("n_users", C.c_int32), ("n_items", C.c_int32), ("k", C.c_int32), ("reserved", C.c_int32), ("rel_threshold", C.c_double),
+                ("discount", C.c_double * TOPK_MAX)]
+
+
 # name -> (restype, argtypes).  Must list every symbol include/cirs_hip.h declares (tests check this).
 _P = C.c_void_p
 SIGNATURES = {
@@ -386,6 +396,9 @@ SIGNATURES = {
     "cirs_eval_coverage": (C.c_int, [_P, C.c_int64, C.c_int32, _P, _P, _P, _P]),
     "cirs_adam_step": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_float,
                                  C.c_float, _P, C.c_int32, _P]),
+    "cirs_rows_topk": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "cirs_rank_metrics_workspace_bytes": (C.c_int64, [C.c_int32]),
+    "cirs_rank_metrics": (C.c_int, [C.POINTER(RankCfg), _P, C.c_int64, _P, C.c_int32, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

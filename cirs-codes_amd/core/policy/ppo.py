@@ -173,6 +173,24 @@ class PPOPolicy(nn.Module):
         ids, logp = self._dev_policy.topk(obs, k, env_ids=env_ids, visited=visited)
         return Batch(act=ids, policy=Batch(logp=logp))
 
+    def rank_metrics(self, batch, users, env, k, *, rel_threshold=None, buffer=None, remove_recommended_ids=False):
+        """Ranking and diversity metrics of the policy's top-k lists (self.topk) for the rows of `batch`, row j scored as env user users[j] against
+        the ground truth of the KuaishouEnv `env` (env.mat, its item categories): the dict of cirs_hip.rankmetrics.RankMetrics.evaluate
+        (Precision / Recall / HR / MRR / NDCG / ILD / CV @k, n, per_row).  rel_threshold is required: an item is relevant iff mat >= rel_threshold.
+        With remove_recommended_ids the same bitmap masks the list, n_rel and the ideal list.  No reference counterpart."""
+        from cirs_hip.rankmetrics import RankMetrics, check_k
+        k = check_k(k)
+        key = (env.batch_key(), None if rel_threshold is None else float(rel_threshold))
+        cached = self.__dict__.get("_rank_metrics")
+        if cached is None or cached[0] != key:
+            cached = (key, RankMetrics.for_env(env, rel_threshold=rel_threshold, device=self.flat.device))
+            self.__dict__["_rank_metrics"] = cached
+        if cached[1].n_items != self.n_items:
+            raise ValueError(f"the env has {cached[1].n_items} items, the policy's catalogue {self.n_items}")
+        obs, env_ids, visited = self._rows(batch, buffer, remove_recommended_ids)
+        ids, _ = self._dev_policy.topk(obs, k, env_ids=env_ids, visited=visited)
+        return cached[1].evaluate(ids, users, visited=visited, env_ids=env_ids)
+
     def _rows(self, batch, buffer, remove_recommended_ids):
         """(obs on the device, env_ids, visited bitmap) of a per-step call."""
         obs = batch.obs

@@ -158,6 +158,34 @@ class UserModel(nn.Module):
         self._publish()
         return history
 
+    # ---- offline ranking evaluation against the fully observed env matrix (no reference counterpart) ----------------------
+    def evaluate_ranking(self, env, dataset_val, k, *, rel_threshold=None, users=None, batch_users=1024):
+        """Top-k lists of the model for env users (`users`: env numbering, default all of them) scored against env.mat: per block of
+        `batch_users` users one catalogue sweep over dataset_val.df_photo_env (device_model().sweep: Pairwise, the IPS / PD builds, DICE) and one
+        row-wise top-k (cirs_rows_topk), then one cirs_rank_metrics over all lists.  Returns the dict of RankMetrics.evaluate; its "ids" entry holds
+        the lists [n, k] (env-encoded: positions in df_photo_env, as recommend_k_item returns them).  rel_threshold is required."""
+        from cirs_hip.rankmetrics import RankMetrics, check_k
+        k = check_k(k)
+        df_item_val = dataset_val.df_photo_env
+        item_index = df_item_val.index.to_numpy()
+        assert np.array_equal(item_index, np.asarray(env.lbe_photo.classes_)), "df_photo_env must be in env item order (lbe_photo.classes_)"
+        dm = self.device_model()
+        rm = RankMetrics.for_env(env, rel_threshold=rel_threshold, device=dm.device)
+        users = np.arange(env.mat.shape[0]) if users is None else np.asarray(users, dtype=np.int64).reshape(-1)
+        if len(users) and (users.min() < 0 or users.max() >= env.mat.shape[0]):
+            raise ValueError(f"users must be env user ids in [0, {env.mat.shape[0]})")
+        raw_users = np.asarray(env.lbe_user.classes_)[users]
+        feats = df_item_val[["feat0", "feat1", "feat2", "feat3"]].to_numpy()
+        dur = df_item_val["photo_duration"].to_numpy()
+        step = max(1, int(batch_users))
+        ids = torch.empty((len(users), k), dtype=torch.int64, device=dm.device)
+        for u0 in range(0, len(users), step):
+            scores, _ = dm.sweep(raw_users[u0:u0 + step], item_index, feats, dur)       # [block, I] fp32 on the device
+            ids[u0:u0 + step] = rm.topk_rows(scores, k)[0]
+        out = rm.evaluate(ids, users)
+        out["ids"] = ids
+        return out
+
     # ---- static-baseline recommendation (reference core/user_model.py:250-348) ------------------------------------------
     def compile_UCB(self, n_arm):
         self.n_rec = n_arm

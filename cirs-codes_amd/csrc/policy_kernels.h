@@ -1049,7 +1049,7 @@ __device__ __forceinline__ float cand_logp(const Cand& r) {
 // zfull: the masked logits the no-noise head kept ([item tile][n_pad][32], -inf = masked); (m, s): the row's merged log-sum-exp (actor_merge_chunks: the very
 // Cand cirs_actor_greedy's merge forms, so k = 1 returns its id and logp bit for bit).  Items are ranked by (logit descending, id ascending) -- a strict total
 // order, so the list does not depend on the order of the comparisons.  Lane l owns the items l, l + 64, ...: it keeps its best item that ranks AFTER the last
-// one it has given away; every round the wavefront takes the best of the 64 lane candidates and only the winning lane looks through its items again.
+// one it has given away; every round the wavefront takes the best of the 64 lane candidates and only the winning lane's items are looked through again.
 __device__ __forceinline__ float item_logp(float z, float m, float s) {
     const float lse = m + __logf(s);
     float p = __expf(z - lse);
@@ -1057,34 +1057,61 @@ __device__ __forceinline__ float item_logp(float z, float m, float s) {
     p = fminf(fmaxf(p, eps), 1.0f - eps);  // torch probs_to_logits clamp
     return __logf(p);
 }
+// The selection loop itself, over any layout and value type: value_at(i) is the value of slot i < n_slots (float or double; -inf = not a candidate,
+// NaN never wins a comparison), emit(r, value, id) receives rank r = 0 .. k-1 in every lane (id 0x7FFFFFFF: nothing left, the fill).  The first scan reads
+// slots lane, lane + 64, ...: consecutive lanes read consecutive slots.  emit(0, ..) runs after the first scan and before any later one.
+template <class T>
+struct Pick { T v; int i; };
+template <class T>
+__device__ __forceinline__ void pick_fold(Pick<T>& a, T ov, int oi) {
+    if (ov > a.v || (ov == a.v && oi < a.i)) { a.v = ov; a.i = oi; }
+}
+__device__ __forceinline__ Pick<float> pick_wave_reduce(Pick<float> a) {
+    const Best w = best_wave_reduce(Best{a.v, a.v, a.i});
+    return Pick<float>{w.bs, w.bi};
+}
+__device__ __forceinline__ Pick<double> pick_wave_reduce(Pick<double> a) {     // a strict total order: the pairing order does not matter
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) pick_fold(a, __shfl_xor(a.v, off, CIRS_WAVE), __shfl_xor(a.i, off, CIRS_WAVE));
+    return a;   // identical in every lane
+}
+template <class T, class ValueAt, class Emit>
+__device__ __forceinline__ void topk_select_wave(int lane, int n_slots, int k, ValueAt value_at, Emit emit) {
+    // mine: this lane's best item that ranks after everything it has given away (nothing yet: its best item)
+    Pick<T> mine{(T)-INFINITY, 0x7FFFFFFF};
+#pragma unroll 4
+    for (int i = lane; i < n_slots; i += CIRS_WAVE) {
+        const T v = value_at(i);
+        if (v > (T)-INFINITY) pick_fold(mine, v, i);
+    }
+    for (int r = 0; r < k; ++r) {
+        const Pick<T> w = pick_wave_reduce(mine);     // identical in every lane
+        emit(r, w.v, w.i);
+        if (w.i == 0x7FFFFFFF) continue;   // wave-uniform: the rest of the list is the fill
+        if (r + 1 == k) break;
+        // the winning lane's next candidate: its items that rank after the winner (everything it gave away earlier ranks before the winner).  The whole
+        // wavefront looks through that lane's n_slots / 64 items, 64 at a time, instead of the one lane walking them alone.
+        const int wl = w.i & (CIRS_WAVE - 1);
+        Pick<T> next{(T)-INFINITY, 0x7FFFFFFF};
+        for (int i = wl + CIRS_WAVE * lane; i < n_slots; i += CIRS_WAVE * CIRS_WAVE) {
+            const T v = value_at(i);
+            const bool after = v < w.v || (v == w.v && i > w.i);
+            if (v > (T)-INFINITY && after) pick_fold(next, v, i);
+        }
+        next = pick_wave_reduce(next);
+        if (lane == wl) mine = next;
+    }
+}
 __device__ __forceinline__ void actor_topk_wave(int j, int lane, int n_pad, int n_tiles, const float* __restrict__ zfull, float m, float s, int k,
                                                 int64_t* __restrict__ ids_out, float* __restrict__ logp_out) {
-    const int n_slots = n_tiles * kTileN;
-    float last_v = INFINITY;     // this lane's last item given away: (value, id); nothing yet
-    int last_i = -1;
-    Best mine{-INFINITY, 0.f, 0x7FFFFFFF};
-    auto rescan = [&]() {
-        mine = Best{-INFINITY, 0.f, 0x7FFFFFFF};
-        for (int i = lane; i < n_slots; i += CIRS_WAVE) {
-            const float v = zfull[((size_t)(i >> 5) * n_pad + j) * kTileN + (i & 31)];
-            const bool after = v < last_v || (v == last_v && i > last_i);
-            if (v > -INFINITY && after) best_fold(mine, v, i, v);
-        }
-    };
-    rescan();
-    for (int r = 0; r < k; ++r) {
-        const Best w = best_wave_reduce(mine);     // identical in every lane
-        const bool none = w.bi == 0x7FFFFFFF;
-        if (lane == 0) {
-            ids_out[(size_t)j * k + r] = none ? -1 : (int64_t)w.bi;
-            if (logp_out) logp_out[(size_t)j * k + r] = none ? -INFINITY : item_logp(w.bz, m, s);
-        }
-        if (none) continue;        // wave-uniform: the rest of the list is the fill
-        if ((w.bi & (CIRS_WAVE - 1)) == lane) {
-            last_v = w.bs; last_i = w.bi;
-            rescan();
-        }
-    }
+    topk_select_wave<float>(
+        lane, n_tiles * kTileN, k, [&](int i) { return zfull[((size_t)(i >> 5) * n_pad + j) * kTileN + (i & 31)]; },
+        [&](int r, float v, int id) {
+            if (lane != 0) return;
+            const bool none = id == 0x7FFFFFFF;
+            ids_out[(size_t)j * k + r] = none ? -1 : (int64_t)id;
+            if (logp_out) logp_out[(size_t)j * k + r] = none ? -INFINITY : item_logp(v, m, s);
+        });
 }
 
 // Column-sharded head: this shard's chunk partials of env row j as ONE tuple (score, global id, logit of that candidate, running

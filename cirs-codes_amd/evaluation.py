@@ -4,6 +4,7 @@
   Callback_Coverage_Count  evaluation.py:286-371 (CV, CV_turn and ifeat_* for the FB / NX_0 / NX_k test collectors)
   test_kuaishou            evaluation.py:179-234  (the per-epoch evaluation loop of the LinUCB baseline, core/policy/linucb.py)
   test_taobao              evaluation.py:238-282  (the VirtualTaobao static baselines: MLP-taobao.py, MLP-epsilonGreedy-taobao.py)
+  test_ranking_kuaishou    no reference counterpart (offline Precision / Recall / HR / MRR / NDCG / ILD / CV @k of a static model's top-k lists)
 
 The reference walks the replay buffers on the host (buffer.prev / buffer.next); here each collector's buffer carries the
 device trajectory of its fused rollout and the counts come from cirs_eval_coverage (integer kernel, bit-exact)."""
@@ -198,6 +199,17 @@ def test_kuaishou(model, env, dataset_val, is_softmax=True, epsilon=0, is_ucb=Fa
 
 
 test_kuaishou.__test__ = False  # not a pytest test
+
+
+def test_ranking_kuaishou(model, env, dataset_val, k=10, *, rel_threshold=None, users=None):
+    """Offline ranking evaluation of a static user model (UserModel.evaluate_ranking: Pairwise, IPS / PD, DICE) against the fully observed
+    KuaishouEnv matrix: {"Precision@k", "Recall@k", "HR@k", "MRR@k", "NDCG@k", "ILD@k", "CV@k", "n", "per_row", "ids"}.  rel_threshold is
+    required.  Like the other evaluation functions it can be handed to compile_RL_test through functools.partial (env, dataset_val, k and
+    rel_threshold bound).  No reference counterpart."""
+    return model.evaluate_ranking(env, dataset_val, k, rel_threshold=rel_threshold, users=users)
+
+
+test_ranking_kuaishou.__test__ = False  # not a pytest test
 
 
 def test_taobao(model, env, epsilon=0, *, device=None, num_trajectory=100, seed=0):

@@ -1279,6 +1279,49 @@ int cirs_mlp_train_epoch(const cirs_mlp_train_cfg* cfg, float* params, float* gr
                          int64_t n_order, int32_t batch_size, float* losses_out, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Ranking and list-diversity metrics of top-k lists (csrc/rankmetrics.hip).  No reference counterpart: the reference has the
+ * interactive metrics only (evaluation.py); the ground truth here is the fully observed user x item matrix of KuaishouEnv.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* The k (1..CIRS_TOPK_MAX) best entries of every row of a row-major fp32 score table scores [n, ld], ld >= n_items: value
+ * descending, ties -> the lower id first (the strict total order of cirs_actor_topk, the same selection loop).  Entries that are
+ * -inf, NaN or masked are never listed.  visited (nullable): uint32 bitmap, bit i of row env_ids[j] (NULL = j) masks item i of
+ * row j, (n_items + 31) / 32 words per row, as in cirs_actor_topk (env_ids are trusted as there); skip[j] != 0 (nullable): the
+ * row is all fill.  ids_out [n, k] i64, vals_out [n, k] f32 (nullable): the table's own bits; fills are -1 / -inf. */
+int cirs_rows_topk(const float* scores, int32_t n, int32_t n_items, int64_t ld, int32_t k, const int32_t* env_ids,
+                   const uint32_t* visited, const uint8_t* skip, int64_t* ids_out, float* vals_out, void* stream);
+
+#define CIRS_RANK_NCOL 11 /* n_list, n_rel, hits, precision, recall, hit, mrr, dcg, idcg, ndcg, ild */
+#define CIRS_RANK_NSUM 8  /* evaluated rows, error word, mean precision, recall, hit, mrr, ndcg, ild */
+#define CIRS_RANK_ERR_ID 1   /* a list id outside [-1, n_items) */
+#define CIRS_RANK_ERR_USER 2 /* a user outside [0, n_users)     */
+typedef struct cirs_rank_cfg {
+    int32_t n_users, n_items; /* rows / used columns of rel */
+    int32_t k;                /* 1..CIRS_TOPK_MAX list positions scored */
+    int32_t reserved;
+    double rel_threshold;     /* an item is relevant iff rel >= rel_threshold */
+    double discount[CIRS_TOPK_MAX]; /* 1 / log2(r + 2), computed by the caller: the device takes no logarithm */
+} cirs_rank_cfg;
+/* Scores n lists against a relevance table.  ids [n, ld_ids] i64 (columns 0..k-1 used, -1 = fill, ld_ids >= k), users [n] i32 =
+ * the row of rel f64 [n_users, ld_rel] (ld_rel >= n_items), item_cats [n_items] packed categories (cirs_env_tables.item_cats);
+ * visited / env_ids / skip as in cirs_rows_topk: masked items leave n_rel and the ideal list (a list is scored as it stands: it is
+ * expected to come from a selection under the same mask).  per_row f64 [n, CIRS_RANK_NCOL]:
+ *   n_list = ids >= 0 | n_rel = unmasked items with rel >= rel_threshold | hits = listed items with rel >= rel_threshold
+ *   precision = hits / k | recall = hits / n_rel (0 if n_rel = 0) | hit = hits > 0 | mrr = 1 / rank of the first hit (from 1; 0 if none)
+ *   dcg = sum over positions r = 0..k-1, in that order, of gain(rel[u, id_r]) * discount[r], gain(x) = x > 0 ? x : 0 (fills add nothing)
+ *   idcg = the same sum over the k largest gains of the unmasked items in descending order | ndcg = dcg / idcg (0 if idcg = 0)
+ *   ild = 1 - mean Jaccard similarity popc(a & b) / popc(a | b) of the category masks over the pairs of listed items (empty union:
+ *         0; fewer than two items: ild = 0); summed per first item a over b = a+1.. ascending, the partial sums then added in ascending a.
+ * A skipped row is all zero.  An id outside [-1, n_items) or a user outside [0, n_users) is never used as an index: the row is all
+ * zero and its CIRS_RANK_ERR_* bits are or-ed into the error word.  sums f64 [CIRS_RANK_NSUM] = {rows not skipped, error word, means
+ * of precision, recall, hit, mrr, ndcg, ild over the rows not skipped (0 if there is none)}: a second launch of one 256-thread
+ * workgroup, thread t adds rows t, t + 256, ... in ascending order, then a halving tree over the 256 partials (no float atomics).
+ * Lists are assumed duplicate-free.  workspace: cirs_rank_metrics_workspace_bytes(n) (0 for n <= 0). */
+int64_t cirs_rank_metrics_workspace_bytes(int32_t n);
+int cirs_rank_metrics(const cirs_rank_cfg* cfg, const int64_t* ids, int64_t ld_ids, const int32_t* users, int32_t n, const double* rel,
+                      int64_t ld_rel, const uint32_t* item_cats, const int32_t* env_ids, const uint32_t* visited, const uint8_t* skip,
+                      double* per_row, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
