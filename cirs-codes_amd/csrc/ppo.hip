@@ -502,12 +502,39 @@ __device__ __forceinline__ float dz_of(float z, float lse, float c_logp, float c
     return c_logp * ((is_act ? 1.0f : 0.0f) - p) + c_ent * p * (z - lse + h_ent);
 }
 
+// Values that cross workgroups INSIDE one launch are written through (sc1 stores, completed before the arrival is counted) and read around
+// the non-coherent caches (sc1 loads): the write-through form of MI355X_MICROARCH.md's inter-workgroup visibility rules -- no L2 write-back fence.
+__device__ __forceinline__ void st_sc1(float* p, float a) { __hip_atomic_store(p, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float2 ld_sc1x2(const float* p) {      // (p 8-byte aligned)
+    const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
+}
+// 16-byte write-through store (buffer_store_dwordx4 ... sc1) for slabs that a LATER launch reads.  A plain store stays dirty in the writing XCD's L2 and
+// leaves in the end-of-kernel write-back, on the launch boundary, while the next kernel waits; written through, the same bytes leave while the kernel
+// still computes, and a 16-byte unit costs what a plain store costs (8- and 4-byte sc1 stores are one fabric write each: 2.7 x and 6 x per byte).
+// Nothing waits for these stores inside the launch -- no drain, no fence: the boundary publishes them; the R slabs of trunk_rows_kernel, which ARE
+// handed over inside their launch, keep their drain.  `base` is wave-uniform (made so here) and is the tile's / slab's own address, `bytes` its size:
+// the per-lane byte offset is small by construction -- never one descriptor for a workspace region, those pass 4 GB -- and a store at or beyond
+// `bytes` is dropped.  Kept where profiles/r13_step_store_forms.md measured a gain, site by site.
+typedef unsigned wt_u32x4 __attribute__((ext_vector_type(4)));
+struct WtBuf { __amdgpu_buffer_rsrc_t r; };
+__device__ __forceinline__ WtBuf wt_buf(const void* base, unsigned bytes) {
+    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+    return WtBuf{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, (int)bytes, 0x00020000)};
+}
+__device__ __forceinline__ void st_wt16(const WtBuf& b, int byte_off, f32x4 x) {      // (base + byte_off 16-byte aligned; aux 16 = sc1)
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(wt_u32x4, x), b.r, byte_off, 0, 16);
+}
+__device__ __forceinline__ void st_wt16(const WtBuf& b, int byte_off, uint4 x) { st_wt16(b, byte_off, __builtin_bit_cast(f32x4, x)); }
+
 // Wa as fp16 planes, per item tile of 32 (items beyond I are zero rows), 24576 B per tile:
 //   [0, 12288)      row-major  R[p][item 32][col 64]    : A operand of Z^T = Wa H2^T (lane = item, 8 consecutive cols)
 //   [12288, 24576)  col-major  C[p][col 64][slot 32]    : B operand of dH2 = dZ Wa  (lane = col, 8 consecutive slots);
 //                   slot 16 t + 8 hi + j holds item acc_row(8 t + j, hi): the order in which the logit accumulators
 //                   of a lane enumerate the items, so the dZ registers are the A operand as they are.
-__device__ __forceinline__ void wa_planes_from_lds(int tile, uint4* __restrict__ planes, const float* sw);
+template <bool kWt = false> __device__ __forceinline__ void wa_planes_from_lds(int tile, uint4* __restrict__ planes, const float* sw);
 __device__ __forceinline__ void wa_planes_block(int tile, int I, const float* __restrict__ wa, uint4* __restrict__ planes, float* sw) {
     const int tid = threadIdx.x, tile0 = tile * kTileN;
 #pragma unroll
@@ -522,13 +549,16 @@ __device__ __forceinline__ void wa_planes_block(int tile, int I, const float* __
     wa_planes_from_lds(tile, planes, sw);
 }
 // the six planes of item tile `tile` from its fp32 image sw[item][65] (all 256 threads; the caller has synchronised the image)
-__device__ __forceinline__ void wa_planes_from_lds(int tile, uint4* __restrict__ planes, const float* sw) {
+// kWt: the units are written through (adam_next_kernel: the next step's head kernels read them, one launch boundary later)
+template <bool kWt> __device__ __forceinline__ void wa_planes_from_lds(int tile, uint4* __restrict__ planes, const float* sw) {
     const int tid = threadIdx.x;
     uint4* out = planes + (size_t)tile * kPlaneTileU4;
+    const WtBuf ob = wt_buf(out, kPlaneTileU4 * 16);      // the tile's 24 KB
     {
         const float* r = &sw[(tid >> 3) * 65 + 8 * (tid & 7)];
         const HPl pl = hsplit8(kScWa * r[0], kScWa * r[1], kScWa * r[2], kScWa * r[3], kScWa * r[4], kScWa * r[5], kScWa * r[6], kScWa * r[7]);
-        out[tid] = __builtin_bit_cast(uint4, pl.h); out[512 + tid] = __builtin_bit_cast(uint4, pl.l);
+        if constexpr (kWt) { st_wt16(ob, 16 * tid, __builtin_bit_cast(uint4, pl.h)); st_wt16(ob, 16 * (512 + tid), __builtin_bit_cast(uint4, pl.l)); }
+        else { out[tid] = __builtin_bit_cast(uint4, pl.h); out[512 + tid] = __builtin_bit_cast(uint4, pl.l); }
     }
     {
         const int n = tid >> 2, t = (tid >> 1) & 1, hi = tid & 1;
@@ -536,7 +566,8 @@ __device__ __forceinline__ void wa_planes_from_lds(int tile, uint4* __restrict__
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[j] = kScWa * sw[acc_row(8 * t + j, hi) * 65 + n];
         const HPl pl = hsplit8(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7]);
-        out[768 + tid] = __builtin_bit_cast(uint4, pl.h); out[1280 + tid] = __builtin_bit_cast(uint4, pl.l);
+        if constexpr (kWt) { st_wt16(ob, 16 * (768 + tid), __builtin_bit_cast(uint4, pl.h)); st_wt16(ob, 16 * (1280 + tid), __builtin_bit_cast(uint4, pl.l)); }
+        else { out[768 + tid] = __builtin_bit_cast(uint4, pl.h); out[1280 + tid] = __builtin_bit_cast(uint4, pl.l); }
     }
 }
 
@@ -769,10 +800,10 @@ __global__ __launch_bounds__(256, 2) void head_stats_kernel(int I, int mb, int n
             hmfma_split2(za[2], hz[2], za[3], hz[3], acc, accs, acct);
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = acc[r] + (accs[r] + acct[r]);
-            if (kZout) {      // four 1 KB stores per wave, issued before the statistics below (nothing waits for them)
-                float4* zp = zslab + ((size_t)(tile0 / kTileN) * (n_pad / kTileM) + (row0 / kTileM)) * kZTileF4 + lane;
+            if (kZout) {      // four 1 KB stores per wave, written through, issued before the statistics below (nothing waits for them)
+                const WtBuf zb = wt_buf(zslab + ((size_t)(tile0 / kTileN) * (n_pad / kTileM) + (row0 / kTileM)) * kZTileF4, kZTileF4 * 16);      // this tile's 4 KB
 #pragma unroll
-                for (int q = 0; q < 4; ++q) zp[q * 64] = float4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]};
+                for (int q = 0; q < 4; ++q) st_wt16(zb, 16 * (q * 64 + lane), f32x4{acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]});
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] *= kScZi;
@@ -1689,14 +1720,6 @@ __device__ __forceinline__ void dw_tile_x_lds(const float* sX, int ldx, int K, i
 #pragma unroll
     for (int j = 0; j < 16; ++j) b[j] = (k_ok && row0 + 2 * j + hi < n_rows) ? sX[(2 * j + hi) * ldx + k] : 0.f;
 }
-// Values that cross workgroups INSIDE one launch are written through (sc1 stores, completed before the arrival is counted) and read around
-// the non-coherent caches (sc1 loads): the write-through form of MI355X_MICROARCH.md's inter-workgroup visibility rules -- no L2 write-back fence.
-__device__ __forceinline__ void st_sc1(float* p, float a) { __hip_atomic_store(p, a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float2 ld_sc1x2(const float* p) {      // (p 8-byte aligned)
-    const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
-}
 __device__ __forceinline__ void dw_tile_32rows(const float* sY, const float (&b)[16], int K, int o0, int k0, float* __restrict__ out, int lane) {
     const int hi = lane >> 5, lo = lane & 31;
     const int o = o0 + lo, k = k0 + lo;
@@ -2008,10 +2031,6 @@ struct RowsLds {
     float dv[kRR];
     __attribute__((aligned(16))) float ps[3][kRR * kH];          // chunk-slab sums of quarters 1..3 of the chunks (quarter 0 stays in its threads' registers)
 };
-__device__ __forceinline__ void st_sc1x2(float* p, float a, float b) {      // 8-byte write-through store (p 8-byte aligned)
-    __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), ((unsigned long long)__float_as_uint(b) << 32) | __float_as_uint(a), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int n_chunks, int S, const float* __restrict__ w1, const float* __restrict__ w2,
                                                          const float* __restrict__ wc, MbView v, float* __restrict__ dobs_accum, float* __restrict__ g,
                                                          long wa_beg, long wa_len, long slab_stride, int n_slabs, int n_r, int rslab /* floats per R slab */,
@@ -2174,6 +2193,7 @@ __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int 
     __syncthreads();
     CIRS_PSTAMP(b == 0, 22);
     float* slab = v.dwp + (size_t)b * rslab;
+    const WtBuf sbuf = wt_buf(slab, 4u * (unsigned)rslab);      // this workgroup's slab (rslab = snap_stride(S): a multiple of 4 floats, so every slab is 16-byte aligned)
     const int o_b1 = kH * S, o_w2 = o_b1 + kH, o_b2 = o_w2 + kH * kH;
     {   // d W2 [o][k]: thread (o = tid / 8, k = 8 (tid % 8) .. + 8), rows in order
         const int o = tid >> 3, kb = (tid & 7) * 8;
@@ -2185,9 +2205,9 @@ __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int 
 #pragma unroll
             for (int u = 0; u < 4; ++u) { w[u] = __builtin_fmaf(a, ha[u], w[u]); w[4 + u] = __builtin_fmaf(a, hb[u], w[4 + u]); }
         }
-        float* d = slab + o_w2 + o * kH + kb;       // (o_w2 = 64 (S + 1): 8-byte aligned)
-#pragma unroll
-        for (int u = 0; u < 8; u += 2) st_sc1x2(d + u, w[u], w[u + 1]);
+        const int d = o_w2 + o * kH + kb;           // (o_w2 = 64 (S + 1) and the slabs are 16-byte aligned: two 16-byte units)
+        st_wt16(sbuf, 4 * d, f32x4{w[0], w[1], w[2], w[3]});
+        st_wt16(sbuf, 4 * (d + 4), f32x4{w[4], w[5], w[6], w[7]});
     }
     {   // d W1 [o][s]: thread (o = tid / 8, s = 4 (tid % 8) .. + 4)
         const int o = tid >> 3, sb = (tid & 7) * 4;
@@ -2199,8 +2219,12 @@ __global__ __launch_bounds__(512) void trunk_rows_kernel(int mb, int n_pad, int 
 #pragma unroll
             for (int u = 0; u < 4; ++u) w[u] = __builtin_fmaf(a, x4[u], w[u]);
         }
+        if ((S & 3) == 0) {      // (wave-uniform) the thread's four outputs are one aligned 16-byte unit
+            if (sb < S) st_wt16(sbuf, 4 * (o * S + sb), f32x4{w[0], w[1], w[2], w[3]});
+        } else {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) if (sb + u < S) st_sc1(slab + o * S + sb + u, w[u]);
+            for (int u = 0; u < 4; ++u) if (sb + u < S) st_sc1(slab + o * S + sb + u, w[u]);
+        }
     }
     if (tid < kH) {             // bias columns and the critic's row
         float s2 = 0.f, s1 = 0.f, wcg = 0.f;
@@ -2633,6 +2657,7 @@ __device__ __forceinline__ void adam_next_planes(const AdamArgs& a, const AdamNe
     }
     float tn;
     const float c = norm_coef_block(a.partial, a.cfg, l.sh, tn);
+    const size_t tile_off = (size_t)a.L.wa + (size_t)tile0 * kH;
     CIRS_PSTAMP(nx.n_t > 0 && bp == 0, 9);
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
@@ -2643,15 +2668,16 @@ __device__ __forceinline__ void adam_next_planes(const AdamArgs& a, const AdamNe
             adam_elem<1, 1>(pi, mi, vi, g4[q][u], a.sb, c, a.beta1, a.beta2, a.eps);
             p4[q][u] = ok[q] ? pi : 0.f; m4[q][u] = mi; v4[q][u] = vi;          // (items beyond the catalogue: zero rows in the planes)
         }
-        if (ok[q]) {
-            *reinterpret_cast<f32x4*>(a.p + off[q]) = p4[q]; *reinterpret_cast<f32x4*>(a.m + off[q]) = m4[q]; *reinterpret_cast<f32x4*>(a.v + off[q]) = v4[q];
+        if (ok[q]) {      // written through: the tile's 8 KB of each array, off[q] = tile_off + 4 f here
+            st_wt16(wt_buf(a.p + tile_off, kTileN * kH * 4), 16 * f, p4[q]); st_wt16(wt_buf(a.m + tile_off, kTileN * kH * 4), 16 * f, m4[q]);
+            st_wt16(wt_buf(a.v + tile_off, kTileN * kH * 4), 16 * f, v4[q]);
         }
         float* d = &l.lt[item * 65 + col];
         d[0] = p4[q][0]; d[1] = p4[q][1]; d[2] = p4[q][2]; d[3] = p4[q][3];
     }
     __syncthreads();
     CIRS_PSTAMP(nx.n_t > 0 && bp == 0, 10);
-    wa_planes_from_lds(bp, nx.planes, l.lt);
+    wa_planes_from_lds<true>(bp, nx.planes, l.lt);
 }
 // A0: element e of [trunk | wc | bc] (nothing else: the T workgroups wait for these)
 __device__ __forceinline__ void adam_next_trunk_params(const AdamArgs& a, const MbView& mv, AdamLds& l, int b0, int drop_arrival) {
