@@ -1606,12 +1606,6 @@ __host__ inline HeadBwdFn head_bwd_fn(bool ent, bool merge, bool zin) {
 }
 // (the hand-over form runs two wave roles per row tile: twice the threads)
 __host__ inline int head_bwd_threads(bool zin) { return zin ? kBwdRoleThreads : kBwdWaves * 64; }
-// CIRS_PPO_HEAD_RECOMPUTE=1: the head backward forms the logits itself instead of reading head_stats_kernel's from the slab (read per call: the bit-identity
-// test and same-box A/B runs toggle it; not a tuning knob -- both forms give the same bits)
-__host__ inline bool head_recompute_env() {
-    const char* e = getenv("CIRS_PPO_HEAD_RECOMPUTE");
-    return e && atoi(e) != 0;
-}
 
 // ---- slab sums of the wa|ba gradient (one of kWaSumBlocks workgroups of 512 threads) ------------------------------------
 // The n_slabs row-block partials written by head_bwd_fused_kernel are summed in slab order into the flat gradient, one
@@ -2945,8 +2939,9 @@ extern "C" int cirs_adam_step(float* params, const float* grads, float* m, float
     return launch_adam(params, grads, m, v, n, step_before, n_sub, lr, beta1, beta2, eps, grad_scale, scale_pow, (hipStream_t)stream);
 }
 
-// ---- the launches of a minibatch step as separate pieces, so that cirs_ppo_minibatch (one step), cirs_ppo_minibatch_dp (the step cut at the
-// gradient all-reduce) and cirs_ppo_learn (all steps of an update from one call) issue the SAME kernels on the same data ---------------
+// ---- the launches of a minibatch step as separate pieces, so that every caller issues the SAME kernels on the same data: cirs_ppo_minibatch (one step),
+// cirs_ppo_minibatch_dp / cirs_ppo_minibatch_dp_chain (the step cut at the gradient all-reduce), cirs_ppo_learn (all steps of an update from one call) and
+// cirs_ppo_minibatch_tp (the item-sharded step, cut at its two exchanges: only the launches that work on the exchanged data are written out there) --------
 struct PpoRun {     // what does not change between the steps of a call
     const cirs_ppo_cfg* cfg;
     float *params, *grads, *adam_m, *adam_v;
@@ -2961,11 +2956,21 @@ struct PpoRun {     // what does not change between the steps of a call
     cirs_policy_weights w;
     cirs::MbView v;
     float* tail;            // {clip, vf, ent, 0} partials of this rank (behind the flat gradient)
+    // the A/B and test switches: read by ppo_run, so once per exported call and never cached across calls (tests flip them between calls)
     bool merge_launch;      // CIRS_PPO_MERGE_KERNEL=1: the round-2 sequence with the merge of the statistics partials as a launch of its own (A/B runs)
-    bool head_recompute;    // CIRS_PPO_HEAD_RECOMPUTE=1: no logit hand-over between the two head kernels (A/B runs, bit-identity test)
+    bool head_recompute;    // CIRS_PPO_HEAD_RECOMPUTE=1: the head backward forms the logits itself instead of reading head_stats_kernel's from the slab (the
+                            // bit-identity test and same-box A/B runs toggle it; not a tuning knob -- both forms give the same bits).  Phase 1 of a
+                            // cirs_ppo_minibatch_tp step writes the slab and phase 2 reads it: the switch is the same in both phases of a step
+    bool rows_kernel;       // CIRS_PPO_ROWS_KERNEL=0/1 forces either trunk backward (rows_kernel_wanted; A/B runs, tests)
+    bool learn_prefetch;    // CIRS_PPO_LEARN_PREFETCH=0: every step of cirs_ppo_learn starts with its own trunk_adv_kernel launch (A/B runs, tests)
+    int drop_arrival;       // CIRS_PPO_TEST_DROP_ARRIVAL=1: AdamNext::drop_arrival of a launch that runs the next step's head (test hook)
 };
 struct PpoStep { const int32_t* idx; int mb; const int32_t* sidx; int mb_norm; float* dobs; float* loss_out; long opt_step; };
 
+static int env_int(const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+}
 static PpoRun ppo_run(const cirs_ppo_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, const cirs_ppo_batch* batch, int n_env,
                       void* workspace, int max_mb, hipStream_t s) {
     using namespace cirs;
@@ -2978,60 +2983,63 @@ static PpoRun ppo_run(const cirs_ppo_cfg* cfg, float* params, float* grads, floa
                               params + r.L.bc};
     r.v = carve(workspace, r.n_pad_carve, r.I, r.S);
     r.tail = grads + r.L.total;
-    const char* mk_ = getenv("CIRS_PPO_MERGE_KERNEL");      // (read per call: tests toggle it)
-    r.merge_launch = mk_ && atoi(mk_) != 0;
-    r.head_recompute = head_recompute_env();
+    r.merge_launch = env_int("CIRS_PPO_MERGE_KERNEL", 0) != 0;
+    r.head_recompute = env_int("CIRS_PPO_HEAD_RECOMPUTE", 0) != 0;
+    r.rows_kernel = env_int("CIRS_PPO_ROWS_KERNEL", 1) != 0;
+    r.learn_prefetch = env_int("CIRS_PPO_LEARN_PREFETCH", 1) != 0;
+    r.drop_arrival = env_int("CIRS_PPO_TEST_DROP_ARRIVAL", 0);
     return r;
 }
 static cirs::TrunkRowOut trunk_out_of(const cirs::MbView& v) { return cirs::TrunkRowOut{v.h2, v.value, v.h1, v.obs, v.act, v.dst_row, v.adv, v.h2z, v.h2b}; }
+static long head_seg(const PpoRun& r) { return (long)r.I * cirs::kH + r.I; }    // floats of wa | ba in the flat parameter / gradient buffer
 
 // 1+2. advantage statistics of the (global) minibatch, the trunk forward (same fma chains as the rollout -> ratio == 1 exactly while the
-//      weights are unchanged; rows gathered from the buffer-order batch through idx, v.obs keeps the copy for d W1) and the fp16 planes of Wa
-static int launch_trunk_adv(const PpoRun& r, const PpoStep& st) {
+//      weights are unchanged; rows gathered from the buffer-order batch through idx, out.obs_copy keeps the copy for d W1) and the fp16 planes of Wa
+static int launch_trunk_adv(const PpoRun& r, const PpoStep& st, const cirs::TrunkRowOut& out) {
     using namespace cirs;
     const int n_pad = n_pad_of(st.mb);
     hipLaunchKernelGGL(trunk_adv_kernel, dim3(cdiv(n_pad, 4) + 1 + cdiv(r.I, kTileN)), dim3(256), 0, r.s, r.pcfg, r.w, (const float*)r.batch->obs, (long)r.S,
                        n_pad, st.idx, st.mb, (const float*)r.batch->adv, st.sidx, st.mb_norm, (int)r.cfg->norm_adv, r.v.red, (int)cdiv(n_pad, 4),
-                       r.v.wa_planes, *r.batch, r.n_env, trunk_out_of(r.v));
+                       r.v.wa_planes, *r.batch, r.n_env, out);
     CIRS_CHECK_LAUNCH("trunk_adv_kernel");
     return CIRS_OK;
 }
-// 3-5. head statistics, head backward (+ the merge of the statistics partials in its prologue), chunk-slab sums of d h2 (unless the trunk-backward
-//      launch of the single-rank step sums them itself)
-static int launch_head(const PpoRun& r, const PpoStep& st, int* n_bchunks_out, bool with_dh2_sum) {
+// 3. head statistics (log-sum-exp, E_p[z]) on the matrix cores from the fp16 planes of Wa; all workgroups co-resident (2 per CU) with equal tile counts.
+//    Its logits go to v.zslab for the backward kernel unless CIRS_PPO_HEAD_RECOMPUTE=1.  *hma: what the merge of its partials needs (pv, n_schunks).
+static int launch_head_stats(const PpoRun& r, const PpoStep& st, const int32_t* act_rows, float* za_out, cirs::HeadMergeArgs* hma) {
     using namespace cirs;
-    const int I = r.I, mb = st.mb, n_pad = n_pad_of(mb), n_slabs = n_row_blocks_of(n_pad);
-    const MbView& v = r.v;
-    ActorPartialView pv = partial_view(v.head_ws, n_pad, I);
-    const int n_item_tiles = cdiv(I, kTileN);
-    // head statistics (log-sum-exp, E_p[z]) on the matrix cores from the fp16 planes of Wa; all workgroups co-resident (2 per CU) with equal tile counts
+    const int n_pad = n_pad_of(st.mb), n_slabs = n_row_blocks_of(n_pad), n_item_tiles = cdiv(r.I, kTileN);
     const int tpc_s = head_tiles_per_chunk(n_item_tiles, n_slabs, 2);   // measured: 1 / 2 / 3 workgroups per CU = 17.4 / 14.5 / 16.7 us
     const int n_schunks = cdiv(n_item_tiles, tpc_s);   // <= n_chunks: the partial arrays fit
-    // (its logits go to v.zslab for the backward kernel unless CIRS_PPO_HEAD_RECOMPUTE=1)
+    *hma = HeadMergeArgs{*r.cfg, *r.batch, st.idx, st.mb_norm, n_schunks, partial_view(r.v.head_ws, n_pad, r.I)};
     const auto stats_fn = r.head_recompute ? head_stats_kernel<false> : head_stats_kernel<true>;
-    CIRS_PROF_LAUNCH(2, r.s, hipLaunchKernelGGL(stats_fn, dim3(n_schunks, n_slabs), dim3(256), 0, r.s, I, mb, n_pad, tpc_s,
-                                                (const uint4*)v.wa_planes, r.w.ba, (const uint4*)v.h2z, pv, (const int32_t*)v.act, v.za, v.zslab));
+    CIRS_PROF_LAUNCH(2, r.s, hipLaunchKernelGGL(stats_fn, dim3(n_schunks, n_slabs), dim3(256), 0, r.s, r.I, st.mb, n_pad, tpc_s, (const uint4*)r.v.wa_planes,
+                                                r.w.ba, (const uint4*)r.v.h2z, hma->pv, act_rows, za_out, r.v.zslab));
     CIRS_CHECK_LAUNCH("head_stats_kernel");
-    // head backward; the merge of the statistics partials + row losses + backward coefficients (means over the global minibatch) run in
-    // its prologue (CIRS_PPO_MERGE_KERNEL=1: as a launch of their own, the round-2 sequence, for A/B runs)
-    const HeadMergeArgs hma{*r.cfg, *r.batch, st.idx, st.mb_norm, n_schunks, pv};
-    if (r.merge_launch) {
-        hipLaunchKernelGGL(head_stats_merge_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, r.s, *r.cfg, *r.batch, st.idx, mb, st.mb_norm, n_pad, n_schunks,
-                           r.n_env, pv, r.w.wa, r.w.ba, v, (const float*)nullptr, 0);
-        CIRS_CHECK_LAUNCH("head_stats_merge_kernel");
-    }
-    // chunking of the backward kernel: all workgroups co-resident (1 per CU) with equal tile counts -> no tail round
+    return CIRS_OK;
+}
+// 4. head backward; with `merge` the merge of the statistics partials + row losses + backward coefficients (means over the global minibatch) run in its
+//    prologue from `hma`, otherwise a head_stats_merge_kernel launch of the caller has left them in the workspace
+static int launch_head_bwd(const PpoRun& r, const PpoStep& st, const cirs::HeadMergeArgs& hma, bool merge, int* n_bchunks_out) {
+    using namespace cirs;
+    const int n_pad = n_pad_of(st.mb), n_slabs = n_row_blocks_of(n_pad), n_item_tiles = cdiv(r.I, kTileN);
+    // chunking: all workgroups co-resident (1 per CU) with equal tile counts -> no tail round
     const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
     const int n_bchunks = cdiv(n_item_tiles, tpc);  // <= n_chunks: the d h2 / entropy partial slabs fit
     const dim3 bgrid((n_bchunks + 7) & ~7, n_slabs), bblock(head_bwd_threads(!r.head_recompute));
-    const HeadBwdFn bwd_fn = head_bwd_fn(r.cfg->ent_coef != 0.f, !r.merge_launch, !r.head_recompute);
-    CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL(bwd_fn, bgrid, bblock, 0, r.s, I, mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)r.w.ba, v, v.dwap, hma));
+    const HeadBwdFn bwd_fn = head_bwd_fn(r.cfg->ent_coef != 0.f, merge, !r.head_recompute);
+    CIRS_PROF_LAUNCH(1, r.s, hipLaunchKernelGGL(bwd_fn, bgrid, bblock, 0, r.s, r.I, st.mb, n_pad, tpc, (const uint4*)r.v.wa_planes, (const float*)r.w.ba, r.v,
+                                                r.v.dwap, hma));
     CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
-    if (with_dh2_sum) {
-        hipLaunchKernelGGL(dh2_sum_kernel, dim3(n_pad * (kH / 4) / 64 + cdiv(n_pad, 64)), dim3(64), 0, r.s, mb, n_pad, n_bchunks, v);
-        CIRS_CHECK_LAUNCH("dh2_sum_kernel");
-    }
     *n_bchunks_out = n_bchunks;
+    return CIRS_OK;
+}
+// 5. chunk-slab sums of d h2 and of the entropy partials (trunk_rows_kernel sums them itself); tp_dh2 / tp_ent: into the exchange buffer of the item-sharded step
+static int launch_dh2_sum(const PpoRun& r, const PpoStep& st, int n_bchunks, float* tp_dh2 = nullptr, float* tp_ent = nullptr) {
+    using namespace cirs;
+    const int n_pad = n_pad_of(st.mb);
+    hipLaunchKernelGGL(dh2_sum_kernel, dim3(n_pad * (kH / 4) / 64 + cdiv(n_pad, 64)), dim3(64), 0, r.s, st.mb, n_pad, n_bchunks, r.v, tp_dh2, tp_ent);
+    CIRS_CHECK_LAUNCH("dh2_sum_kernel");
     return CIRS_OK;
 }
 // d wc/d bc, d W2/d b2, d W1/d b1 as one row slab per trunk-backward workgroup (32 rows)
@@ -3054,16 +3062,15 @@ static cirs::DwJobs trunk_dw_jobs(const PpoRun& r, int n_pad) {
     return jobs;
 }
 // 6. trunk backward of the data-parallel step (and of CIRS_PPO_ROWS_KERNEL=0): d a2, d a1, d obs (scattered to the tracker-gradient tensor) over 32-row
-//    MFMA tiles + the slab sums of the wa|ba gradient as extra workgroups of the same launch; the weight gradients stay in row slabs
-static int launch_trunk_bwd(const PpoRun& r, const PpoStep& st, int n_bchunks) {
+//    MFMA tiles of `v` (r.v, or the item-sharded step's copy that reads the all-reduced d h2) + with `wa_sum` the slab sums of the wa|ba gradient as extra
+//    workgroups of the same launch; the weight gradients stay in row slabs
+static int launch_trunk_bwd(const PpoRun& r, const PpoStep& st, const cirs::MbView& v, int n_chunks, bool wa_sum) {
     using namespace cirs;
     static_assert(kH == 64, "trunk_bwd_kernel tiles assume hidden == 64");
     CIRS_REQUIRE(r.S <= 32, "dim_state > 32 is not supported by the trunk backward kernel");
     const int n_pad = n_pad_of(st.mb), n_slabs = n_row_blocks_of(n_pad);
-    const long seg = (long)r.I * kH + r.I;
-    const DwJobs jobs = trunk_dw_jobs(r, n_pad);
-    hipLaunchKernelGGL(trunk_bwd_kernel, dim3(n_pad / kTileM + kWaSumBlocks), dim3(512), 0, r.s, st.mb, n_pad, n_bchunks, r.S, r.w.w1, r.w.w2, r.w.wc, r.v, st.dobs,
-                       r.grads, (long)r.L.wa, seg, (long)dwa_slab_stride(r.I), n_slabs, jobs, r.v.dwp);
+    hipLaunchKernelGGL(trunk_bwd_kernel, dim3(n_pad / kTileM + (wa_sum ? kWaSumBlocks : 0)), dim3(512), 0, r.s, st.mb, n_pad, n_chunks, r.S, r.w.w1, r.w.w2,
+                       r.w.wc, v, st.dobs, r.grads, (long)r.L.wa, head_seg(r), (long)dwa_slab_stride(r.I), n_slabs, trunk_dw_jobs(r, n_pad), v.dwp);
     CIRS_CHECK_LAUNCH("trunk_bwd_kernel");
     return CIRS_OK;
 }
@@ -3072,18 +3079,14 @@ static int launch_trunk_bwd(const PpoRun& r, const PpoStep& st, int n_bchunks) {
 // one box at C3, 1024 rows (tools/ab_step.py, round 5): with ONE arrival counter 78.5 us per step against 77.2 us for the sequence; with one arrival FLAG
 // per row workgroup (128 read-modify-writes of one address were serialised at the memory side) 75.75 against 76.1 us.  CIRS_PPO_ROWS_KERNEL=0/1 forces
 // either (A/B runs, tests).
-static bool rows_kernel_wanted(int phase, int mb) {
-    if (cirs::n_pad_of(mb) / cirs::kRR > cirs::kSyncA0) return false;      // (one arrival flag per row workgroup)
-    const char* e = getenv("CIRS_PPO_ROWS_KERNEL");
-    if (e) return atoi(e) != 0;
-    (void)phase;
-    return true;
+static bool rows_kernel_wanted(const PpoRun& r, int mb) {
+    return cirs::n_pad_of(mb) / cirs::kRR <= cirs::kSyncA0 && r.rows_kernel;      // (one arrival flag per row workgroup)
 }
 static int launch_trunk_rows(const PpoRun& r, const PpoStep& st, int n_bchunks, bool with_loss_partials) {
     using namespace cirs;
     CIRS_REQUIRE(r.S <= 32, "dim_state > 32 is not supported by the trunk backward kernel");
     const int n_pad = n_pad_of(st.mb), n_slabs = n_row_blocks_of(n_pad);
-    const long seg = (long)r.I * kH + r.I;
+    const long seg = head_seg(r);
     const int n_r = n_pad / kRR, n_f = cdiv(snap_floats(r.S), kFOut);
     CIRS_REQUIRE(n_r <= kSyncA0, "trunk_rows_kernel: more than 2048 rows in a minibatch (one arrival flag per 8 rows)");
     const long n4 = seg >> 2;
@@ -3096,6 +3099,28 @@ static int launch_trunk_rows(const PpoRun& r, const PpoStep& st, int n_bchunks, 
                        r.w.w2, r.w.wc, r.v, st.dobs, r.grads, (long)r.L.wa, seg, (long)dwa_slab_stride(r.I), n_slabs, n_r, snap_stride(r.S),
                        with_loss_partials ? r.tail : (float*)nullptr, st.mb_norm, n_w);
     CIRS_CHECK_LAUNCH("trunk_rows_kernel");
+    return CIRS_OK;
+}
+// the data-parallel step without trunk_rows_kernel: the flat trunk gradient from the row slabs + this rank's loss partials, for the caller's all-reduce
+static int launch_dw_final_loss(const PpoRun& r, const PpoStep& st) {
+    using namespace cirs;
+    const int n_pad = n_pad_of(st.mb);
+    const DwJobs jobs = trunk_dw_jobs(r, n_pad);
+    hipLaunchKernelGGL(dw_multi_final, dim3(cdiv(jobs.total_out, 256)), dim3(256), 0, r.s, jobs, n_pad / kTileM, (const float*)r.v.dwp);
+    CIRS_CHECK_LAUNCH("dw_multi_final");
+    hipLaunchKernelGGL(loss_partials_kernel, dim3(1), dim3(256), 0, r.s, st.mb, st.mb_norm, r.v, r.tail);
+    CIRS_CHECK_LAUNCH("loss_partials_kernel");
+    return CIRS_OK;
+}
+// clip_grad_norm_ stage 1 where no earlier launch of the step left the partials: `from_slabs` folds the row slabs of the trunk weight gradients into the
+// flat gradient on the way (behind trunk_bwd_kernel); without it the flat gradient is complete (the all-reduced one of data-parallel phase 2)
+static int launch_sumsq(const PpoRun& r, const PpoStep& st, bool from_slabs) {
+    using namespace cirs;
+    const int n_pad = n_pad_of(st.mb);
+    const DwJobs jobs = from_slabs ? trunk_dw_jobs(r, n_pad) : DwJobs{};
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(kNormBlocks), dim3(256), 0, r.s, r.grads, r.L.trunk, r.L.total, r.L.wa, head_seg(r), (int)from_slabs, jobs,
+                       from_slabs ? n_pad / kTileM : 0, from_slabs ? (const float*)r.v.dwp : (const float*)nullptr, r.S, r.v.normp);
+    CIRS_CHECK_LAUNCH("sumsq_partial_kernel");
     return CIRS_OK;
 }
 static cirs::AdamSeg adam_seg_of(const cirs_ppo_cfg* cfg, long step_before, int n_sub, int scale_pow) {
@@ -3112,15 +3137,8 @@ static cirs::AdamSeg adam_seg_of(const cirs_ppo_cfg* cfg, long step_before, int 
 //    phase 2: the squared norm of the all-reduced flat gradient first (sumsq_partial_kernel).
 static int launch_norm_adam(const PpoRun& r, const PpoStep& st, int phase, bool folded, const PpoStep* next) {
     using namespace cirs;
-    const int n_pad = n_pad_of(st.mb);
-    const long seg = (long)r.I * kH + r.I;
     const MbView& v = r.v;
-    if (!(phase == 0 && folded)) {
-        const DwJobs jobs = phase == 0 ? trunk_dw_jobs(r, n_pad) : DwJobs{};
-        hipLaunchKernelGGL(sumsq_partial_kernel, dim3(kNormBlocks), dim3(256), 0, r.s, r.grads, r.L.trunk, r.L.total, r.L.wa, seg, (int)(phase == 0), jobs,
-                           phase == 0 ? n_pad / kTileM : 0, phase == 0 ? (const float*)v.dwp : (const float*)nullptr, r.S, v.normp);
-        CIRS_CHECK_LAUNCH("sumsq_partial_kernel");
-    }
+    if (!(phase == 0 && folded)) { if (int rc = launch_sumsq(r, st, phase == 0)) return rc; }
     const AdamSeg sa = adam_seg_of(r.cfg, 2 * st.opt_step, 2, 2), sb = adam_seg_of(r.cfg, st.opt_step, 1, 1);
     AdamNext nx{};
     nx.n_p = cdiv(r.I, kTileN);
@@ -3131,8 +3149,7 @@ static int launch_norm_adam(const PpoRun& r, const PpoStep& st, int phase, bool 
         nx.pcfg = r.pcfg; nx.obs_flat = r.batch->obs; nx.idx = next->idx; nx.mb = next->mb; nx.n_pad = np;
         nx.adv_flat = r.batch->adv; nx.sidx = next->sidx; nx.m_stats = next->mb_norm; nx.enable = (int)r.cfg->norm_adv; nx.red = v.red;
         nx.bt = *r.batch; nx.n_env = r.n_env; nx.out = trunk_out_of(v); nx.s_magic = (65536 + r.S - 1) / r.S;
-        const char* da_ = getenv("CIRS_PPO_TEST_DROP_ARRIVAL");
-        nx.drop_arrival = da_ ? atoi(da_) : 0;
+        nx.drop_arrival = r.drop_arrival;
     }
     nx.n_a0 = cdiv(r.L.trunk + kH + 1, 256);
     const int n_a = nx.n_a0 + cdiv(r.I, 256);
@@ -3144,9 +3161,37 @@ static int launch_norm_adam(const PpoRun& r, const PpoStep& st, int phase, bool 
     return CIRS_OK;
 }
 
+// The single-rank step up to the gradient: 1-2 unless the step before ran them (head_done), 3-5, then trunk_rows_kernel or the trunk_bwd_kernel sequence.
+// for_allreduce (data-parallel phase 1): the flat gradient and this rank's loss partials are complete in `grads` when the launches end.
+static int launch_step_grads(const PpoRun& r, const PpoStep& st, bool head_done, bool for_allreduce) {
+    using namespace cirs;
+    const int n_pad = n_pad_of(st.mb);
+    HeadMergeArgs hma;
+    int n_bchunks = 0;
+    if (!head_done) { if (int rc = launch_trunk_adv(r, st, trunk_out_of(r.v))) return rc; }
+    if (int rc = launch_head_stats(r, st, r.v.act, r.v.za, &hma)) return rc;
+    if (r.merge_launch) {
+        hipLaunchKernelGGL(head_stats_merge_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, r.s, *r.cfg, *r.batch, st.idx, st.mb, st.mb_norm, n_pad, hma.n_schunks,
+                           r.n_env, hma.pv, r.w.wa, r.w.ba, r.v, (const float*)nullptr, 0);
+        CIRS_CHECK_LAUNCH("head_stats_merge_kernel");
+    }
+    if (int rc = launch_head_bwd(r, st, hma, !r.merge_launch, &n_bchunks)) return rc;
+    if (rows_kernel_wanted(r, st.mb)) return launch_trunk_rows(r, st, n_bchunks, for_allreduce);
+    if (int rc = launch_dh2_sum(r, st, n_bchunks)) return rc;
+    if (int rc = launch_trunk_bwd(r, st, r.v, n_bchunks, true)) return rc;
+    return for_allreduce ? launch_dw_final_loss(r, st) : CIRS_OK;
+}
+// One whole single-rank step: the gradient, then 7 (folded: trunk_rows_kernel has summed the flat gradient and written the squared-norm partials; with
+// `next` the launch also runs the head of the next step, which then runs with head_done)
+static int launch_step(const PpoRun& r, const PpoStep& st, bool head_done, const PpoStep* next) {
+    if (int rc = launch_step_grads(r, st, head_done, false)) return rc;
+    return launch_norm_adam(r, st, 0, rows_kernel_wanted(r, st.mb), next);
+}
+
 // options of a data-parallel step that is part of a chain of steps (cirs_ppo_minibatch_dp_chain): the workspace is carved for the update's largest
 // local minibatch, phase 1 skips the head launch when the previous step's phase 2 already ran it, phase 2 runs the head of the next step
 struct DpChain { int max_mb; int head_done; const int32_t* next_idx; int next_mb; const int32_t* next_idx_global; int next_mb_global; };
+// phase 0: the whole step; phases 1 | 2: the same step cut at the caller's all-reduce of the flat gradient and the loss partials
 static int ppo_minibatch_impl(const cirs_ppo_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t opt_step,
                               const cirs_ppo_batch* batch, const int32_t* idx, int32_t mb, const int32_t* idx_global,
                               int32_t mb_global, float* dobs_accum, int32_t n_env, float* loss_out, void* workspace,
@@ -3161,35 +3206,16 @@ static int ppo_minibatch_impl(const cirs_ppo_cfg* cfg, float* params, float* gra
     CIRS_REQUIRE(workspace_bytes >= cirs_ppo_workspace_bytes(cfg, carve_mb), "workspace too small");
     const PpoRun r = ppo_run(cfg, params, grads, adam_m, adam_v, batch, n_env, workspace, carve_mb, (hipStream_t)stream);
     const PpoStep st{idx, (int)mb, idx_global ? idx_global : idx, (int)(idx_global ? mb_global : mb), dobs_accum, loss_out, (long)opt_step};
-    bool folded = false;
-    const bool rows = rows_kernel_wanted(phase, mb);
-    if (phase == 0 || phase == 1) {
-        CIRS_REQUIRE(idx != nullptr || (ch && ch->head_done), "idx is null");
-        int n_bchunks = 0;
-        if (!(ch && ch->head_done)) { if (int rc = launch_trunk_adv(r, st)) return rc; }
-        if (int rc = launch_head(r, st, &n_bchunks, !rows)) return rc;
-        if (rows) {     // phase 1: the flat gradient and this rank's loss partials are complete in `grads` after this launch (the caller's all-reduce follows)
-            if (int rc = launch_trunk_rows(r, st, n_bchunks, phase == 1)) return rc;
-            folded = true;
-            if (phase == 1) return CIRS_OK;
-        } else {
-            if (int rc = launch_trunk_bwd(r, st, n_bchunks)) return rc;
-            if (phase == 1) {
-                const DwJobs jobs = trunk_dw_jobs(r, n_pad_of(mb));
-                hipLaunchKernelGGL(dw_multi_final, dim3(cdiv(jobs.total_out, 256)), dim3(256), 0, r.s, jobs, n_pad_of(mb) / kTileM, (const float*)r.v.dwp);
-                CIRS_CHECK_LAUNCH("dw_multi_final");
-                hipLaunchKernelGGL(loss_partials_kernel, dim3(1), dim3(256), 0, r.s, (int)mb, st.mb_norm, r.v, r.tail);
-                CIRS_CHECK_LAUNCH("loss_partials_kernel");
-                return CIRS_OK;
-            }
-        }
-    }
-    if (ch && ch->next_idx && phase == 2) {
+    if (phase == 2) {
+        if (!(ch && ch->next_idx)) return launch_norm_adam(r, st, 2, false, nullptr);
         const PpoStep nxt{ch->next_idx, ch->next_mb, ch->next_idx_global ? ch->next_idx_global : ch->next_idx,
                           ch->next_idx_global ? ch->next_mb_global : ch->next_mb, nullptr, nullptr, (long)opt_step + 1};
-        return launch_norm_adam(r, st, phase, folded, &nxt);
+        return launch_norm_adam(r, st, 2, false, &nxt);
     }
-    return launch_norm_adam(r, st, phase, folded, nullptr);
+    const bool head_done = ch && ch->head_done;
+    CIRS_REQUIRE(idx != nullptr || head_done, "idx is null");
+    if (phase == 1) return launch_step_grads(r, st, head_done, true);
+    return launch_step(r, st, head_done, nullptr);
 }
 
 extern "C" int cirs_ppo_minibatch(const cirs_ppo_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v,
@@ -3253,8 +3279,7 @@ extern "C" int cirs_ppo_learn(const cirs_ppo_cfg* cfg, float* params, float* gra
     for (int k = 0; k < n_sl; ++k) { int b, e; ppo_slice(n_rows, batch_size, k, &b, &e); CIRS_REQUIRE(e - b >= 2, "a minibatch of one row has no unbiased std"); max_mb = e - b > max_mb ? e - b : max_mb; }
     CIRS_REQUIRE(workspace_bytes >= cirs_ppo_workspace_bytes(cfg, max_mb), "workspace too small");
     const PpoRun r = ppo_run(cfg, params, grads, adam_m, adam_v, batch, n_env, workspace, max_mb, (hipStream_t)stream);
-    const char* pf_ = getenv("CIRS_PPO_LEARN_PREFETCH");      // =0: every step starts with its own trunk_adv_kernel launch (A/B runs, tests)
-    const bool prefetch = !(pf_ && atoi(pf_) == 0) && !r.merge_launch;
+    const bool prefetch = r.learn_prefetch && !r.merge_launch;
     const int n_steps = n_repeat * n_sl;
     auto step_of = [&](int k) {
         const int rep = k / n_sl;
@@ -3268,16 +3293,9 @@ extern "C" int cirs_ppo_learn(const cirs_ppo_cfg* cfg, float* params, float* gra
         if (dobs_accum && k == (n_repeat - 1) * n_sl) {      // optim.zero_grad() at the top of the last repeat: only its d loss / d obs reaches the tracker
             if (hipMemsetAsync(dobs_accum, 0, sizeof(float) * (size_t)dobs_floats, r.s) != hipSuccess) return fail(CIRS_E_LAUNCH, "hipMemsetAsync(dobs_accum)");
         }
-        int n_bchunks = 0;
-        bool folded = false;
-        const bool rows = rows_kernel_wanted(0, st.mb);
-        if (!have_head) { if (int rc = launch_trunk_adv(r, st)) return rc; }
-        if (int rc = launch_head(r, st, &n_bchunks, !rows)) return rc;
-        if (rows) { if (int rc = launch_trunk_rows(r, st, n_bchunks, false)) return rc; folded = true; }
-        else if (int rc = launch_trunk_bwd(r, st, n_bchunks)) return rc;
         const bool has_next = prefetch && k + 1 < n_steps;
         const PpoStep nxt = has_next ? step_of(k + 1) : PpoStep{};
-        if (int rc = launch_norm_adam(r, st, 0, folded, has_next ? &nxt : nullptr)) return rc;
+        if (int rc = launch_step(r, st, have_head, has_next ? &nxt : nullptr)) return rc;
         have_head = has_next;
     }
     return CIRS_OK;
@@ -3311,6 +3329,8 @@ extern "C" int64_t cirs_ppo_tp_exchange_floats(int32_t n_rows, int32_t world) {
     return (int64_t)cirs::n_pad_of(n_rows) * (cirs::kH + 1) + (int64_t)world * cirs::kWaSumBlocks;
 }
 
+// The single-rank step over the items of THIS shard (cfg->n_items), cut at the all-gather of the row statistics (behind phase 1) and at the all-reduce of
+// `red` (behind phase 2); written out here: what works on the exchanged data
 extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, float* grads, float* adam_m, float* adam_v, int64_t opt_step,
                                      const cirs_ppo_batch* batch, const int32_t* idx, int32_t mb, int32_t item_base, int32_t rank,
                                      int32_t world, float* stats4, const float* stats_all, float* red, float* dobs_accum, int32_t n_env,
@@ -3321,37 +3341,22 @@ extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, flo
     CIRS_REQUIRE(phase >= 1 && phase <= 3, "phase must be 1, 2 or 3");
     CIRS_REQUIRE(mb >= 2 && world >= 1 && rank >= 0 && rank < world && item_base >= 0, "bad minibatch / rank arguments");
     CIRS_REQUIRE(workspace_bytes >= cirs_ppo_workspace_bytes(cfg, mb), "workspace too small");
-    hipStream_t s = (hipStream_t)stream;
-    const int I = cfg->n_items, S = cfg->dim_state;      // I = items of THIS shard
-    CIRS_REQUIRE(S <= 32, "dim_state > 32 is not supported by the trunk backward kernel");
+    CIRS_REQUIRE(cfg->dim_state <= 32, "dim_state > 32 is not supported by the trunk backward kernel");
+    const PpoRun r = ppo_run(cfg, params, grads, adam_m, adam_v, batch, n_env, workspace, mb, (hipStream_t)stream);
+    const PpoStep st{idx, (int)mb, idx, (int)mb, dobs_accum, loss_out, (long)opt_step};
+    const MbView& v = r.v;
     const int n_pad = n_pad_of(mb);
-    const PpoLayout L = ppo_layout(I, S);
-    MbView v = carve(workspace, n_pad, I, S);
-    cirs_policy_cfg pcfg{I, S, kH};
-    cirs_policy_weights w{params + L.w1, params + L.b1, params + L.w2, params + L.b2, params + L.wa, params + L.ba, params + L.wc, params + L.bc};
-    const long seg = (long)I * kH + I;
-    const int n_slabs = n_row_blocks_of(n_pad);
-    const int n_item_tiles = cdiv(I, kTileN);
     float* red_dh2 = red;
     float* red_ent = red + (size_t)n_pad * kH;
     float* red_slots = red_ent + n_pad;
-    float* tail = grads + L.total;
     if (phase == 1) {
         CIRS_REQUIRE(stats4, "stats4 is null");
-        hipLaunchKernelGGL(trunk_adv_kernel, dim3(cdiv(n_pad, 4) + 1 + cdiv(I, kTileN)), dim3(256), 0, s, pcfg, w, (const float*)batch->obs, (long)S, n_pad,
-                           idx, (int)mb, (const float*)batch->adv, idx, (int)mb, (int)cfg->norm_adv, v.red, (int)cdiv(n_pad, 4), v.wa_planes, *batch, (int)n_env,
-                           TrunkRowOut{v.h2, v.value, v.h1, v.obs, nullptr, nullptr, nullptr, v.h2z, v.h2b});
-        CIRS_CHECK_LAUNCH("trunk_adv_kernel");
-        ActorPartialView pv = partial_view(v.head_ws, n_pad, I);
-        const int tpc_s = head_tiles_per_chunk(n_item_tiles, n_slabs, 2);
-        const int n_schunks = cdiv(n_item_tiles, tpc_s);
-        // (phase 2 of the same step reads the logits from v.zslab: the switch is the same in both phases of a step)
-        const auto stats_fn = head_recompute_env() ? head_stats_kernel<false> : head_stats_kernel<true>;
-        hipLaunchKernelGGL(stats_fn, dim3(n_schunks, n_slabs), dim3(256), 0, s, I, (int)mb, n_pad, tpc_s, (const uint4*)v.wa_planes, (const float*)w.ba,
-                           (const uint4*)v.h2z, pv, (const int32_t*)nullptr, (float*)nullptr, v.zslab);
-        CIRS_CHECK_LAUNCH("head_stats_kernel");
-        hipLaunchKernelGGL(head_tp_fold_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, s, *batch, idx, (int)mb, n_pad, n_schunks, pv, (const float*)w.wa,
-                           (const float*)w.ba, (int)item_base, I, (const float*)v.h2, stats4);
+        // (no gathered action / tracker row / batch columns: phase 2's merge reads the batch through idx)
+        if (int rc = launch_trunk_adv(r, st, TrunkRowOut{v.h2, v.value, v.h1, v.obs, nullptr, nullptr, nullptr, v.h2z, v.h2b})) return rc;
+        HeadMergeArgs hma;
+        if (int rc = launch_head_stats(r, st, nullptr, nullptr, &hma)) return rc;
+        hipLaunchKernelGGL(head_tp_fold_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, r.s, *batch, idx, (int)mb, n_pad, hma.n_schunks, hma.pv, (const float*)r.w.wa,
+                           (const float*)r.w.ba, (int)item_base, r.I, (const float*)v.h2, stats4);
         CIRS_CHECK_LAUNCH("head_tp_fold_kernel");
         return CIRS_OK;
     }
@@ -3359,60 +3364,32 @@ extern "C" int cirs_ppo_minibatch_tp(const cirs_ppo_cfg* cfg, float* params, flo
         CIRS_REQUIRE(stats_all, "stats_all is null");
         // stats_all [4][world][n_pad]: the triples of all shards in rank order are the chunk partials of the merge (fixed order: every
         // rank computes identical row statistics and coefficients)
-        ActorPartialView pa;
+        ActorPartialView pa{};
         pa.m = const_cast<float*>(stats_all); pa.s = pa.m + (size_t)world * n_pad; pa.score = pa.s + (size_t)world * n_pad;
-        pa.idx = nullptr; pa.z = nullptr;
         const float* za = pa.score + (size_t)world * n_pad;
-        hipLaunchKernelGGL(head_stats_merge_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, s, *cfg, *batch, idx, (int)mb, (int)mb, n_pad, (int)world,
+        hipLaunchKernelGGL(head_stats_merge_kernel, dim3(cdiv(n_pad, 4)), dim3(256), 0, r.s, *cfg, *batch, idx, (int)mb, (int)mb, n_pad, (int)world,
                            (int)n_env, pa, (const float*)nullptr, (const float*)nullptr, v, za, (int)item_base);
         CIRS_CHECK_LAUNCH("head_stats_merge_kernel");
-        const int tpc = head_tiles_per_chunk(n_item_tiles, n_slabs, 1);
-        const int n_bchunks = cdiv(n_item_tiles, tpc);
-        const HeadMergeArgs no_merge{};    // the row coefficients come from head_stats_merge_kernel above (statistics of every shard)
-        const bool zin = !head_recompute_env();
-        hipLaunchKernelGGL(head_bwd_fn(cfg->ent_coef != 0.f, false, zin), dim3((n_bchunks + 7) & ~7, n_slabs), dim3(head_bwd_threads(zin)), 0, s, I,
-                           (int)mb, n_pad, tpc, (const uint4*)v.wa_planes, (const float*)w.ba, v, v.dwap, no_merge);
-        CIRS_CHECK_LAUNCH("head_bwd_fused_kernel");
-        CIRS_HIP(hipMemsetAsync(red_slots, 0, sizeof(float) * (size_t)world * kWaSumBlocks, s));
-        hipLaunchKernelGGL(dh2_sum_kernel, dim3(n_pad * (kH / 4) / 64 + cdiv(n_pad, 64)), dim3(64), 0, s, (int)mb, n_pad, n_bchunks, v, red_dh2, red_ent);
-        CIRS_CHECK_LAUNCH("dh2_sum_kernel");
-        hipLaunchKernelGGL(wa_slab_sum_kernel, dim3(kWaSumBlocks), dim3(512), 0, s, grads, (long)L.wa, seg, (const float*)v.dwap,
-                           (long)dwa_slab_stride(I), n_slabs, red_slots + (size_t)rank * kWaSumBlocks);
+        int n_bchunks = 0;      // (no merge in the prologue: the row coefficients come from the launch above, statistics of every shard)
+        if (int rc = launch_head_bwd(r, st, HeadMergeArgs{}, false, &n_bchunks)) return rc;
+        CIRS_HIP(hipMemsetAsync(red_slots, 0, sizeof(float) * (size_t)world * kWaSumBlocks, r.s));
+        if (int rc = launch_dh2_sum(r, st, n_bchunks, red_dh2, red_ent)) return rc;
+        hipLaunchKernelGGL(wa_slab_sum_kernel, dim3(kWaSumBlocks), dim3(512), 0, r.s, grads, (long)r.L.wa, head_seg(r), (const float*)v.dwap,
+                           (long)dwa_slab_stride(r.I), n_row_blocks_of(n_pad), red_slots + (size_t)rank * kWaSumBlocks);
         CIRS_CHECK_LAUNCH("wa_slab_sum_kernel");
         return CIRS_OK;
     }
     // phase 3: `red` holds the sums over the ranks
     CIRS_REQUIRE(loss_out, "loss_out is null");
-    hipLaunchKernelGGL(tp_post_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, s, (int)mb, n_pad, (int)world, (const float*)red_ent,
-                       (const float*)red_slots, v);
+    hipLaunchKernelGGL(tp_post_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, r.s, (int)mb, n_pad, (int)world, (const float*)red_ent, (const float*)red_slots, v);
     CIRS_CHECK_LAUNCH("tp_post_kernel");
-    DwJobs jobs;
-    jobs.n = 3;
-    jobs.j[0] = DwJob{v.dvalue, 1, v.h2, kH, 1, kH, grads + L.wc, grads + L.bc, 0, 0};
-    jobs.j[1] = DwJob{v.da2, kH, v.h1, kH, kH, kH, grads + L.w2, grads + L.b2, 0, 0};
-    jobs.j[2] = DwJob{v.da1, kH, v.obs, S, kH, S, grads + L.w1, grads + L.b1, 0, 0};
-    const int n_dw_slabs = n_pad / kTileM;
-    {
-        int off = 0, out = 0;
-        for (int q = 0; q < 3; ++q) {
-            jobs.j[q].part_off = off;
-            off += n_dw_slabs * jobs.j[q].O * (jobs.j[q].K + 1);
-            out += jobs.j[q].O * (jobs.j[q].K + 1);
-        }
-        jobs.total_out = out;
-    }
     MbView v3 = v;
     v3.dh2p = red_dh2;      // the trunk backward reads the summed d h2 (slab 0 position) from the exchange buffer
-    hipLaunchKernelGGL(trunk_bwd_kernel, dim3(n_pad / kTileM), dim3(512), 0, s, (int)mb, n_pad, 1, S, w.w1, w.w2, w.wc, v3, dobs_accum, grads,
-                       (long)L.wa, seg, (long)dwa_slab_stride(I), n_slabs, jobs, v.dwp);
-    CIRS_CHECK_LAUNCH("trunk_bwd_kernel");
-    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(kNormBlocks), dim3(256), 0, s, grads, L.trunk, L.total, L.wa, seg, 1, jobs, n_dw_slabs,
-                       (const float*)v.dwp, S, v.normp);
-    CIRS_CHECK_LAUNCH("sumsq_partial_kernel");
-    auto seg_of = [&](long step_before, int n_sub, int scale_pow) { return adam_seg_of(cfg, step_before, n_sub, scale_pow); };
-    hipLaunchKernelGGL(adam2_kernel, dim3(cdiv(L.total, 256)), dim3(256), 0, s, params, grads, adam_m, adam_v, L.total, L.trunk,
-                       seg_of(2 * opt_step, 2, 2), seg_of(opt_step, 1, 1), cfg->beta1, cfg->beta2, cfg->adam_eps, *cfg, v.normp, tail, v3, loss_out,
-                       (int)mb, (int)mb);
+    if (int rc = launch_trunk_bwd(r, st, v3, 1, false)) return rc;      // (one chunk; the wa|ba slab sums ran in phase 2)
+    if (int rc = launch_sumsq(r, st, true)) return rc;
+    hipLaunchKernelGGL(adam2_kernel, dim3(cdiv(r.L.total, 256)), dim3(256), 0, r.s, params, grads, adam_m, adam_v, r.L.total, r.L.trunk,
+                       adam_seg_of(cfg, 2 * opt_step, 2, 2), adam_seg_of(cfg, opt_step, 1, 1), cfg->beta1, cfg->beta2, cfg->adam_eps, *cfg, v.normp, r.tail, v3,
+                       loss_out, (int)mb, (int)mb);
     CIRS_CHECK_LAUNCH("adam2_kernel");
     return CIRS_OK;
 }
@@ -3440,10 +3417,9 @@ extern "C" int cirs_ppo_shard_adam(const cirs_ppo_cfg* cfg, float* params_shard,
     CIRS_REQUIRE(params_shard && grads_shard && adam_m_shard && adam_v_shard && stats_all, "null argument");
     CIRS_REQUIRE(shard_begin >= 0 && shard_len > 0 && world >= 1, "bad shard arguments");
     const PpoLayout L = ppo_layout(cfg->n_items, cfg->dim_state);
-    auto seg_of = [&](long step_before, int n_sub, int scale_pow) { return adam_seg_of(cfg, step_before, n_sub, scale_pow); };
     hipLaunchKernelGGL(shard_adam_kernel, dim3(cdiv(shard_len, 256)), dim3(256), 0, (hipStream_t)stream, params_shard, grads_shard,
-                       adam_m_shard, adam_v_shard, (long)shard_begin, (long)shard_len, L.trunk, L.total, seg_of(2 * opt_step, 2, 2),
-                       seg_of(opt_step, 1, 1), cfg->beta1, cfg->beta2, cfg->adam_eps, *cfg, stats_all, (int)world, loss_out);
+                       adam_m_shard, adam_v_shard, (long)shard_begin, (long)shard_len, L.trunk, L.total, adam_seg_of(cfg, 2 * opt_step, 2, 2),
+                       adam_seg_of(cfg, opt_step, 1, 1), cfg->beta1, cfg->beta2, cfg->adam_eps, *cfg, stats_all, (int)world, loss_out);
     CIRS_CHECK_LAUNCH("shard_adam_kernel");
     return CIRS_OK;
 }
