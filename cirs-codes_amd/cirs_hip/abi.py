@@ -61,6 +61,28 @@ class TrackerState(C.Structure):
     _fields_ = [("x_hist", C.c_void_p), ("kcache", C.c_void_p), ("vcache", C.c_void_p), ("len", C.c_void_p)]
 
 
+GRU_MAX_LAYERS = 2
+
+
+class GruCfg(C.Structure):          # cirs_gru_cfg
+    _fields_ = [("n_users", C.c_int32), ("n_items", C.c_int32), ("dim_model", C.c_int32), ("dim_state", C.c_int32),
+                ("nlayers", C.c_int32), ("max_len", C.c_int32), ("n_env", C.c_int32)]
+
+
+class GruLayer(C.Structure):        # cirs_gru_layer / cirs_gru_layer_grads
+    _fields_ = [(k, C.c_void_p) for k in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class GruWeights(C.Structure):      # cirs_gru_weights / cirs_gru_grads (same layout)
+    _fields_ = [("emb_user", C.c_void_p), ("emb_item", C.c_void_p), ("ffn_user_w", C.c_void_p), ("ffn_user_b", C.c_void_p),
+                ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("layer", GruLayer * GRU_MAX_LAYERS), ("dec_w", C.c_void_p),
+                ("dec_b", C.c_void_p)]
+
+
+class GruState(C.Structure):        # cirs_gru_state
+    _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -327,6 +349,14 @@ SIGNATURES = {
                                              _P, _P, _P, _P, _P, C.c_int32, _P, C.POINTER(TrackerWeights), _P, C.c_int64, _P]),
     "cirs_tracker_prefix_states": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(TrackerWeights), C.POINTER(TrackerState), _P, _P, _P, _P, C.c_int32, _P,
                                             C.c_int64, _P, C.c_int64, _P]),
+    "cirs_gru_tracker_init": (C.c_int, [C.POINTER(GruCfg), C.POINTER(GruWeights), C.POINTER(GruState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_gru_tracker_step": (C.c_int, [C.POINTER(GruCfg), C.POINTER(GruWeights), C.POINTER(GruState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_gru_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(GruCfg), C.c_int32]),
+    "cirs_gru_tracker_backward": (C.c_int, [C.POINTER(GruCfg), C.POINTER(GruWeights), C.POINTER(GruState), _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                            C.POINTER(GruWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_gru": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(GruCfg), C.POINTER(GruWeights),
+                                           C.POINTER(GruState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                           C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -119,6 +119,62 @@ extern "C" int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const ci
                         nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, users, true);
 }
 
+// cirs_rollout_collect with a GRU tracker (gru_tracker.hip): the unfused sequence of rollout_impl's online-reward branch without the scorer, built from
+// the public entry points -- about five launches per vector step against the fused Transformer collect's two (StateTrackerGRU).
+extern "C" int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                        const cirs_gru_cfg* trk_cfg, const cirs_gru_weights* trk_w, cirs_gru_state* trk_st,
+                                        const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                        const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                        int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    using namespace cirs;
+    CIRS_REQUIRE(env_cfg && env_tab && env_st && trk_cfg && trk_w && trk_st && pol_cfg && pol_w && traj && users && workspace && n_env > 0,
+                 "cirs_rollout_collect_gru: null argument");
+    CIRS_REQUIRE(env_tab->pred_online == nullptr, "gru rollout: the online-reward loop is not built for the GRU tracker (tables with pred_online are refused)");
+    CIRS_REQUIRE(!(greedy && gumbel), "gru rollout: greedy draws no noise, it cannot be combined with gumbel");
+    CIRS_REQUIRE(traj->obs && traj->act && traj->rew && traj->done && traj->logp && traj->value && traj->ctr, "trajectory pointer null");
+    CIRS_REQUIRE(env_st->user && env_st->turn && env_st->done && env_st->hist_action && env_st->cum_reward, "env state has null field");
+    CIRS_REQUIRE(trk_cfg->n_env == n_env, "tracker n_env mismatch");
+    CIRS_REQUIRE(trk_cfg->dim_state == pol_cfg->dim_state, "tracker/policy dim_state mismatch");
+    CIRS_REQUIRE(trk_cfg->max_len >= env_cfg->max_turn + 1, "tracker max_len < max_turn + 1");
+    CIRS_REQUIRE(pol_cfg->n_items == env_cfg->n_items && trk_cfg->n_items == env_cfg->n_items, "policy/env/tracker n_items mismatch");
+    CIRS_REQUIRE(workspace_bytes >= cirs_policy_workspace_bytes(pol_cfg, n_env) && workspace_bytes >= (int64_t)sizeof(int64_t) * n_env, "workspace too small");
+    const long B = n_env, S = trk_cfg->dim_state;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = cirs_env_reset(env_cfg, env_st, users, nullptr, n_env, nullptr, stream)) return rc;
+    if (int rc = cirs_gru_tracker_init(trk_cfg, trk_w, trk_st, users, nullptr, n_env, traj->obs, S, stream)) return rc;
+    for (int t = 0; t < env_cfg->max_turn; ++t) {
+        float* obs_t = traj->obs + (size_t)t * B * S;
+        float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
+        int64_t* act_t = traj->act + (size_t)t * B;
+        double* rew_t = traj->rew + (size_t)t * B;
+        uint8_t* done_t = traj->done + (size_t)t * B;
+        // policy(obs_t): finished envs (env_st->done) are skipped and get act = -1
+        if (greedy) {
+            if (int rc = cirs_actor_greedy(pol_cfg, pol_w, obs_t, S, n_env, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
+                                           traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
+                return rc;
+        } else {
+            if (int rc = cirs_actor_sample(pol_cfg, pol_w, obs_t, S, n_env, gumbel ? gumbel + (size_t)t * B * pol_cfg->n_items : nullptr, seed,
+                                           rng_base + (uint32_t)t, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
+                                           traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
+                return rc;
+        }
+        if (visited) {
+            hipLaunchKernelGGL(mark_visited_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, act_t, n_env, pol_cfg->n_items, visited);
+            CIRS_CHECK_LAUNCH("mark_visited_kernel");
+        }
+        if (int rc = cirs_env_step(env_cfg, env_tab, env_st, act_t, nullptr, n_env, (int64_t*)workspace, rew_t, done_t, traj->ctr + (size_t)t * B, nullptr, stream))
+            return rc;
+        if (force_length > 0) {
+            hipLaunchKernelGGL(force_done_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->done, done_t, act_t, n_env, (t + 1 >= force_length) ? 1 : 0);
+            CIRS_CHECK_LAUNCH("force_done_kernel");
+        }
+        // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
+        if (int rc = cirs_gru_tracker_step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream)) return rc;
+    }
+    return CIRS_OK;
+}
+
 extern "C" int cirs_rollout_steps(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
                                   const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w,
                                   cirs_tracker_state* trk_st, const cirs_policy_cfg* pol_cfg,

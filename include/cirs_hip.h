@@ -596,6 +596,90 @@ int cirs_embedding_scatter(const int32_t* keys, const float* contrib, int64_t n_
                            void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, recurrent: StateTrackerGRU (csrc/gru_tracker.hip)
+ * The reference declares the class and leaves it empty (core/state_tracker.py:282-289); the model is defined here:
+ *   inputs  the Transformer tracker's slots, unchanged (state_tracker.py:205-215,225-242): slot 0 = ffn_user(Emb_user[u]),
+ *           slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k; no sqrt(D) scale, no positional encoding
+ *   cell    torch.nn.GRU(input_size = D, hidden_size = D, num_layers = nlayers), h_{-1} = 0, gate order r, z, n:
+ *             r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)      z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+ *             n = tanh(W_in x + b_in + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
+ *           layer l > 0 reads layer l - 1's h' of the same position
+ *   state   s_t = decoder(h_t of the top layer)
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, nlayers in {1, 2}.  No dropout (nn.GRU has it between layers only).
+ * The existing tracker structs are not touched: a GRU tracker has its own.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_GRU_MAX_LAYERS 2
+
+typedef struct cirs_gru_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t nlayers;   /* 1 or 2 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_gru_cfg;
+
+typedef struct cirs_gru_layer { /* names: gru.weight_ih_l<k>, gru.weight_hh_l<k> [3D,D]; gru.bias_ih_l<k>, gru.bias_hh_l<k> [3D]; rows r | z | n */
+    const float *w_ih, *w_hh, *b_ih, *b_hh;
+} cirs_gru_layer;
+
+typedef struct cirs_gru_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    cirs_gru_layer layer[CIRS_GRU_MAX_LAYERS];
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_gru_weights;
+
+typedef struct cirs_gru_state {
+    float* x_hist; /* [B, max_len, D] the input slots (what the backward recomputes from) */
+    float* h;      /* [nlayers, B, D] the carried hidden state of every layer */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_gru_state;
+
+typedef struct cirs_gru_layer_grads {
+    float *w_ih, *w_hh, *b_ih, *b_hh;
+} cirs_gru_layer_grads;
+
+typedef struct cirs_gru_grads { /* same tensors, same order as cirs_gru_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    cirs_gru_layer_grads layer[CIRS_GRU_MAX_LAYERS];
+    float *dec_w, *dec_b;
+} cirs_gru_grads;
+
+/* cirs_tracker_init / cirs_tracker_step for the GRU tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j (NULL: j);
+ * init writes slot 0, h = cell(x_0, 0), len = 1; step appends one position.  Rows with skip != 0 (step) or item < 0 are left untouched: neither
+ * the tracker state nor their row of state_out is written.  state_out row stride = state_stride floats. */
+int cirs_gru_tracker_init(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int32_t* users,
+                          const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_gru_tracker_step(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int64_t* items,
+                          const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                          int64_t state_stride, void* stream);
+
+/* cirs_tracker_backward for the GRU tracker: back-propagation through time, recomputed from the stored slots.  users[B]; act / rew are the
+ * time-major trajectory rows [T,B]; row_env / row_t / offsets / lens describe the buffer rows (env-major, see cirs_ppo_prepare);
+ * dstate [T+1,B,S] = d loss / d obs.  Every gradient tensor is OVERWRITTEN.  No float atomics; every reduction has a fixed order, so two
+ * calls give the same bits.  A workspace smaller than cirs_gru_tracker_backward_workspace_bytes(cfg, n_rows) is refused before any launch. */
+int64_t cirs_gru_tracker_backward_workspace_bytes(const cirs_gru_cfg* cfg, int32_t n_rows);
+int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, const cirs_gru_state* st, const int32_t* users,
+                              const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                              const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                              const cirs_gru_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect with a GRU tracker: env reset, cirs_gru_tracker_init, then per vector step cirs_actor_sample (greedy != 0:
+ * cirs_actor_greedy), the visited bits, cirs_env_step, the forced length and cirs_gru_tracker_step -- the unfused launch sequence of
+ * cirs_rollout_steps_online without its scorer, on the caller's stream, no host synchronisation.  Same trajectory contract: every entry
+ * [t][env] is written (envs that finished earlier: act -1, done 1, rew / ctr 0).  gumbel (nullable; not with greedy): harness-supplied
+ * sampler noise [max_turn][n_env][n_items] as in cirs_rollout_steps_noise.  workspace >= cirs_policy_workspace_bytes(pol_cfg, n_env). */
+int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                             const cirs_gru_cfg* trk_cfg, const cirs_gru_weights* trk_w, cirs_gru_state* trk_st,
+                             const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                             int32_t n_env, const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited,
+                             int32_t force_length, int32_t greedy, const float* gumbel, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),

@@ -1,0 +1,144 @@
+"""The GRU state tracker against the Transformer one at the benchmark shapes:  python tools/probe_gru_tracker.py [--workload c2|c3] [--reps 60]
+
+Three trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU with 1 and with 2
+layers.  Per tracker, alternated inside every repetition so that drift of the machine hits all three alike:
+  step_us        one tracker step alone (one launch, all envs) at positions 1, 15 and 30 -- a device-event pair around the launch
+  collect_ms     one DeviceRollout.collect (what Collector.collect runs on the device): the fused two-launch sequence for the Transformer,
+                 cirs_rollout_collect_gru's unfused sequence for the GRU -- device events around the call, enqueued behind a spin kernel (the host
+                 ahead of the device, as in the training loop); collect_idle_ms: the same from an idle stream (the host's launch rate counts)
+  bwd_adam_ms    the tracker backward + Adam step of one update (the learner's d loss / d obs as upstream gradient) -- device events
+Medians over --reps repetitions after a warm-up, min and max alongside.  One JSON line.
+--trace: no timing, a few collects and backwards per tracker -- the run to put under `rocprofv3 --kernel-trace --stats -- python ...` for kernel times
+(tracing slows the host: never in the same run as the timings above)."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "cirs-codes_amd"))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from cirs_hip.gru_tracker import DeviceGruTracker, gru_param_shapes, init_gru_tracker_params  # noqa: E402
+from cirs_hip.rollout import DeviceRollout  # noqa: E402
+from cirs_hip.tracker import flat_tracker_params  # noqa: E402
+
+
+def gru_engine(wl, layers, device):
+    U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
+    flat, views = flat_tracker_params(gru_param_shapes(U, I, 32, 20, layers), device=device,
+                                      init=init_gru_tracker_params(U, I, seed=2023, nlayers=layers))
+    trk = DeviceGruTracker(dict(views), U, I, B, T, nlayers=layers, device=device)
+    trk.enable_training(flat)
+    return trk
+
+
+def stats(xs):
+    xs = np.asarray(xs, dtype=np.float64)
+    return {"median": round(float(np.median(xs)), 3), "min": round(float(xs.min()), 3), "max": round(float(xs.max()), 3)}
+
+
+def timed(fn, queued=True):
+    """device time of what fn enqueues.  queued: behind a spin kernel, so that the host has enqueued everything before the first event fires --
+    the gaps between the launches are then the device's, not the host's (the state of the training loop, whose host runs an update ahead)"""
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    if queued:
+        torch.cuda._sleep(1000000)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="c3", choices=sorted(bench.WORKLOADS))
+    ap.add_argument("--reps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--trace", action="store_true")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "the probe measures on an MI355X: no CPU fallback"
+    assert args.trace or args.reps >= 50, "at least 50 repetitions"
+    device = torch.device("cuda:0")
+    wl = bench.WORKLOADS[args.workload]
+    U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
+    eng, _ = bench.build_engine(wl, 0, 1, device, dropout=0.0)
+    ln = eng.learner
+    variants = {"transformer_l2": (eng.tracker, eng.rollout)}
+    for layers in (1, 2):
+        trk = gru_engine(wl, layers, device)
+        variants[f"gru_l{layers}"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
+    users = torch.as_tensor(np.random.RandomState(0).randint(0, U, B)).to(device, torch.int32)
+    items = torch.as_tensor(np.random.RandomState(1).randint(0, I, B)).to(device)
+    rews = torch.rand(B, dtype=torch.float64, device=device)
+    state = torch.empty((B, 20), device=device)
+    for trk, _ in variants.values():
+        trk.reserve_backward(B * T)
+
+    def collect(name):
+        trk, ro = variants[name]
+        return ro.collect(users, seed=2023 << 8, rng_base=0)
+
+    def prepare_update(name):
+        """the learner's pass over this tracker's buffer: leaves d loss / d obs in ln.dobs; the policy is restored so that every tracker meets the same one"""
+        trk, ro = variants[name]
+        lens = collect(name).cpu().numpy().astype(np.int32)
+        keep = eng.policy_flat.clone()
+        n = ln.prepare(ro.traj, lens)
+        ln.learn(1024, 2, want_tracker_grad=True)
+        eng.policy_flat.copy_(keep)
+        offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int32)
+        return dict(lens=lens, n=n, offsets=torch.as_tensor(offsets).to(device), lens_d=torch.as_tensor(lens).to(device), dobs=ln.dobs.clone(),
+                    b_env=ln.b_env.clone(), b_t=ln.b_t.clone(), params=trk.flat.clone())
+
+    def bwd_adam(name, u):
+        trk, ro = variants[name]
+        trk.backward(users, ro.traj, u["b_env"], u["b_t"], u["offsets"], u["lens_d"], u["n"], u["dobs"])
+        trk.adam_update()
+
+    def step_at(name, pos):
+        trk, _ = variants[name]
+        trk.len.fill_(pos)
+        return timed(lambda: trk.step(items, rews, out=state, out_stride=20)) * 1e3
+
+    if args.trace:
+        for name in variants:
+            u = prepare_update(name)
+            for _ in range(5):
+                collect(name)
+                bwd_adam(name, u)
+        torch.cuda.synchronize()
+        print(json.dumps({"trace": True, "workload": args.workload, "trackers": list(variants)}), flush=True)
+        return
+    # the update inputs of every tracker: its own collect's buffer (the trajectories differ: different states -> different actions)
+    ups = {name: prepare_update(name) for name in variants}
+    out = {"workload": args.workload, "n_env": B, "n_users": U, "n_items": I, "max_turn": T, "reps": args.reps, "warmup": args.warmup, "trackers": {}}
+    acc = {name: {"step_us": {p: [] for p in (1, 15, 30)}, "collect_ms": [], "collect_idle_ms": [], "bwd_adam_ms": []} for name in variants}
+    for rep in range(args.warmup + args.reps):
+        for name in variants:      # alternated: one measurement of every kind per tracker per repetition
+            trk, ro = variants[name]
+            row = {p: step_at(name, p) for p in (1, 15, 30)}
+            c = timed(lambda: collect(name))
+            ci = timed(lambda: collect(name), queued=False)      # from an idle stream: the host's launch rate counts
+            # the collect overwrote the slots with the same episodes (same users, seed, parameters restored below): the stored update inputs still describe them
+            b = timed(lambda: bwd_adam(name, ups[name]))
+            trk.flat.copy_(ups[name]["params"])      # undo the Adam step: every repetition runs the same episodes
+            if rep >= args.warmup:
+                for p in row:
+                    acc[name]["step_us"][p].append(row[p])
+                acc[name]["collect_ms"].append(c)
+                acc[name]["collect_idle_ms"].append(ci)
+                acc[name]["bwd_adam_ms"].append(b)
+    for name in variants:
+        a = acc[name]
+        out["trackers"][name] = {"rows": int(ups[name]["n"]), "mean_len": round(float(ups[name]["lens"].mean()), 2),
+                                 "step_us": {str(p): stats(v) for p, v in a["step_us"].items()}, "collect_ms": stats(a["collect_ms"]), "collect_idle_ms": stats(a["collect_idle_ms"]),
+                                 "bwd_adam_ms": stats(a["bwd_adam_ms"])}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
