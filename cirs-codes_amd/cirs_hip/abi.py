@@ -83,6 +83,27 @@ class GruState(C.Structure):        # cirs_gru_state
     _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("len", C.c_void_p)]
 
 
+LSTM_MAX_LAYERS = 2
+
+
+class LstmCfg(C.Structure):         # cirs_lstm_cfg
+    _fields_ = list(GruCfg._fields_)
+
+
+class LstmLayer(C.Structure):       # cirs_lstm_layer / cirs_lstm_layer_grads
+    _fields_ = [(k, C.c_void_p) for k in ("w_ih", "w_hh", "b_ih", "b_hh")]
+
+
+class LstmWeights(C.Structure):     # cirs_lstm_weights / cirs_lstm_grads (same layout)
+    _fields_ = [("emb_user", C.c_void_p), ("emb_item", C.c_void_p), ("ffn_user_w", C.c_void_p), ("ffn_user_b", C.c_void_p),
+                ("gate_w", C.c_void_p), ("gate_b", C.c_void_p), ("layer", LstmLayer * LSTM_MAX_LAYERS), ("dec_w", C.c_void_p),
+                ("dec_b", C.c_void_p)]
+
+
+class LstmState(C.Structure):       # cirs_lstm_state
+    _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("c", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -357,6 +378,14 @@ SIGNATURES = {
     "cirs_rollout_collect_gru": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(GruCfg), C.POINTER(GruWeights),
                                            C.POINTER(GruState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                            C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_lstm_tracker_init": (C.c_int, [C.POINTER(LstmCfg), C.POINTER(LstmWeights), C.POINTER(LstmState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_lstm_tracker_step": (C.c_int, [C.POINTER(LstmCfg), C.POINTER(LstmWeights), C.POINTER(LstmState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_lstm_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(LstmCfg), C.c_int32]),
+    "cirs_lstm_tracker_backward": (C.c_int, [C.POINTER(LstmCfg), C.POINTER(LstmWeights), C.POINTER(LstmState), _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                             C.POINTER(LstmWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_lstm": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(LstmCfg), C.POINTER(LstmWeights),
+                                            C.POINTER(LstmState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                            C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

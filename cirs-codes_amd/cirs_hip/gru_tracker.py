@@ -58,43 +58,57 @@ def init_gru_tracker_params(n_users, n_items, seed=2021, dim_model=32, dim_state
     return {k: p[k] for k in gru_param_shapes(n_users, n_items, dim_model, dim_state, nlayers)}
 
 
-def weights_struct(params: Dict[str, torch.Tensor], nlayers: int):
-    """cirs_gru_weights (or cirs_gru_grads: same layout) from tensors keyed by state_dict names (fp32, contiguous, device)."""
-    w = abi.GruWeights()
+def weights_struct(params: Dict[str, torch.Tensor], nlayers: int, struct=abi.GruWeights, layer_fields=None):
+    """cirs_gru_weights (or cirs_gru_grads: same layout; `struct` / `layer_fields`: another cell's) from tensors keyed by state_dict names
+    (fp32, contiguous, device)."""
+    w = struct()
     for f, name in TOP_FIELDS:
         t = params[name]
         assert t.dtype == torch.float32 and t.is_contiguous(), name
         setattr(w, f, t.data_ptr())
     for l in range(nlayers):
-        for f, name in LAYER_FIELDS:
+        for f, name in layer_fields or LAYER_FIELDS:
             t = params[name.format(l)]
             assert t.dtype == torch.float32 and t.is_contiguous(), name
             setattr(w.layer[l], f, t.data_ptr())
     return w
 
 
-class DeviceGruTracker:
-    """Recurrent tracker state for B envs.  `params` maps state_dict names (gru_param_shapes) to device tensors."""
+class DeviceRecurrentTracker:
+    """Recurrent tracker state for B envs: what the GRU and the LSTM engine share.  A subclass names its cell: the ctypes structs, the
+    layers' state_dict names, the prefix of its entry points, its shape check, and the carried tensors next to h (CARRY)."""
+    CFG = WEIGHTS = STATE = LAYER_FIELDS = ENTRY = check_shape = None
+    CARRY = ("h",)
 
     def __init__(self, params: Dict[str, torch.Tensor], n_users, n_items, n_env, max_turn, *, dim_model=32, dim_state=20, nlayers=1,
                  device="cuda"):
-        check_gru_shape(dim_model, dim_state, nlayers)
+        type(self).check_shape(dim_model, dim_state, nlayers)
         self.device = torch.device(device)
-        self.cfg = abi.GruCfg(n_users=n_users, n_items=n_items, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
-                              max_len=max_turn + 1, n_env=n_env)
+        self.cfg = self.CFG(n_users=n_users, n_items=n_items, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
+                            max_len=max_turn + 1, n_env=n_env)
         self.params = params
         self.nlayers = nlayers
-        self.w = weights_struct(params, nlayers)
+        self.w = self._weights(params)
         L, B, D = max_turn + 1, n_env, dim_model
         self.x_hist = torch.zeros((B, L, D), dtype=torch.float32, device=self.device)
-        self.h = torch.zeros((nlayers, B, D), dtype=torch.float32, device=self.device)
+        for k in self.CARRY:
+            setattr(self, k, torch.zeros((nlayers, B, D), dtype=torch.float32, device=self.device))
         self.len = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.st = abi.GruState(x_hist=self.x_hist.data_ptr(), h=self.h.data_ptr(), len=self.len.data_ptr())
+        self.st = self._state(self.x_hist)
         self._bws = None
         self._lib = abi.lib()
         self.dim_state = dim_state
 
-    # nn.GRU has dropout between layers only, and that one is not built: nothing to set
+    def _weights(self, tensors):
+        return weights_struct(tensors, self.nlayers, self.WEIGHTS, self.LAYER_FIELDS)
+
+    def _state(self, x_hist):
+        return self.STATE(x_hist=x_hist.data_ptr(), len=self.len.data_ptr(), **{k: getattr(self, k).data_ptr() for k in self.CARRY})
+
+    def _entry(self, suffix):
+        return getattr(self._lib, self.ENTRY + suffix), self.ENTRY + suffix
+
+    # nn.GRU / nn.LSTM have dropout between layers only, and that one is not built: nothing to set
     def set_dropout(self, p: float):
         pass
 
@@ -102,7 +116,7 @@ class DeviceGruTracker:
         pass
 
     def refresh_weights(self):
-        self.w = weights_struct(self.params, self.nlayers)
+        self.w = self._weights(self.params)
 
     # ---- training side ------------------------------------------------------------------------------------------
     def enable_training(self, flat_params: torch.Tensor, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
@@ -111,7 +125,7 @@ class DeviceGruTracker:
         self.flat = flat_params
         self.flat_grad, self.grad_views = flat_tracker_params(shapes, device=self.device)
         assert self.flat_grad.numel() == flat_params.numel()
-        self.g = weights_struct(self.grad_views, self.nlayers)
+        self.g = self._weights(self.grad_views)
         self.adam_m = torch.zeros_like(flat_params)
         self.adam_v = torch.zeros_like(flat_params)
         self.adam_steps = 0
@@ -119,7 +133,7 @@ class DeviceGruTracker:
         self._bws = None
 
     def _workspace(self, cfg, n_rows):
-        need = self._lib.cirs_gru_tracker_backward_workspace_bytes(C.byref(cfg), n_rows)
+        need = self._entry("_backward_workspace_bytes")[0](C.byref(cfg), n_rows)
         if self._bws is None or self._bws.numel() < need:
             self._bws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._bws
@@ -131,14 +145,15 @@ class DeviceGruTracker:
         users = users.to(self.device, torch.int32).contiguous()
         cfg, st = self.cfg, self.st
         if x_hist is not None:
-            cfg = abi.GruCfg.from_buffer_copy(self.cfg)
+            cfg = self.CFG.from_buffer_copy(self.cfg)
             cfg.n_env = x_hist.shape[0]
-            st = abi.GruState(x_hist=x_hist.data_ptr(), h=self.h.data_ptr(), len=self.len.data_ptr())
+            st = self._state(x_hist)
         ws = self._workspace(cfg, n_rows)
-        abi.check(self._lib.cirs_gru_tracker_backward(
+        fn, name = self._entry("_backward")
+        abi.check(fn(
             C.byref(cfg), C.byref(self.w), C.byref(st), users.data_ptr(), traj.act.data_ptr(), traj.rew.data_ptr(), row_env.data_ptr(),
             row_t.data_ptr(), offsets.data_ptr(), lens.data_ptr(), n_rows, dstate.data_ptr(), C.byref(self.g), ws.data_ptr(), ws.numel(),
-            self._stream()), "cirs_gru_tracker_backward")
+            self._stream()), name)
 
     def reserve_backward(self, max_rows):
         self._workspace(self.cfg, max_rows)
@@ -164,8 +179,9 @@ class DeviceGruTracker:
         if out is None:
             out = torch.empty((n, self.dim_state), dtype=torch.float32, device=self.device)
             out_stride = self.dim_state
-        abi.check(self._lib.cirs_gru_tracker_init(C.byref(self.cfg), C.byref(self.w), C.byref(self.st), users.data_ptr(), abi.ptr(ids), n,
-                                                  out.data_ptr(), out_stride, self._stream()), "cirs_gru_tracker_init")
+        fn, name = self._entry("_init")
+        abi.check(fn(C.byref(self.cfg), C.byref(self.w), C.byref(self.st), users.data_ptr(), abi.ptr(ids), n, out.data_ptr(), out_stride,
+                     self._stream()), name)
         return out
 
     def step(self, items, rew, env_ids=None, skip=None, out=None, out_stride=None):
@@ -176,7 +192,13 @@ class DeviceGruTracker:
         if out is None:
             out = torch.empty((n, self.dim_state), dtype=torch.float32, device=self.device)
             out_stride = self.dim_state
-        abi.check(self._lib.cirs_gru_tracker_step(C.byref(self.cfg), C.byref(self.w), C.byref(self.st), items.data_ptr(), rew.data_ptr(),
-                                                  abi.ptr(ids), abi.ptr(skip), n, out.data_ptr(), out_stride, self._stream()),
-                  "cirs_gru_tracker_step")
+        fn, name = self._entry("_step")
+        abi.check(fn(C.byref(self.cfg), C.byref(self.w), C.byref(self.st), items.data_ptr(), rew.data_ptr(), abi.ptr(ids), abi.ptr(skip), n,
+                     out.data_ptr(), out_stride, self._stream()), name)
         return out
+
+
+class DeviceGruTracker(DeviceRecurrentTracker):
+    """`params` maps state_dict names (gru_param_shapes) to device tensors."""
+    CFG, WEIGHTS, STATE, LAYER_FIELDS, ENTRY, check_shape = abi.GruCfg, abi.GruWeights, abi.GruState, LAYER_FIELDS, "cirs_gru_tracker", check_gru_shape
+    COLLECT, NAME = "cirs_rollout_collect_gru", "GRU"

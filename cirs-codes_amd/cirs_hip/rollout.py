@@ -13,7 +13,7 @@ import torch
 from . import abi
 from .env import DeviceEnv
 from .policy import DevicePolicy
-from .gru_tracker import DeviceGruTracker
+from .gru_tracker import DeviceRecurrentTracker
 from .tracker import DeviceTracker
 
 
@@ -73,10 +73,10 @@ class DeviceRollout:
                  force_length=0, online: Optional[OnlineReward] = None):
         assert env.n_env == tracker.cfg.n_env
         self.env, self.tracker, self.policy = env, tracker, policy
-        # the recurrent tracker has a collect of its own (cirs_rollout_collect_gru: the unfused launch sequence)
-        self.gru = isinstance(tracker, DeviceGruTracker)
+        # a recurrent tracker has a collect of its own (cirs_rollout_collect_gru / _lstm: the unfused launch sequence)
+        self.gru = isinstance(tracker, DeviceRecurrentTracker)
         if self.gru and online is not None:
-            raise NotImplementedError("the online-reward rollout is not built for the GRU tracker (out of scope: precompute the reward table)")
+            raise NotImplementedError(f"the online-reward rollout is not built for the {tracker.NAME} tracker (out of scope: precompute the reward table)")
         self.device = env.device
         self.traj = Trajectory(env.n_env, env.max_turn, tracker.dim_state, self.device)
         self.remove_recommended_ids = remove_recommended_ids
@@ -111,9 +111,9 @@ class DeviceRollout:
             raise NotImplementedError("the online-reward rollout has no greedy mode (out of scope: precompute the reward table)")
 
     def _collect_gru(self, users, seed, rng_base, sync_every, gumbel, greedy):
-        """collect() with a DeviceGruTracker: reset_env + every vector step from one call, no host synchronisation."""
+        """collect() with a recurrent tracker (DeviceGruTracker, DeviceLstmTracker): reset_env + every vector step from one call, no host synchronisation."""
         if sync_every is not None:
-            raise NotImplementedError("sync_every is not built for the GRU tracker: its collect is one call over all max_turn steps")
+            raise NotImplementedError(f"sync_every is not built for the {self.tracker.NAME} tracker: its collect is one call over all max_turn steps")
         users_d = users.to(self.device, torch.int32).contiguous()
         if self.visited is not None:
             self.visited.zero_()
@@ -122,16 +122,16 @@ class DeviceRollout:
             assert tuple(gumbel.shape) == (self.env.max_turn, self.env.n_env, self.policy.n_items)
         ws = self.policy.workspace(self.env.n_env)
         self._users_keepalive, self._gumbel_keep = users_d, gumbel
-        abi.check(self._lib.cirs_rollout_collect_gru(
+        abi.check(getattr(self._lib, self.tracker.COLLECT)(
             C.byref(self.env.cfg), C.byref(self.env._tab), C.byref(self.env._st), C.byref(self.tracker.cfg), C.byref(self.tracker.w),
             C.byref(self.tracker.st), C.byref(self.policy.cfg), C.byref(self.policy.w), C.byref(self.traj.struct), self.env.n_env,
             users_d.data_ptr(), seed, rng_base, abi.ptr(self.visited), self.force_length, int(bool(greedy)), abi.ptr(gumbel), ws.data_ptr(),
-            ws.numel(), self._stream()), "cirs_rollout_collect_gru")
+            ws.numel(), self._stream()), self.tracker.COLLECT)
         return self.env.turn.clone()
 
     def run_steps(self, t_begin, t_end, seed, rng_base, gumbel=None, greedy=False):
         if self.gru:
-            raise NotImplementedError("run_steps is not built for the GRU tracker: use collect()")
+            raise NotImplementedError(f"run_steps is not built for the {self.tracker.NAME} tracker: use collect()")
         ws = self.policy.workspace(self.env.n_env)
         if greedy:      # the arg-max action (deterministic_eval in eval mode): seed / rng_base are not used
             self._check_greedy(gumbel)

@@ -64,11 +64,12 @@ class Collector:
                  dropout_redraw=False):
         assert hasattr(env, "__len__"), "pass a tianshou.env.DummyVectorEnv"
         assert preprocess_fn is not None and hasattr(preprocess_fn, "__self__"), \
-            "preprocess_fn must be StateTrackerTransformer.build_state or StateTrackerGRU.build_state (CIRS-RL-kuaishou.py:291)"
+            "preprocess_fn must be the build_state of StateTrackerTransformer, StateTrackerGRU or StateTrackerLSTM (CIRS-RL-kuaishou.py:291)"
         assert not exploration_noise
-        from core.state_tracker import StateTrackerGRU
-        if dropout_redraw and isinstance(preprocess_fn.__self__, StateTrackerGRU):
-            raise ValueError("dropout_redraw=True is not built for StateTrackerGRU: the GRU tracker has no dropout to redraw")
+        from core.state_tracker import _RecurrentStateTracker
+        if dropout_redraw and isinstance(preprocess_fn.__self__, _RecurrentStateTracker):
+            cell = preprocess_fn.__self__.CELL
+            raise ValueError(f"dropout_redraw=True is not built for StateTracker{cell}: the {cell} tracker has no dropout to redraw")
         self.env, self.env_num = env, len(env)
         self.policy = policy
         self.preprocess_fn = preprocess_fn

@@ -1,16 +1,18 @@
-"""StateTrackerTransformer (reference core/state_tracker.py:128-250) and StateTrackerGRU (:282-289, declared empty there) on the
-device engines.
+"""StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
+there) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
-Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's for the recurrence) but live in ONE flat device
-buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells) and the
-gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward (no autograd graph)."""
+Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
+buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
+LSTM cells) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward (no autograd
+graph)."""
 import numpy as np
 import torch
 from torch import nn
 
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
+from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
 from cirs_hip.tracker import DeviceTracker, flat_tracker_params, tracker_param_shapes
 
 
@@ -150,20 +152,21 @@ class StateTrackerTransformer(_DeviceStateTracker):
                              dim_state=self.dim_state, nhead=self.nhead, d_hid=self.d_hid, nlayers=self.nlayers, device=self.device)
 
 
-class StateTrackerGRU(_DeviceStateTracker):
-    """The recurrent tracker the reference announces (core/state_tracker.py:282-289: an empty class): the Transformer tracker's input
-    slots, torch.nn.GRU(dim_model, dim_model, nlayers) with h_{-1} = 0 over them, the same decoder (StateTrackerGRU).
-    It takes StateTrackerTransformer's constructor keywords, so a script changes the class name only; nhead and d_hid are accepted and
-    unused.  dropout: nn.GRU applies it between layers only -- without effect at nlayers == 1 (as in torch); at nlayers == 2 it is
-    not built and training mode with dropout > 0 raises."""
+class _RecurrentStateTracker(_DeviceStateTracker):
+    """What StateTrackerGRU and StateTrackerLSTM share: StateTrackerTransformer's constructor keywords (a script changes the class name
+    only; nhead and d_hid are accepted and unused), the refusals, the engine.  A subclass names its cell (CELL), its device engine and
+    the three functions of its cirs_hip module.  dropout: torch applies it between the layers only -- without effect at nlayers == 1
+    (as in torch); at nlayers == 2 it is not built and training mode with dropout > 0 raises."""
+    CELL = ENGINE = check_shape = param_shapes = init_params = None
 
     def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
                  dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
                  nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100):
         super().__init__()
+        cls = type(self)
         if dataset != "KuaishouEnv-v0":
-            raise NotImplementedError("StateTrackerGRU serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
-        check_gru_shape(dim_model, dim_state, nlayers)
+            raise NotImplementedError(f"StateTracker{self.CELL} serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
+        cls.check_shape(dim_model, dim_state, nlayers)
         self.dropout_p = float(dropout)
         self.nlayers = int(nlayers)
         self._check_dropout(self.training)
@@ -171,22 +174,36 @@ class StateTrackerGRU(_DeviceStateTracker):
         self.dim_model, self.dim_state = dim_model, dim_state
         self.MAX_TURN = MAX_TURN + 1
         self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
-        init = init_gru_tracker_params(self.n_users, self.n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
-                                       init_std=init_std)
-        self._setup(gru_param_shapes(self.n_users, self.n_items, dim_model, dim_state, nlayers), init, seed)
+        init = cls.init_params(self.n_users, self.n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
+                               init_std=init_std)
+        self._setup(cls.param_shapes(self.n_users, self.n_items, dim_model, dim_state, nlayers), init, seed)
 
     def _check_dropout(self, training):
         if training and self.nlayers > 1 and self.dropout_p > 0:
-            raise ValueError("StateTrackerGRU: dropout between GRU layers is not built (nlayers == 2 with dropout > 0 in training mode); "
-                             "use dropout=0.0 or call .eval()")
+            raise ValueError(f"StateTracker{self.CELL}: dropout between {self.CELL} layers is not built (nlayers == 2 with dropout > 0 in "
+                             "training mode); use dropout=0.0 or call .eval()")
 
     def _engine_dropout(self, training):
         return 0.0
 
     def _make_engine(self, n_env):
-        return DeviceGruTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
-                                dim_state=self.dim_state, nlayers=self.nlayers, device=self.device)
+        return self.ENGINE(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
+                           dim_state=self.dim_state, nlayers=self.nlayers, device=self.device)
 
     def train(self, mode: bool = True):
         self._check_dropout(mode)
         return super().train(mode)
+
+
+class StateTrackerGRU(_RecurrentStateTracker):
+    """The recurrent tracker the reference announces (core/state_tracker.py:282-289: an empty class): the Transformer tracker's input
+    slots, torch.nn.GRU(dim_model, dim_model, nlayers) with h_{-1} = 0 over them, the same decoder."""
+    CELL, ENGINE = "GRU", DeviceGruTracker
+    check_shape, param_shapes, init_params = check_gru_shape, gru_param_shapes, init_gru_tracker_params
+
+
+class StateTrackerLSTM(_RecurrentStateTracker):
+    """The second recurrent tracker the reference announces and leaves empty: the same input slots, torch.nn.LSTM(dim_model, dim_model,
+    nlayers) with h_{-1} = c_{-1} = 0 over them, the same decoder."""
+    CELL, ENGINE = "LSTM", DeviceLstmTracker
+    check_shape, param_shapes, init_params = check_lstm_shape, lstm_param_shapes, init_lstm_tracker_params

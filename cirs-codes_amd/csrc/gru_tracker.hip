@@ -22,7 +22,7 @@
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <utility>
-#include "tracker_rows.h"
+#include "recurrent.h"
 
 namespace cirs {
 
@@ -30,8 +30,6 @@ constexpr int gG = 3 * tD;                                 // gate rows of a cel
 constexpr int kGruLds = tD + 65;                           // LDS stride of one k of a staged [k][96] matrix: 97 (odd: conflict-free both ways)
 constexpr int kGruMat = tD * kGruLds;                      // 3104 floats; = 32 mod 64: the two matrices of a layer start half the banks apart
 constexpr int kGruLayerFloats = 2 * kGruMat + 2 * gG;      // W_ih^T | W_hh^T | b_ih | b_hh = 6400 floats = 25.6 KB
-
-__device__ __forceinline__ float gru_sigmoid(float a) { return 1.0f / (1.0f + expf(-a)); }
 
 __global__ __launch_bounds__(256) void gru_step_kernel(cirs_gru_cfg cfg, cirs_gru_weights w, cirs_gru_state st, const int32_t* __restrict__ users,
                                                        const int64_t* __restrict__ items, const double* __restrict__ rew,
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(256) void gru_step_kernel(cirs_gru_cfg cfg, cirs_gr
             float acc = __builtin_fmaf(gw[0], r, w.gate_b[d]);
 #pragma unroll
             for (int k = 0; k < tD; ++k) acc = __builtin_fmaf(gw[1 + k], vec[k], acc);
-            x = gru_sigmoid(acc) * a;
+            x = cell_sigmoid(acc) * a;
         }
         __builtin_amdgcn_wave_barrier();
         if (lane < tD) st.x_hist[((size_t)e * L + pos) * tD + d] = x;
@@ -110,7 +108,7 @@ __global__ __launch_bounds__(256) void gru_step_kernel(cirs_gru_cfg cfg, cirs_gr
             const float o0 = __shfl_xor(g0, 32, CIRS_WAVE), o1 = __shfl_xor(g1, 32, CIRS_WAVE), o2 = __shfl_xor(g2, 32, CIRS_WAVE);
             const float gi_r = half ? o0 : g0, gh_r = half ? g0 : o0, gi_z = half ? o1 : g1, gh_z = half ? g1 : o1;
             const float gi_n = half ? o2 : g2, gh_n = half ? g2 : o2;
-            const float r = gru_sigmoid(gi_r + gh_r), z = gru_sigmoid(gi_z + gh_z);
+            const float r = cell_sigmoid(gi_r + gh_r), z = cell_sigmoid(gi_z + gh_z);
             const float nn = tanhf(gi_n + r * gh_n);
             const float hnew = (1.0f - z) * nn + z * hprev;
             __builtin_amdgcn_wave_barrier();
@@ -133,14 +131,6 @@ __global__ __launch_bounds__(256) void gru_step_kernel(cirs_gru_cfg cfg, cirs_gr
 }
 
 // ---- BPTT ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gru_gather_x(const float* __restrict__ x_hist, const int32_t* __restrict__ row_env, const int32_t* __restrict__ row_t,
-                                                    int R, int L, float* __restrict__ X) {
-    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    if (i >= (long)R * tD) return;
-    const int r = (int)(i >> 5), k = (int)(i & 31);
-    X[i] = x_hist[((size_t)row_env[r] * L + row_t[r]) * tD + k];
-}
-
 struct GruRows { float *r, *z, *n, *hn, *h, *hp; };      // [R, 32] each: the gates, W_hn h + b_hn, the new and the previous h of every row
 
 // (B) one wavefront per env.  Lane (half, d): half 0 forms row d of W_hr h and the first 16 terms of row d of W_hz h, half 1 row d of W_hn h and the other 16.
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(64) void gru_seq_fwd(const float* __restrict__ Gi, 
         const float oacc = __shfl_xor(acc, 32, CIRS_WAVE), oc = __shfl_xor(c, 32, CIRS_WAVE);
         const float gh_r = half ? oacc : acc, gh_n = half ? acc : oacc;
         const float gh_z = (half ? oc : c) + (half ? c : oc);
-        const float r = gru_sigmoid(gi_r + gh_r), z = gru_sigmoid(gi_z + gh_z);
+        const float r = cell_sigmoid(gi_r + gh_r), z = cell_sigmoid(gi_z + gh_z);
         const float nn = tanhf(gi_n + r * gh_n);
         const float hnew = (1.0f - z) * nn + z * h;
         __builtin_amdgcn_wave_barrier();
@@ -221,12 +211,9 @@ __global__ __launch_bounds__(64) void gru_seq_bwd(const float* __restrict__ dH, 
     }
 }
 
-struct GruScratch {
+struct GruScratch : SlotScratch {
     float *X, *G, *dHa, *dHb, *dGi, *dGh, *Gi;
     GruRows rows[CIRS_GRU_MAX_LAYERS];
-    float *DU, *EU, *DPRE, *CU, *CI, *GIN, *partial;
-    int32_t *key_user, *key_item;
-    void* sort;
 };
 
 static size_t gru_partial_floats(const cirs_gru_cfg* cfg, long R) {
@@ -255,18 +242,7 @@ static GruScratch carve_gru(void* ws, const cirs_gru_cfg* cfg, long R, size_t* t
     return s;
 }
 
-static int validate_gru(const cirs_gru_cfg* cfg, const cirs_gru_weights* w) {
-    CIRS_REQUIRE(cfg && w, "gru tracker cfg/weights null");
-    if (cfg->dim_model != tD) return fail(CIRS_E_UNSUPPORTED, "gru tracker: this build supports dim_model == 32");
-    if (cfg->nlayers < 1 || cfg->nlayers > CIRS_GRU_MAX_LAYERS) return fail(CIRS_E_UNSUPPORTED, "gru tracker: nlayers must be 1 or 2");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= 32, "gru tracker: dim_state must be in 1..32");
-    CIRS_REQUIRE(cfg->max_len >= 1 && cfg->max_len <= 4096, "gru tracker: max_len out of range");
-    CIRS_REQUIRE(cfg->n_env >= 1 && cfg->n_users >= 1 && cfg->n_items >= 1, "gru tracker: n_env / n_users / n_items must be positive");
-    CIRS_REQUIRE(w->emb_user && w->emb_item && w->ffn_user_w && w->ffn_user_b && w->gate_w && w->gate_b && w->dec_w && w->dec_b, "gru tracker weight pointer null");
-    for (int l = 0; l < cfg->nlayers; ++l)
-        CIRS_REQUIRE(w->layer[l].w_ih && w->layer[l].w_hh && w->layer[l].b_ih && w->layer[l].b_hh, "gru tracker layer weight pointer null");
-    return CIRS_OK;
-}
+static int validate_gru(const cirs_gru_cfg* cfg, const cirs_gru_weights* w) { return validate_recurrent(cfg, w, CIRS_GRU_MAX_LAYERS, "gru tracker"); }
 
 static int launch_gru_step(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int32_t* users, const int64_t* items,
                            const double* rew, const int32_t* env_ids, const uint8_t* skip, int n, float* state_out, long state_stride, hipStream_t s) {
@@ -328,10 +304,7 @@ extern "C" int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru
     if (int rc = validate_gru(cfg, w)) return rc;
     CIRS_REQUIRE(st && st->x_hist && users && act && rew && row_env && row_t && offsets && lens && dstate && grads && workspace, "null argument");
     CIRS_REQUIRE(n_rows > 0, "n_rows must be positive");
-    CIRS_REQUIRE(grads->emb_user && grads->emb_item && grads->ffn_user_w && grads->ffn_user_b && grads->gate_w && grads->gate_b && grads->dec_w && grads->dec_b,
-                 "gru tracker gradient pointer null");
-    for (int l = 0; l < cfg->nlayers; ++l)
-        CIRS_REQUIRE(grads->layer[l].w_ih && grads->layer[l].w_hh && grads->layer[l].b_ih && grads->layer[l].b_hh, "gru tracker layer gradient pointer null");
+    if (int rc = validate_recurrent_grads(cfg, grads, "gru tracker")) return rc;
     CIRS_REQUIRE(workspace_bytes >= cirs_gru_tracker_backward_workspace_bytes(cfg, n_rows), "workspace too small");
     CIRS_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -340,7 +313,7 @@ extern "C" int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru
     GruScratch sc = carve_gru(workspace, cfg, R, &total);
     auto g1 = [&](long n) { return dim3(cdiv(n, 256)); };
     // ---- forward recompute ----
-    hipLaunchKernelGGL(gru_gather_x, g1((long)R * tD), dim3(256), 0, s, (const float*)st->x_hist, row_env, row_t, R, L, sc.X);
+    hipLaunchKernelGGL(gather_x, g1((long)R * tD), dim3(256), 0, s, (const float*)st->x_hist, row_env, row_t, R, L, sc.X);
     for (int l = 0; l < nl; ++l) {
         const float* in = l == 0 ? sc.X : sc.rows[l - 1].h;
         launch_rows_gemm(true, in, tD, w->layer[l].w_ih, tD, w->layer[l].b_ih, R, tD, gG, 0, nullptr, 0, sc.Gi, gG, s);
@@ -364,20 +337,5 @@ extern "C" int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru
         std::swap(dH, dX);
     }
     CIRS_CHECK_LAUNCH("gru tracker backward layers");
-    // ---- input slots + embeddings: the Transformer tracker's kernels with input scale 1 ----
-    cirs_tracker_weights tw{};
-    tw.emb_user = w->emb_user; tw.emb_item = w->emb_item; tw.ffn_user_w = w->ffn_user_w; tw.ffn_user_b = w->ffn_user_b; tw.gate_w = w->gate_w; tw.gate_b = w->gate_b;
-    const int slot_rpw = R >= (1 << 17) ? 8 : 1;
-    hipLaunchKernelGGL(slot_bwd, dim3(cdiv(R, 4 * slot_rpw)), dim3(256), 0, s, tw, (const float*)dH, users, act, rew, row_env, row_t, R, B, sc.DU, sc.EU, sc.DPRE,
-                       sc.GIN, sc.CU, sc.CI, sc.key_user, sc.key_item, sc.CI + (size_t)R * tD, slot_rpw, 1.0f);
-    if (int rc = emb_scatter_merged(sc.key_item, users, lens, sc.CI, R, B, cfg->n_items, cfg->n_users, grads->emb_item, grads->emb_user, sc.sort,
-                                    emb_sort_bytes(R + B), s))
-        return rc;
-    DwBatch bt{};
-    dw_batch_add(bt, dwl, sc.DU, tD, sc.EU, tD, R, tD, tD, grads->ffn_user_w, grads->ffn_user_b, 0, sc.partial);
-    dw_batch_add(bt, dwl, sc.DPRE, tD, sc.GIN, tD + 1, R, tD, tD + 1, grads->gate_w, grads->gate_b, 0, sc.partial);
-    dw_batch_launch(bt, R, s);
-    launch_dw_list_final(dwl, R, sc.partial, s);
-    CIRS_CHECK_LAUNCH("gru tracker backward slots");
-    return CIRS_OK;
+    return recurrent_slots_backward(cfg, w, grads, dH, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

@@ -119,18 +119,22 @@ extern "C" int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const ci
                         nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, users, true);
 }
 
-// cirs_rollout_collect with a GRU tracker (gru_tracker.hip): the unfused sequence of rollout_impl's online-reward branch without the scorer, built from
-// the public entry points -- about five launches per vector step against the fused Transformer collect's two (StateTrackerGRU).
-extern "C" int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
-                                        const cirs_gru_cfg* trk_cfg, const cirs_gru_weights* trk_w, cirs_gru_state* trk_st,
-                                        const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
-                                        const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
-                                        int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
-    using namespace cirs;
-    CIRS_REQUIRE(env_cfg && env_tab && env_st && trk_cfg && trk_w && trk_st && pol_cfg && pol_w && traj && users && workspace && n_env > 0,
-                 "cirs_rollout_collect_gru: null argument");
-    CIRS_REQUIRE(env_tab->pred_online == nullptr, "gru rollout: the online-reward loop is not built for the GRU tracker (tables with pred_online are refused)");
-    CIRS_REQUIRE(!(greedy && gumbel), "gru rollout: greedy draws no noise, it cannot be combined with gumbel");
+// cirs_rollout_collect with a recurrent tracker (gru_tracker.hip, lstm_tracker.hip): the unfused sequence of rollout_impl's online-reward branch without the
+// scorer, built from the public entry points -- about five launches per vector step against the fused Transformer collect's two.  One loop
+// for both trackers: `init` / `step` are the tracker's entry points, `what` names it in the messages.
+namespace cirs {
+template <class Cfg, class Weights, class State>
+static int collect_recurrent(const char* what, int (*init)(const Cfg*, const Weights*, State*, const int32_t*, const int32_t*, int32_t, float*, int64_t, void*),
+                             int (*step)(const Cfg*, const Weights*, State*, const int64_t*, const double*, const int32_t*, const uint8_t*, int32_t, float*,
+                                         int64_t, void*),
+                             const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st, const Cfg* trk_cfg, const Weights* trk_w,
+                             State* trk_st, const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                             const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length, int32_t greedy,
+                             const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    const std::string p = std::string(what) + " rollout: ";
+    CIRS_REQUIRE(env_cfg && env_tab && env_st && trk_cfg && trk_w && trk_st && pol_cfg && pol_w && traj && users && workspace && n_env > 0, p + "null argument");
+    CIRS_REQUIRE(env_tab->pred_online == nullptr, p + "the online-reward loop is not built for this tracker (tables with pred_online are refused)");
+    CIRS_REQUIRE(!(greedy && gumbel), p + "greedy draws no noise, it cannot be combined with gumbel");
     CIRS_REQUIRE(traj->obs && traj->act && traj->rew && traj->done && traj->logp && traj->value && traj->ctr, "trajectory pointer null");
     CIRS_REQUIRE(env_st->user && env_st->turn && env_st->done && env_st->hist_action && env_st->cum_reward, "env state has null field");
     CIRS_REQUIRE(trk_cfg->n_env == n_env, "tracker n_env mismatch");
@@ -141,7 +145,7 @@ extern "C" int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_
     const long B = n_env, S = trk_cfg->dim_state;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = cirs_env_reset(env_cfg, env_st, users, nullptr, n_env, nullptr, stream)) return rc;
-    if (int rc = cirs_gru_tracker_init(trk_cfg, trk_w, trk_st, users, nullptr, n_env, traj->obs, S, stream)) return rc;
+    if (int rc = init(trk_cfg, trk_w, trk_st, users, nullptr, n_env, traj->obs, S, stream)) return rc;
     for (int t = 0; t < env_cfg->max_turn; ++t) {
         float* obs_t = traj->obs + (size_t)t * B * S;
         float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
@@ -170,9 +174,28 @@ extern "C" int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_
             CIRS_CHECK_LAUNCH("force_done_kernel");
         }
         // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
-        if (int rc = cirs_gru_tracker_step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream)) return rc;
+        if (int rc = step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream)) return rc;
     }
     return CIRS_OK;
+}
+}  // namespace cirs
+
+extern "C" int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                        const cirs_gru_cfg* trk_cfg, const cirs_gru_weights* trk_w, cirs_gru_state* trk_st,
+                                        const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                        const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                        int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    return cirs::collect_recurrent("gru", cirs_gru_tracker_init, cirs_gru_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w, traj,
+                                   n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cirs_rollout_collect_lstm(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                         const cirs_lstm_cfg* trk_cfg, const cirs_lstm_weights* trk_w, cirs_lstm_state* trk_st,
+                                         const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                         const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                         int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    return cirs::collect_recurrent("lstm", cirs_lstm_tracker_init, cirs_lstm_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w, traj,
+                                   n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cirs_rollout_steps(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,

@@ -680,6 +680,91 @@ int cirs_rollout_collect_gru(const cirs_env_cfg* env_cfg, const cirs_env_tables*
                              int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, recurrent: StateTrackerLSTM (csrc/lstm_tracker.hip)
+ * The reference declares the class and leaves it empty (core/state_tracker.py:282-289); the model is defined here:
+ *   inputs  the GRU tracker's slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *           no sqrt(D) scale, no positional encoding
+ *   cell    torch.nn.LSTM(input_size = D, hidden_size = D, num_layers = nlayers), h_{-1} = c_{-1} = 0, gate order i, f, g, o:
+ *             i = sigmoid(W_ii x + b_ii + W_hi h + b_hi)   f = sigmoid(W_if x + b_if + W_hf h + b_hf)
+ *             g = tanh(W_ig x + b_ig + W_hg h + b_hg)      o = sigmoid(W_io x + b_io + W_ho h + b_ho)
+ *             c' = f * c + i * g                           h' = o * tanh(c')
+ *           layer l > 0 reads layer l - 1's h' of the same position; no proj_size, not bidirectional
+ *   state   s_t = decoder(h_t of the top layer)
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, nlayers in {1, 2}.  No dropout (nn.LSTM has it between layers only).
+ * The existing tracker structs are not touched: an LSTM tracker has its own.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_LSTM_MAX_LAYERS 2
+
+typedef struct cirs_lstm_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t nlayers;   /* 1 or 2 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_lstm_cfg;
+
+typedef struct cirs_lstm_layer { /* names: lstm.weight_ih_l<k>, lstm.weight_hh_l<k> [4D,D]; lstm.bias_ih_l<k>, lstm.bias_hh_l<k> [4D]; rows i | f | g | o */
+    const float *w_ih, *w_hh, *b_ih, *b_hh;
+} cirs_lstm_layer;
+
+typedef struct cirs_lstm_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    cirs_lstm_layer layer[CIRS_LSTM_MAX_LAYERS];
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_lstm_weights;
+
+typedef struct cirs_lstm_state {
+    float* x_hist; /* [B, max_len, D] the input slots (what the backward recomputes from) */
+    float* h;      /* [nlayers, B, D] the carried hidden state of every layer */
+    float* c;      /* [nlayers, B, D] the carried cell state of every layer */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_lstm_state;
+
+typedef struct cirs_lstm_layer_grads { /* b_ih and b_hh receive the same gradient; both are written */
+    float *w_ih, *w_hh, *b_ih, *b_hh;
+} cirs_lstm_layer_grads;
+
+typedef struct cirs_lstm_grads { /* same tensors, same order as cirs_lstm_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    cirs_lstm_layer_grads layer[CIRS_LSTM_MAX_LAYERS];
+    float *dec_w, *dec_b;
+} cirs_lstm_grads;
+
+/* cirs_gru_tracker_init / cirs_gru_tracker_step for the LSTM tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, (h, c) = cell(x_0, 0, 0), len = 1; step appends one position.  Rows with skip != 0 (step), an env / user /
+ * item id out of range (item < 0: the env finished), a never-initialised or a full history are left untouched: neither h, c, len nor their
+ * row of state_out is written.  state_out row stride = state_stride floats. */
+int cirs_lstm_tracker_init(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, cirs_lstm_state* st, const int32_t* users,
+                           const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_lstm_tracker_step(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, cirs_lstm_state* st, const int64_t* items,
+                           const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                           int64_t state_stride, void* stream);
+
+/* cirs_gru_tracker_backward for the LSTM tracker: back-propagation through time through h and c, recomputed from the stored slots.  Same
+ * arguments: users[B]; act / rew are the time-major trajectory rows [T,B]; row_env / row_t / offsets / lens describe the buffer rows
+ * (env-major, see cirs_ppo_prepare); dstate [T+1,B,S] = d loss / d obs.  Every gradient tensor is OVERWRITTEN.  No float atomics; every
+ * reduction has a fixed order, so two calls give the same bits.  A workspace smaller than
+ * cirs_lstm_tracker_backward_workspace_bytes(cfg, n_rows), or one not 16-byte aligned, is refused before any launch. */
+int64_t cirs_lstm_tracker_backward_workspace_bytes(const cirs_lstm_cfg* cfg, int32_t n_rows);
+int cirs_lstm_tracker_backward(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, const cirs_lstm_state* st, const int32_t* users,
+                               const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                               const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                               const cirs_lstm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with an LSTM tracker: the same launch sequence (one loop serves both, csrc/rollout.hip) with
+ * cirs_lstm_tracker_init / cirs_lstm_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_lstm(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                              const cirs_lstm_cfg* trk_cfg, const cirs_lstm_weights* trk_w, cirs_lstm_state* trk_st,
+                              const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                              int32_t n_env, const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited,
+                              int32_t force_length, int32_t greedy, const float* gumbel, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),
