@@ -8,6 +8,10 @@ torch_train              the optimiser steps of UserModel_MMOE.fit_data (referen
 mlp_torch_train          the same for the two-task build of the static baselines (reference MLP-taobao.py: 91 static-state inputs ->
                          feat_item (27) and y (1), its own loss_taobao, MLP-taobao.py:137-155), for run-time shapes: the comparison
                          object of csrc/mlp_train.hip, in tests and in tools/probe_mlp_train.py.
+loss_and_grad            the loss columns {loss, reg} and the gradient of loss + reg of ONE batch by autograd over the same forward, loss
+mlp_loss_and_grad        and regulariser, in the dtype asked for: the float64 reference of a device step's gradient buffer.
+hidden_preactivations    the inputs of every hidden layer's relu for a batch (a unit within rounding of zero may take the other side
+                         of the kink in another precision).
 """
 import numpy as np
 import torch
@@ -63,6 +67,16 @@ def loss_taobao(y_pred, y, exposure):
     return (((1 / (1 + exposure) * y_pred - y) ** 2) * (y + 1)).mean()
 
 
+def _regulariser(p, l2_linear, l2_all, dtype, device):
+    """core/user_model.py's two lists: linear_model.weight (l2_linear) and EVERY parameter, linear_model.weight among them (l2_all) -> [1]."""
+    reg = torch.zeros((1,), dtype=dtype, device=device)
+    w = p["linear_model.weight"]
+    reg = reg + torch.sum(l2_linear * w * w)
+    for k in p:      # state_dict order = the reference's parameter order
+        reg = reg + torch.sum(l2_all * p[k] * p[k])
+    return reg
+
+
 def _torch_train(forward_loss, init, cols, batch_size, steps, order, l2_linear, l2_all, lr, betas, eps, dtype, device, keep):
     """The optimiser loop of torch_train / mlp_torch_train: forward_loss(p, *batch columns) -> the data loss; cols: the columns as 2-d
     tensors, x first."""
@@ -77,11 +91,7 @@ def _torch_train(forward_loss, init, cols, batch_size, steps, order, l2_linear, 
         idx = order[st * batch_size:(st + 1) * batch_size]
         loss = forward_loss(p, *(c[idx] for c in cols))
         opt.zero_grad()
-        reg = torch.zeros((1,), dtype=dtype, device=device)
-        w = p["linear_model.weight"]
-        reg = reg + torch.sum(l2_linear * w * w)
-        for k in names:
-            reg = reg + torch.sum(l2_all * p[k] * p[k])
+        reg = _regulariser(p, l2_linear, l2_all, dtype, device)
         (loss + reg.squeeze()).backward()
         opt.step()
         losses.append([float(loss.detach()), float(reg.detach())])
@@ -96,6 +106,34 @@ def torch_train(init, x, y, exposure, batch_size, steps=None, order=None, l2_lin
     cols = [torch.as_tensor(np.asarray(x)).to(device, dtype)] + [torch.as_tensor(np.asarray(c)).to(device, dtype).reshape(-1, 1) for c in (y, exposure)]
     return _torch_train(lambda p, xb, yb, eb: loss_taobao(forward(p, xb), yb, eb), init, cols, batch_size, steps, order, l2_linear, l2_all, lr,
                         betas, eps, dtype, device, keep)
+
+
+def _loss_and_grad(forward_loss, p, cols, l2_linear, l2_all, dtype):
+    """One batch of _torch_train's loop without the optimiser -> (tensor {loss, reg}, {name: d (loss + reg) / d p[name]}), detached."""
+    p = {k: torch.as_tensor(np.asarray(v)).to(dtype).clone().requires_grad_(True) for k, v in p.items()}
+    cols = [torch.as_tensor(np.asarray(c)).to(dtype) for c in cols]
+    loss = forward_loss(p, *cols)
+    reg = _regulariser(p, l2_linear, l2_all, dtype, "cpu").squeeze()
+    grads = torch.autograd.grad(loss + reg, list(p.values()))
+    return torch.stack([loss.detach(), reg.detach()]), dict(zip(p, grads))
+
+
+def loss_and_grad(p, x, y, exposure, l2_linear=1e-5, l2_all=1e-2, dtype=torch.float64):
+    """p: a state_dict (numpy) of the one-task build, x [n, 118], y and exposure [n] or [n, 1] -> (the columns the device writes to
+    loss_out = {data loss, regulariser}, {name: gradient of loss + reg}) in `dtype`."""
+    x, y, e = np.asarray(x), np.asarray(y).reshape(-1, 1), np.asarray(exposure).reshape(-1, 1)
+    return _loss_and_grad(lambda q, xb, yb, eb: loss_taobao(forward(q, xb), yb, eb), p, (x, y, e), l2_linear, l2_all, dtype)
+
+
+def hidden_preactivations(p, x, dtype=torch.float64):
+    """[z_0, z_1, ...]: z_l [n, H_l] = h_{l-1} W_l^T + b_l of every dnn.linears layer of p (either build), h_l = relu(z_l), in `dtype`."""
+    h = torch.as_tensor(np.asarray(x)).to(dtype)
+    out = []
+    while f"dnn.linears.{len(out)}.weight" in p:
+        w, b = (torch.as_tensor(np.asarray(p[f"dnn.linears.{len(out)}.{t}"])).to(dtype) for t in ("weight", "bias"))
+        out.append(h @ w.t() + b)
+        h = torch.relu(out[-1])
+    return out
 
 
 # ---- the two-task build of the static baselines (MLP-taobao.py, MLP-epsilonGreedy-taobao.py) ------------------------------------------
@@ -165,3 +203,9 @@ def mlp_torch_train(init, x, y, batch_size, steps=None, order=None, l2_linear=1e
     cols = [torch.as_tensor(np.asarray(x)).to(device, dtype), torch.as_tensor(np.asarray(y)).to(device, dtype).reshape(-1, ACTION_COLS + 1)]
     return _torch_train(lambda p, xb, yb: loss_taobao_mlp(mlp_forward(p, xb), yb), init, cols, batch_size, steps, order, l2_linear, l2_all, lr,
                         betas, eps, dtype, device, keep)
+
+
+def mlp_loss_and_grad(p, x, y, l2_linear=1e-5, l2_all=1e-2, dtype=torch.float64):
+    """loss_and_grad for the two-task build: x [n, 91], y [n, 28]."""
+    y = np.asarray(y).reshape(-1, ACTION_COLS + 1)
+    return _loss_and_grad(lambda q, xb, yb: loss_taobao_mlp(mlp_forward(q, xb), yb), p, (np.asarray(x), y), l2_linear, l2_all, dtype)
