@@ -104,6 +104,19 @@ class LstmState(C.Structure):       # cirs_lstm_state
     _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("c", C.c_void_p), ("len", C.c_void_p)]
 
 
+class AvgCfg(C.Structure):          # cirs_avg_cfg
+    _fields_ = [("n_users", C.c_int32), ("n_items", C.c_int32), ("dim_model", C.c_int32), ("dim_state", C.c_int32),
+                ("window", C.c_int32), ("max_len", C.c_int32), ("n_env", C.c_int32)]
+
+
+class AvgWeights(C.Structure):      # cirs_avg_weights / cirs_avg_grads (same layout)
+    _fields_ = [(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b", "dec_w", "dec_b")]
+
+
+class AvgState(C.Structure):        # cirs_avg_state
+    _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -386,6 +399,14 @@ SIGNATURES = {
     "cirs_rollout_collect_lstm": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(LstmCfg), C.POINTER(LstmWeights),
                                             C.POINTER(LstmState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                             C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_avg_tracker_init": (C.c_int, [C.POINTER(AvgCfg), C.POINTER(AvgWeights), C.POINTER(AvgState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_avg_tracker_step": (C.c_int, [C.POINTER(AvgCfg), C.POINTER(AvgWeights), C.POINTER(AvgState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_avg_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(AvgCfg), C.c_int32]),
+    "cirs_avg_tracker_backward": (C.c_int, [C.POINTER(AvgCfg), C.POINTER(AvgWeights), C.POINTER(AvgState), _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                            C.POINTER(AvgWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_avg": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(AvgCfg), C.POINTER(AvgWeights),
+                                           C.POINTER(AvgState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                           C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -76,16 +76,16 @@ def weights_struct(params: Dict[str, torch.Tensor], nlayers: int, struct=abi.Gru
 
 class DeviceRecurrentTracker:
     """Recurrent tracker state for B envs: what the GRU and the LSTM engine share.  A subclass names its cell: the ctypes structs, the
-    layers' state_dict names, the prefix of its entry points, its shape check, and the carried tensors next to h (CARRY)."""
+    layers' state_dict names, the prefix of its entry points, its shape check, and the carried tensors next to h (CARRY).  The pooled-window
+    engine (avg_tracker.DeviceAvgTracker) is the same surface with no layers and nothing carried."""
     CFG = WEIGHTS = STATE = LAYER_FIELDS = ENTRY = check_shape = None
     CARRY = ("h",)
 
     def __init__(self, params: Dict[str, torch.Tensor], n_users, n_items, n_env, max_turn, *, dim_model=32, dim_state=20, nlayers=1,
                  device="cuda"):
-        type(self).check_shape(dim_model, dim_state, nlayers)
+        cell = self._cell_cfg(dim_model, dim_state, nlayers)
         self.device = torch.device(device)
-        self.cfg = self.CFG(n_users=n_users, n_items=n_items, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
-                            max_len=max_turn + 1, n_env=n_env)
+        self.cfg = self.CFG(n_users=n_users, n_items=n_items, dim_model=dim_model, dim_state=dim_state, max_len=max_turn + 1, n_env=n_env, **cell)
         self.params = params
         self.nlayers = nlayers
         self.w = self._weights(params)
@@ -98,6 +98,11 @@ class DeviceRecurrentTracker:
         self._bws = None
         self._lib = abi.lib()
         self.dim_state = dim_state
+
+    def _cell_cfg(self, dim_model, dim_state, nlayers):
+        """The shape check of this build, then the members of the cfg struct that describe the cell."""
+        type(self).check_shape(dim_model, dim_state, nlayers)
+        return {"nlayers": nlayers}
 
     def _weights(self, tensors):
         return weights_struct(tensors, self.nlayers, self.WEIGHTS, self.LAYER_FIELDS)

@@ -1,5 +1,5 @@
 """StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
-there) on the device engines.
+there) and StateTrackerAvg (a pooled window over the last items; no counterpart there) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
@@ -10,6 +10,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from cirs_hip.avg_tracker import DeviceAvgTracker, avg_param_shapes, check_avg_shape, init_avg_tracker_params
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
@@ -207,3 +208,31 @@ class StateTrackerLSTM(_RecurrentStateTracker):
     nlayers) with h_{-1} = c_{-1} = 0 over them, the same decoder."""
     CELL, ENGINE = "LSTM", DeviceLstmTracker
     check_shape, param_shapes, init_params = check_lstm_shape, lstm_param_shapes, init_lstm_tracker_params
+
+
+class StateTrackerAvg(_RecurrentStateTracker):
+    """The cheapest tracker: the same input slots, h_p = x_0 + the mean of the last `window_size` item slots, the same decoder (DESIGN.md
+    7.4; the reference has no counterpart).  StateTrackerTransformer's constructor keywords plus window_size; nhead, d_hid, nlayers and
+    dropout are accepted and unused (the model has no dropout site).  No sequence model, but the engine surface, the collect and every
+    refusal of the recurrent trackers: a _RecurrentStateTracker to whatever asks."""
+    CELL, ENGINE = "Avg", DeviceAvgTracker
+
+    def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
+                 dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
+                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, window_size=10):
+        nn.Module.__init__(self)
+        if dataset != "KuaishouEnv-v0":
+            raise NotImplementedError("StateTrackerAvg serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
+        check_avg_shape(dim_model, dim_state, window_size, MAX_TURN + 1)
+        self.window_size = int(window_size)
+        self.dropout_p, self.nlayers = 0.0, 0
+        self.dataset, self.device = dataset, torch.device(device if str(device) != "cpu" else "cuda")
+        self.dim_model, self.dim_state = dim_model, dim_state
+        self.MAX_TURN = MAX_TURN + 1
+        self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
+        init = init_avg_tracker_params(self.n_users, self.n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, init_std=init_std)
+        self._setup(avg_param_shapes(self.n_users, self.n_items, dim_model, dim_state), init, seed)
+
+    def _make_engine(self, n_env):
+        return DeviceAvgTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
+                                dim_state=self.dim_state, window_size=self.window_size, device=self.device)

@@ -765,6 +765,76 @@ int cirs_rollout_collect_lstm(const cirs_env_cfg* env_cfg, const cirs_env_tables
                               int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, pooled window: StateTrackerAvg (csrc/avg_tracker.hip)
+ * The reference has no counterpart; the model is defined here:
+ *   inputs  the recurrent trackers' slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *           no sqrt(D) scale, no positional encoding
+ *   pooling n_p = min(window, p);  m_0 = 0,  m_p = (x_{p-n_p+1} + ... + x_p) / n_p  -- fp32, summed in ascending k starting from
+ *           x_{p-n_p+1}, then one division by float(n_p);  h_p = x_0 + m_p.  The sum is formed anew from the stored slots at every
+ *           step (no running sum): position p depends on its window only.  A window beyond the history is the mean of all of it.
+ *   state   s_p = decoder(h_p)
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, window >= 1, max_len <= 4096.  No new parameters, no dropout site.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct cirs_avg_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t window;    /* W >= 1: item slots in the mean */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_avg_cfg;
+
+typedef struct cirs_avg_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_avg_weights;
+
+typedef struct cirs_avg_state {
+    float* x_hist; /* [B, max_len, D] the input slots: the window of every step and the backward read them */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_avg_state;
+
+typedef struct cirs_avg_grads { /* same tensors, same order as cirs_avg_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float *dec_w, *dec_b;
+} cirs_avg_grads;
+
+/* cirs_lstm_tracker_init / cirs_lstm_tracker_step for the Avg tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of range
+ * (item < 0: the env finished), a never-initialised or a full history are left untouched: neither x_hist, len nor their row of state_out
+ * is written.  state_out row stride = state_stride floats.  window < 1 is refused (CIRS_E_INVALID). */
+int cirs_avg_tracker_init(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, cirs_avg_state* st, const int32_t* users,
+                          const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_avg_tracker_step(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, cirs_avg_state* st, const int64_t* items,
+                          const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                          int64_t state_stride, void* stream);
+
+/* cirs_gru_tracker_backward for the Avg tracker.  The pooling is linear: with dH[b,p] = sum_s dstate[p,b,s] W_dec[s,:],
+ *   dX[b,0] = sum_{p=0}^{len_b-1} dH[b,p]      dX[b,k] = sum_{p=k}^{min(len_b-1, k+window-1)} dH[b,p] / float(n_p)   (k >= 1; p ascending)
+ * then the slot stage of the recurrent trackers.  Same arguments: users[B]; act / rew are the time-major trajectory rows [T,B];
+ * row_env / row_t / offsets / lens describe the buffer rows (env-major, see cirs_ppo_prepare); dstate [T+1,B,S] = d loss / d obs; of st
+ * only x_hist is read.  Every gradient tensor is OVERWRITTEN.  No float atomics; every reduction has a fixed order, so two calls give
+ * the same bits.  A workspace smaller than cirs_avg_tracker_backward_workspace_bytes(cfg, n_rows), or one not 16-byte aligned, is
+ * refused before any launch. */
+int64_t cirs_avg_tracker_backward_workspace_bytes(const cirs_avg_cfg* cfg, int32_t n_rows);
+int cirs_avg_tracker_backward(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, const cirs_avg_state* st, const int32_t* users,
+                              const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                              const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                              const cirs_avg_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with an Avg tracker: the same launch sequence (one loop serves the three, csrc/rollout.hip) with
+ * cirs_avg_tracker_init / cirs_avg_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_avg(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                             const cirs_avg_cfg* trk_cfg, const cirs_avg_weights* trk_w, cirs_avg_state* trk_st,
+                             const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                             int32_t n_env, const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited,
+                             int32_t force_length, int32_t greedy, const float* gumbel, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),

@@ -1,13 +1,15 @@
-"""The recurrent state trackers (GRU, LSTM) against the Transformer one at the benchmark shapes:  python tools/probe_gru_tracker.py [--workload c2|c3] [--reps 60]
+"""The recurrent state trackers (GRU, LSTM) and the pooled-window one (Avg) against the Transformer one at the benchmark shapes:
+    python tools/probe_gru_tracker.py [--workload c2|c3] [--reps 60]
 
-Five trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
-with 2 layers.  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
+Seven trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
+with 2 layers, the Avg tracker with a window of 3 and of 10.  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
   step_us        one tracker step alone (one launch, all envs) at positions 1, 15 and 30 -- a device-event pair around the launch
   collect_ms     one DeviceRollout.collect (what Collector.collect runs on the device): the fused two-launch sequence for the Transformer,
-                 cirs_rollout_collect_gru's / _lstm's unfused sequence for the recurrent ones -- device events around the call, enqueued behind a spin kernel (the host
+                 cirs_rollout_collect_gru's / _lstm's / _avg's unfused sequence for the others -- device events around the call, enqueued behind a spin kernel (the host
                  ahead of the device, as in the training loop); collect_idle_ms: the same from an idle stream (the host's launch rate counts)
   bwd_adam_ms    the tracker backward + Adam step of one update (the learner's d loss / d obs as upstream gradient) -- device events
-Medians over --reps repetitions after a warm-up, min and max alongside; lstm_over_gru: the ratios of those medians per layer count.  One JSON line.
+Medians over --reps repetitions after a warm-up, min and max alongside; lstm_over_gru: the ratios of those medians per layer count;
+avg_over_gru: the Avg tracker's over the one-layer GRU's, per window.  One JSON line.
 --trace: no timing, a few collects and backwards per tracker -- the run to put under `rocprofv3 --kernel-trace --stats -- python ...` for kernel times
 (tracing slows the host: never in the same run as the timings above)."""
 import argparse
@@ -21,6 +23,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+from cirs_hip.avg_tracker import DeviceAvgTracker, avg_param_shapes, init_avg_tracker_params  # noqa: E402
 from cirs_hip.gru_tracker import DeviceGruTracker, gru_param_shapes, init_gru_tracker_params  # noqa: E402
 from cirs_hip.lstm_tracker import DeviceLstmTracker, init_lstm_tracker_params, lstm_param_shapes  # noqa: E402
 from cirs_hip.rollout import DeviceRollout  # noqa: E402
@@ -35,6 +38,14 @@ def recurrent_engine(cell, wl, layers, device):
     U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
     flat, views = flat_tracker_params(shapes(U, I, 32, 20, layers), device=device, init=init(U, I, seed=2023, nlayers=layers))
     trk = engine(dict(views), U, I, B, T, nlayers=layers, device=device)
+    trk.enable_training(flat)
+    return trk
+
+
+def avg_engine(wl, window, device):
+    U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
+    flat, views = flat_tracker_params(avg_param_shapes(U, I, 32, 20), device=device, init=init_avg_tracker_params(U, I, seed=2023))
+    trk = DeviceAvgTracker(dict(views), U, I, B, T, window_size=window, device=device)
     trk.enable_training(flat)
     return trk
 
@@ -76,6 +87,9 @@ def main():
         for layers in (1, 2):
             trk = recurrent_engine(cell, wl, layers, device)
             variants[f"{cell}_l{layers}"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
+    for window in (3, 10):
+        trk = avg_engine(wl, window, device)
+        variants[f"avg_w{window}"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
     users = torch.as_tensor(np.random.RandomState(0).randint(0, U, B)).to(device, torch.int32)
     items = torch.as_tensor(np.random.RandomState(1).randint(0, I, B)).to(device)
     rews = torch.rand(B, dtype=torch.float64, device=device)
@@ -146,6 +160,9 @@ def main():
     out["lstm_over_gru"] = {f"l{l}": {"step_us_30": round(out["trackers"][f"lstm_l{l}"]["step_us"]["30"]["median"] / out["trackers"][f"gru_l{l}"]["step_us"]["30"]["median"], 3),
                                       "collect_ms": round(med(f"lstm_l{l}", "collect_ms") / med(f"gru_l{l}", "collect_ms"), 3),
                                       "bwd_adam_ms": round(med(f"lstm_l{l}", "bwd_adam_ms") / med(f"gru_l{l}", "bwd_adam_ms"), 3)} for l in (1, 2)}
+    out["avg_over_gru"] = {f"w{w}": {"step_us_30": round(out["trackers"][f"avg_w{w}"]["step_us"]["30"]["median"] / out["trackers"]["gru_l1"]["step_us"]["30"]["median"], 3),
+                                     "collect_ms": round(med(f"avg_w{w}", "collect_ms") / med("gru_l1", "collect_ms"), 3),
+                                     "bwd_adam_ms": round(med(f"avg_w{w}", "bwd_adam_ms") / med("gru_l1", "bwd_adam_ms"), 3)} for w in (3, 10)}
     print(json.dumps(out), flush=True)
 
 
