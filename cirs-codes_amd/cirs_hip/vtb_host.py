@@ -8,6 +8,9 @@ tracker_states    one teacher-forced causal pass of HostStateTracker (core/host_
 redraw_states     the same states under the exact-redraw dropout (dropout_redraw=True): one causal pass per call c with that call's masks
                   over positions 0..c, position c kept, every call's graph retained -- what the reference's tracker in train() does.
 gauss_noise       the rollout's Gaussian draw z (Box-Muller on Philox), restated in numpy bit for bit.
+policy_rows       the policy of CIRS-RL-taobao.py over given states as plain tensor algebra in the dtype of its arguments (the tianshou
+                  modules cast their input to float32): Net trunk, ActorProb's (mu, sigma), Independent(Normal)'s log-probability and
+                  entropy, the Critic's last layer.  hidden_preactivations returns the trunk's pre-activations.
 """
 import math
 
@@ -100,6 +103,45 @@ def redraw_states(tracker, user, rew, act, masks_of_call=None):
                         for c in range(n)])
 
 
+# ---- policy rows -------------------------------------------------------------------------------------------------------------
+SIGMA_MIN, SIGMA_MAX = -20.0, 2.0      # ActorProb's clamp of a conditioned sigma head
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def hidden_preactivations(p, states):
+    """The Net trunk's pre-activations [n, width] per hidden layer over states [n, dim_state]; p: {name: tensor} with the names of
+    vtb_model.policy_tensors (trunk{i}_w / _b, torch's [out][in] layout), in the dtype of the tensors."""
+    out, h = [], states
+    i = 0
+    while f"trunk{i}_w" in p:
+        out.append(h @ p[f"trunk{i}_w"].T + p[f"trunk{i}_b"])
+        h = torch.relu(out[-1])
+        i += 1
+    return out
+
+
+def policy_rows(p, states, act, max_action=1.0, unbounded=False):
+    """Per row of states [n, dim_state] and stored raw actions act [n, 27]: dict(mu, sigma [n, 27], logp, ent, value [n], pre = the trunk's
+    pre-activations, sigma_pre = the sigma head's output [n, 27] or None with the free sigma_param).  ActorProb.forward, Independent(Normal)
+    .log_prob / .entropy and Critic.forward as tensor algebra, in the dtype of the arguments."""
+    pre = hidden_preactivations(p, states)
+    h = torch.relu(pre[-1])
+    mu = h @ p["mu_w"].T + p["mu_b"]
+    if not unbounded:
+        mu = max_action * torch.tanh(mu)
+    if "sigma_w" in p:
+        sigma_pre = h @ p["sigma_w"].T + p["sigma_b"]
+        log_sigma = torch.clamp(sigma_pre, min=SIGMA_MIN, max=SIGMA_MAX)
+    else:
+        sigma_pre = None
+        log_sigma = p["sigma_param"].reshape(1, -1) + torch.zeros_like(mu)
+    sigma = log_sigma.exp()
+    logp = (-((act - mu) ** 2) / (2.0 * sigma ** 2) - log_sigma - HALF_LOG_2PI).sum(-1)
+    ent = (0.5 + HALF_LOG_2PI + log_sigma).sum(-1)
+    value = (h @ p["critic_w"].T + p["critic_b"]).reshape(-1)
+    return dict(mu=mu, sigma=sigma, logp=logp, ent=ent, value=value, pre=pre, sigma_pre=sigma_pre)
+
+
 # ---- Gaussian noise -----------------------------------------------------------------------------------------------------------
 _M32 = np.uint64(0xFFFFFFFF)
 _F = np.float32
@@ -188,3 +230,4 @@ def gauss_noise(seed, collect_id, env_ids, ts, dims=ACTION_DIM):
     cs = np.select([q == 0, q == 1, q == 2], [c, -s, -c], s)
     sn = np.select([q == 0, q == 1, q == 2], [s, c, -s], -c)
     return (rad * np.where((dim & np.uint64(1)) != 0, sn, cs)).astype(_F)
+
