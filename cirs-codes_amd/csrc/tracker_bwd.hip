@@ -255,8 +255,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv(const float* __restrict__ QKV
 // query write a dummy strip row, columns beyond a query's causal limit are never read, selects do the masking.
 // cross-lane reduction.  In the second phase of the backward the lane owns two KEYS the same way (dK / dV accumulated over the later queries
 // in order).  The probabilities are not kept between the forward and the backward pass: the backward recomputes them from Q, K (cheaper
-// than 15 MB of P through HBM).  Used when max_len <= 64 and the LDS image fits 64 KB (max_len <= 50 at 4 heads); longer episodes take the
-// per-row kernels.
+// than 15 MB of P through HBM).  Used when max_len <= 64 and the LDS image of the backward (bwd_floats) fits 64 KB: max_len <= 64 / 62 / 47 / 35
+// at 1 / 2 / 4 / 8 heads (tests/trackercase.py: EP_LIMIT, both sides of each tested); longer episodes take the per-row kernels.
 template <int NH> struct EpGeo {
     static constexpr int NW = NH < 4 ? NH : 4;      // head groups (lane / SL)
     static constexpr int SL = 64 / NW;              // query-pair slots per head group and pass
