@@ -117,6 +117,23 @@ class AvgState(C.Structure):        # cirs_avg_state
     _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+CASER_MAX_HEIGHTS = 4
+
+
+class CaserCfg(C.Structure):        # cirs_caser_cfg
+    _fields_ = list(AvgCfg._fields_) + [("n_heights", C.c_int32), ("heights", C.c_int32 * CASER_MAX_HEIGHTS)]
+
+
+class CaserWeights(C.Structure):    # cirs_caser_weights / cirs_caser_grads (same layout)
+    _fields_ = ([(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b")] +
+                [("conv_w", C.c_void_p * CASER_MAX_HEIGHTS), ("conv_b", C.c_void_p * CASER_MAX_HEIGHTS)] +
+                [(k, C.c_void_p) for k in ("vert_w", "vert_b", "fc_w", "fc_b", "dec_w", "dec_b")])
+
+
+class CaserState(C.Structure):      # cirs_caser_state
+    _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -407,6 +424,14 @@ SIGNATURES = {
     "cirs_rollout_collect_avg": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(AvgCfg), C.POINTER(AvgWeights),
                                            C.POINTER(AvgState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                            C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_caser_tracker_init": (C.c_int, [C.POINTER(CaserCfg), C.POINTER(CaserWeights), C.POINTER(CaserState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_caser_tracker_step": (C.c_int, [C.POINTER(CaserCfg), C.POINTER(CaserWeights), C.POINTER(CaserState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_caser_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(CaserCfg), C.c_int32]),
+    "cirs_caser_tracker_backward": (C.c_int, [C.POINTER(CaserCfg), C.POINTER(CaserWeights), C.POINTER(CaserState), _P, _P, _P, _P, _P, _P, _P, C.c_int32, _P,
+                                            C.POINTER(CaserWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_caser": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(CaserCfg), C.POINTER(CaserWeights),
+                                             C.POINTER(CaserState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                             C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -1,5 +1,6 @@
 """StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
-there) and StateTrackerAvg (a pooled window over the last items; no counterpart there) on the device engines.
+there), StateTrackerAvg (a pooled window over the last items; no counterpart there) and StateTrackerCaser (Caser's convolutions over that
+window; no counterpart there either) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
@@ -11,6 +12,7 @@ import torch
 from torch import nn
 
 from cirs_hip.avg_tracker import DeviceAvgTracker, avg_param_shapes, check_avg_shape, init_avg_tracker_params
+from cirs_hip.caser_tracker import DeviceCaserTracker, caser_param_shapes, check_caser_shape, init_caser_tracker_params
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
@@ -236,3 +238,41 @@ class StateTrackerAvg(_RecurrentStateTracker):
     def _make_engine(self, n_env):
         return DeviceAvgTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
                                 dim_state=self.dim_state, window_size=self.window_size, device=self.device)
+
+
+class StateTrackerCaser(_RecurrentStateTracker):
+    """The convolutional window tracker: the same input slots, the window of the last `window_size` item slots through Caser's horizontal
+    filter banks (heights `filter_sizes`, `num_filters` each, max-pooled over time) and its vertical filter, one fc layer, h_p = x_0 + z, the
+    same decoder (the reference has no counterpart).  StateTrackerTransformer's constructor keywords plus window_size,
+    filter_sizes and num_filters; nhead, d_hid and nlayers are accepted and unused.  Caser's dropout on the concatenation is not built:
+    dropout > 0 in training mode raises.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
+    CELL, ENGINE = "Caser", DeviceCaserTracker
+
+    def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
+                 dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
+                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, window_size=10,
+                 filter_sizes=(2, 3, 4), num_filters=16):
+        nn.Module.__init__(self)
+        if dataset != "KuaishouEnv-v0":
+            raise NotImplementedError("StateTrackerCaser serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
+        check_caser_shape(dim_model, dim_state, window_size, filter_sizes, num_filters, MAX_TURN + 1)
+        self.window_size, self.filter_sizes, self.num_filters = int(window_size), tuple(int(h) for h in filter_sizes), int(num_filters)
+        self.dropout_p, self.nlayers = float(dropout), 0
+        self._check_dropout(self.training)
+        self.dataset, self.device = dataset, torch.device(device if str(device) != "cpu" else "cuda")
+        self.dim_model, self.dim_state = dim_model, dim_state
+        self.MAX_TURN = MAX_TURN + 1
+        self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
+        kw = dict(dim_model=dim_model, dim_state=dim_state, window_size=self.window_size, filter_sizes=self.filter_sizes, num_filters=self.num_filters)
+        init = init_caser_tracker_params(self.n_users, self.n_items, seed=seed, init_std=init_std, **kw)
+        self._setup(caser_param_shapes(self.n_users, self.n_items, **kw), init, seed)
+
+    def _check_dropout(self, training):
+        if training and self.dropout_p > 0:
+            raise ValueError("StateTrackerCaser: dropout on the concatenation is not built (dropout > 0 in training mode); use dropout=0.0 or "
+                             "call .eval()")
+
+    def _make_engine(self, n_env):
+        return DeviceCaserTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
+                                  dim_state=self.dim_state, window_size=self.window_size, filter_sizes=self.filter_sizes,
+                                  num_filters=self.num_filters, device=self.device)

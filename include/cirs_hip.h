@@ -835,6 +835,96 @@ int cirs_rollout_collect_avg(const cirs_env_cfg* env_cfg, const cirs_env_tables*
                              int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, convolutional window: StateTrackerCaser (csrc/caser_tracker.hip)
+ * The reference has no counterpart; the model is defined here (Caser: horizontal filters max-pooled over time plus one vertical filter
+ * over the window of the last W item slots, treated as a [W, D] image):
+ *   inputs  the other trackers' slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *           no sqrt(D) scale, no positional encoding
+ *   window  win_p[j] = x_{p-W+1+j} if p-W+1+j >= 1, else the zero row    (j = 0..W-1: the last W ITEM slots, zero rows in front; x_0 is
+ *           never in it; position 0 has an all-zero window and no special case)
+ *   banks   c_{i,f,t} = bh_i[f] + sum_{j<h_i} sum_d Wh_i[f,j,d] win_p[t+j,d]   (t = 0..W-h_i; fp32, one chain from the bias, j then d ascending)
+ *           o_{i,f}   = relu(max_t c_{i,f,t})     zero rows take part in the convolution and in the max; arg-max = the FIRST maximal t
+ *   vertical v_d = relu(bv + sum_j wv[j] win_p[j,d])
+ *   fc      z = relu(fc([o_0 | o_1 | ... | v]))    fc: [D, 16 n_heights + D]
+ *   state   h_p = x_0 + z;  s_p = decoder(h_p)
+ * The window is read anew from the stored slots at every step: position p depends on its window and x_0 only.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, 16 filters per bank, heights a non-empty strictly ascending subset of
+ * {1, 2, 3, 4}, max(heights) <= window <= 16, max_len <= 4096.  No dropout site.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_CASER_MAX_HEIGHTS 4
+#define CIRS_CASER_FILTERS 16
+#define CIRS_CASER_MAX_WINDOW 16
+
+typedef struct cirs_caser_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t window;    /* W: item slots in the window, max(heights) <= W <= 16 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+    int32_t n_heights; /* horizontal banks, 1..4 */
+    int32_t heights[CIRS_CASER_MAX_HEIGHTS]; /* h_i, strictly ascending, each in 1..4; entries >= n_heights are ignored */
+} cirs_caser_cfg;
+
+typedef struct cirs_caser_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float* conv_w[CIRS_CASER_MAX_HEIGHTS]; /* horizontal_cnn.<i>.weight [16,1,h_i,D] */
+    const float* conv_b[CIRS_CASER_MAX_HEIGHTS]; /* horizontal_cnn.<i>.bias [16] */
+    const float *vert_w, *vert_b;         /* vertical_cnn.weight [1,1,W,1], vertical_cnn.bias [1] */
+    const float *fc_w, *fc_b;             /* fc [D, 16 n_heights + D] (input order o_0 | o_1 | ... | v), [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_caser_weights;
+
+typedef struct cirs_caser_state {
+    float* x_hist; /* [B, max_len, D] the input slots: the window of every step and the backward read them */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_caser_state;
+
+typedef struct cirs_caser_grads { /* same tensors, same order as cirs_caser_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float* conv_w[CIRS_CASER_MAX_HEIGHTS];
+    float* conv_b[CIRS_CASER_MAX_HEIGHTS];
+    float *vert_w, *vert_b, *fc_w, *fc_b;
+    float *dec_w, *dec_b;
+} cirs_caser_grads;
+
+/* cirs_avg_tracker_init / cirs_avg_tracker_step for the Caser tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of range
+ * (item < 0: the env finished), a never-initialised or a full history are left untouched: neither x_hist, len nor their row of state_out
+ * is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes is refused (CIRS_E_INVALID / CIRS_E_UNSUPPORTED)
+ * with a message that names the member, before any pointer is read. */
+int cirs_caser_tracker_init(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, cirs_caser_state* st, const int32_t* users,
+                            const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_caser_tracker_step(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, cirs_caser_state* st, const int64_t* items,
+                            const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                            int64_t state_stride, void* stream);
+
+/* cirs_avg_tracker_backward for the Caser tracker.  No sequential pass: the forward of every buffer row is recomputed from the stored slots
+ * (the pooling's arg-max included), the decoder stage is the other trackers', then fc, both ReLUs, the vertical filter and the max-pool give
+ * a window gradient per row, which is folded into dX[b,k] in ascending p (dX[b,0] = sum_p dH[b,p]); then the slot stage of the recurrent
+ * trackers.  Same arguments: users[B]; act / rew are the time-major trajectory rows [T,B]; row_env / row_t / offsets / lens describe the
+ * buffer rows (env-major, see cirs_ppo_prepare); dstate [T+1,B,S] = d loss / d obs; of st only x_hist is read.  Every gradient tensor is
+ * OVERWRITTEN.  No float atomics; every reduction has a fixed order, so two calls give the same bits.  A workspace smaller than
+ * cirs_caser_tracker_backward_workspace_bytes(cfg, n_rows), or one not 16-byte aligned, is refused before any launch. */
+int64_t cirs_caser_tracker_backward_workspace_bytes(const cirs_caser_cfg* cfg, int32_t n_rows);
+int cirs_caser_tracker_backward(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, const cirs_caser_state* st, const int32_t* users,
+                                const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                                const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                                const cirs_caser_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with a Caser tracker: the same launch sequence (one loop serves the four, csrc/rollout.hip) with
+ * cirs_caser_tracker_init / cirs_caser_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_caser(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                               const cirs_caser_cfg* trk_cfg, const cirs_caser_weights* trk_w, cirs_caser_state* trk_st,
+                               const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj,
+                               int32_t n_env, const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited,
+                               int32_t force_length, int32_t greedy, const float* gumbel, void* workspace,
+                               int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),
