@@ -5,8 +5,9 @@ window; no counterpart there either) on the device engines.
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
 buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
-LSTM cells) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward (no autograd
-graph)."""
+LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions) and the gradient arrives through
+cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward (no
+autograd graph)."""
 import numpy as np
 import torch
 from torch import nn
@@ -156,30 +157,42 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU and StateTrackerLSTM share: StateTrackerTransformer's constructor keywords (a script changes the class name
-    only; nhead and d_hid are accepted and unused), the refusals, the engine.  A subclass names its cell (CELL), its device engine and
-    the three functions of its cirs_hip module.  dropout: torch applies it between the layers only -- without effect at nlayers == 1
-    (as in torch); at nlayers == 2 it is not built and training mode with dropout > 0 raises."""
+    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg and StateTrackerCaser share: StateTrackerTransformer's constructor keywords (a
+    script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
+    with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
+    module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
+    effect at nlayers == 1 (as in torch); at nlayers == 2 it is not built and training mode with dropout > 0 raises."""
     CELL = ENGINE = check_shape = param_shapes = init_params = None
 
     def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
                  dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
-                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100):
+                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, **model_kw):
         super().__init__()
         cls = type(self)
         if dataset != "KuaishouEnv-v0":
             raise NotImplementedError(f"StateTracker{self.CELL} serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
-        cls.check_shape(dim_model, dim_state, nlayers)
-        self.dropout_p = float(dropout)
-        self.nlayers = int(nlayers)
-        self._check_dropout(self.training)
+        self._check_model(dim_model, dim_state, nlayers, dropout, MAX_TURN + 1, **model_kw)
         self.dataset, self.device = dataset, torch.device(device if str(device) != "cpu" else "cuda")
         self.dim_model, self.dim_state = dim_model, dim_state
         self.MAX_TURN = MAX_TURN + 1
         self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
-        init = cls.init_params(self.n_users, self.n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers,
-                               init_std=init_std)
-        self._setup(cls.param_shapes(self.n_users, self.n_items, dim_model, dim_state, nlayers), init, seed)
+        kw = dict(dim_model=dim_model, dim_state=dim_state, **self._model_kw())
+        init = cls.init_params(self.n_users, self.n_items, seed=seed, init_std=init_std, **kw)
+        self._setup(cls.param_shapes(self.n_users, self.n_items, **kw), init, seed)
+
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len):
+        """Refuse a model that is not built; set the model arguments (the subclass's own keywords among them), nlayers and dropout_p as
+        attributes.  An unknown keyword of the constructor ends here, as Python's TypeError."""
+        type(self).check_shape(dim_model, dim_state, nlayers)
+        self.dropout_p, self.nlayers = float(dropout), int(nlayers)
+        self._check_dropout(self.training)
+
+    def _model_kw(self):
+        """The model arguments as init_params and param_shapes take them -- and ENGINE, unless _engine_kw says otherwise."""
+        return dict(nlayers=self.nlayers)
+
+    def _engine_kw(self):
+        return self._model_kw()
 
     def _check_dropout(self, training):
         if training and self.nlayers > 1 and self.dropout_p > 0:
@@ -191,7 +204,7 @@ class _RecurrentStateTracker(_DeviceStateTracker):
 
     def _make_engine(self, n_env):
         return self.ENGINE(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
-                           dim_state=self.dim_state, nlayers=self.nlayers, device=self.device)
+                           dim_state=self.dim_state, device=self.device, **self._engine_kw())
 
     def train(self, mode: bool = True):
         self._check_dropout(mode)
@@ -217,27 +230,18 @@ class StateTrackerAvg(_RecurrentStateTracker):
     7.4; the reference has no counterpart).  StateTrackerTransformer's constructor keywords plus window_size; nhead, d_hid, nlayers and
     dropout are accepted and unused (the model has no dropout site).  No sequence model, but the engine surface, the collect and every
     refusal of the recurrent trackers: a _RecurrentStateTracker to whatever asks."""
-    CELL, ENGINE = "Avg", DeviceAvgTracker
+    CELL, ENGINE, param_shapes, init_params = "Avg", DeviceAvgTracker, avg_param_shapes, init_avg_tracker_params
 
-    def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
-                 dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
-                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, window_size=10):
-        nn.Module.__init__(self)
-        if dataset != "KuaishouEnv-v0":
-            raise NotImplementedError("StateTrackerAvg serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
-        check_avg_shape(dim_model, dim_state, window_size, MAX_TURN + 1)
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len, window_size=10):
+        check_avg_shape(dim_model, dim_state, window_size, max_len)
         self.window_size = int(window_size)
         self.dropout_p, self.nlayers = 0.0, 0
-        self.dataset, self.device = dataset, torch.device(device if str(device) != "cpu" else "cuda")
-        self.dim_model, self.dim_state = dim_model, dim_state
-        self.MAX_TURN = MAX_TURN + 1
-        self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
-        init = init_avg_tracker_params(self.n_users, self.n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, init_std=init_std)
-        self._setup(avg_param_shapes(self.n_users, self.n_items, dim_model, dim_state), init, seed)
 
-    def _make_engine(self, n_env):
-        return DeviceAvgTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
-                                dim_state=self.dim_state, window_size=self.window_size, device=self.device)
+    def _model_kw(self):
+        return {}      # the window has no parameters
+
+    def _engine_kw(self):
+        return dict(window_size=self.window_size)
 
 
 class StateTrackerCaser(_RecurrentStateTracker):
@@ -246,33 +250,18 @@ class StateTrackerCaser(_RecurrentStateTracker):
     same decoder (the reference has no counterpart).  StateTrackerTransformer's constructor keywords plus window_size,
     filter_sizes and num_filters; nhead, d_hid and nlayers are accepted and unused.  Caser's dropout on the concatenation is not built:
     dropout > 0 in training mode raises.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
-    CELL, ENGINE = "Caser", DeviceCaserTracker
+    CELL, ENGINE, param_shapes, init_params = "Caser", DeviceCaserTracker, caser_param_shapes, init_caser_tracker_params
 
-    def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
-                 dataset="KuaishouEnv-v0", has_user_embedding=True, has_action_embedding=True, has_feedback_embedding=False,
-                 nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, window_size=10,
-                 filter_sizes=(2, 3, 4), num_filters=16):
-        nn.Module.__init__(self)
-        if dataset != "KuaishouEnv-v0":
-            raise NotImplementedError("StateTrackerCaser serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
-        check_caser_shape(dim_model, dim_state, window_size, filter_sizes, num_filters, MAX_TURN + 1)
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len, window_size=10, filter_sizes=(2, 3, 4), num_filters=16):
+        check_caser_shape(dim_model, dim_state, window_size, filter_sizes, num_filters, max_len)
         self.window_size, self.filter_sizes, self.num_filters = int(window_size), tuple(int(h) for h in filter_sizes), int(num_filters)
         self.dropout_p, self.nlayers = float(dropout), 0
         self._check_dropout(self.training)
-        self.dataset, self.device = dataset, torch.device(device if str(device) != "cpu" else "cuda")
-        self.dim_model, self.dim_state = dim_model, dim_state
-        self.MAX_TURN = MAX_TURN + 1
-        self.n_users, self.n_items = user_columns[0].vocabulary_size, action_columns[0].vocabulary_size
-        kw = dict(dim_model=dim_model, dim_state=dim_state, window_size=self.window_size, filter_sizes=self.filter_sizes, num_filters=self.num_filters)
-        init = init_caser_tracker_params(self.n_users, self.n_items, seed=seed, init_std=init_std, **kw)
-        self._setup(caser_param_shapes(self.n_users, self.n_items, **kw), init, seed)
+
+    def _model_kw(self):
+        return dict(window_size=self.window_size, filter_sizes=self.filter_sizes, num_filters=self.num_filters)
 
     def _check_dropout(self, training):
         if training and self.dropout_p > 0:
             raise ValueError("StateTrackerCaser: dropout on the concatenation is not built (dropout > 0 in training mode); use dropout=0.0 or "
                              "call .eval()")
-
-    def _make_engine(self, n_env):
-        return DeviceCaserTracker(dict(self._views), self.n_users, self.n_items, n_env, self.MAX_TURN - 1, dim_model=self.dim_model,
-                                  dim_state=self.dim_state, window_size=self.window_size, filter_sizes=self.filter_sizes,
-                                  num_filters=self.num_filters, device=self.device)

@@ -1,175 +1,23 @@
-"""GPU: DeviceRollout.collect with an LSTM tracker (cirs_rollout_collect_lstm) against the same vector steps issued one entry point at a time
-from Python, bit for bit, in every mode; and against the float64 restatement of the tracker, teacher-forced on the device's own actions."""
-import numpy as np
+"""GPU: DeviceRollout.collect with an LSTM tracker (cirs_rollout_collect_lstm).
+The checks are tests/test_gpu_slot_rollout.py's, the same for the four slot trackers; this file binds them to its tracker's record."""
 import pytest
-import torch
 
-import envcase
-import lstmcase
-import policycase
-import rolloutcase
-from cirs_hip import lstm_host
+import test_gpu_slot_rollout as checks
+from slotcase import LSTM as SLOT
+from test_gpu_slot_rollout import tables  # noqa: F401  (the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
-U, I, T, S, L = 200, 300, 8, 20, 1      # I = 300: not a multiple of the sampler's 128-item chunk
-SEED, RNG_BASE = 1234, 40
-
-
-@pytest.fixture(scope="module")
-def tables():
-    from cirs_hip.synthetic import make_tables
-    return make_tables(U, I, seed=0)
-
-
-def build_stack(tab, B, **rollout_kw):
-    from cirs_hip.env import DeviceEnv, DeviceEnvTables
-    from cirs_hip.lstm_tracker import DeviceLstmTracker
-    from cirs_hip.policy import DevicePolicy
-    from cirs_hip.rollout import DeviceRollout
-    a_env, b_env = envcase.ab_env_tables(tab.raw_uid, tab.raw_pid, tab.alpha_u, tab.beta_i, U, I)
-    dt = DeviceEnvTables(tab.mat, tab.normed_mat, tab.item_cats, alpha_env=a_env, beta_env=b_env)
-    env = DeviceEnv(dt, B, num_leave_compute=3, leave_threshold=1, max_turn=T, tau=10.0, gamma_exposure=10.0, version="v1")
-    p = lstmcase.lstm_param_dict(U, I, seed=2, S=S, nlayers=L)
-    trk = DeviceLstmTracker({k: v.float().cuda().contiguous() for k, v in p.items()}, U, I, B, T, dim_state=S, nlayers=L)
-    arrs = policycase.random_weights(np.random.RandomState(2), I)
-    pol = DevicePolicy({rolloutcase.POLICY_NAMES[k]: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)).cuda() for k, v in arrs.items()}, I)
-    return DeviceRollout(env, trk, pol, **rollout_kw), p
-
-
-def stepwise(ro, users, *, greedy=False, remove=False, force_length=0):
-    """The collect, one public entry point at a time from Python (DeviceEnv.reset / step, DevicePolicy.sample / greedy, DeviceLstmTracker.init / step)."""
-    env, trk, pol = ro.env, ro.tracker, ro.policy
-    B = env.n_env
-    dev = env.device
-    obs = torch.zeros((T + 1, B, S), device=dev)
-    act = torch.zeros((T, B), dtype=torch.int64, device=dev); rew = torch.zeros((T, B), dtype=torch.float64, device=dev)
-    done = torch.zeros((T, B), dtype=torch.uint8, device=dev); ctr = torch.zeros((T, B), dtype=torch.float64, device=dev)
-    logp = torch.zeros((T, B), device=dev); value = torch.zeros((T, B), device=dev)
-    visited = torch.zeros((B, (I + 31) // 32), dtype=torch.int32, device=dev) if remove else None
-    users_d = torch.as_tensor(users).to(dev, torch.int32)
-    env.reset(users_d)
-    trk.reset()
-    trk.init(users_d, out=obs[0], out_stride=S)
-    rows = torch.arange(B, device=dev)
-    for t in range(T):
-        kw = dict(visited=visited, skip=env.done, act_out=act[t], logp_out=logp[t], value_out=value[t])
-        if greedy:
-            pol.greedy(obs[t], **kw)
-        else:
-            pol.sample(obs[t], seed=SEED, rng_step=RNG_BASE + t, **kw)
-        if remove:
-            ok = act[t] >= 0
-            a = act[t].clamp(min=0)
-            bit = torch.ones_like(a) << (a & 31)
-            bit = torch.where(bit >= 2 ** 31, bit - 2 ** 32, bit).to(torch.int32)
-            visited[rows[ok], (a >> 5)[ok]] |= bit[ok]
-        _, r, d, c, _ = env.step(act[t])
-        if force_length > 0:
-            fd = 1 if t + 1 >= force_length else 0
-            ok = act[t] >= 0
-            env.done[ok] = fd
-            d[ok] = fd
-        rew[t], done[t], ctr[t] = r, d, c
-        trk.step(act[t], r, out=obs[t + 1], out_stride=S)
-    return dict(obs=obs, act=act, rew=rew, done=done, logp=logp, value=value, ctr=ctr, lengths=env.turn.clone())
-
-
-def assert_same(ro, lengths, want):
-    for k in ("obs", "act", "rew", "done", "logp", "value", "ctr"):
-        assert torch.equal(getattr(ro.traj, k), want[k]), k
-    assert torch.equal(lengths, want["lengths"])
-
-
-def check_contract(ro, lengths):
-    """after an env's done: act -1, rew 0; before: a valid item"""
-    act, rew, done = ro.traj.act.cpu().numpy(), ro.traj.rew.cpu().numpy(), ro.traj.done.cpu().numpy()
-    ln = lengths.cpu().numpy()
-    for b in range(act.shape[1]):
-        assert 1 <= ln[b] <= T
-        assert (act[:ln[b], b] >= 0).all() and (act[:ln[b], b] < I).all()
-        assert done[ln[b] - 1, b] == 1 and (done[:ln[b] - 1, b] == 0).all()
-        assert (act[ln[b]:, b] == -1).all() and (rew[ln[b]:, b] == 0).all() and (done[ln[b]:, b] == 1).all()
-
-
-def check_against_float64(ro, p, users, lengths):
-    """the independent check: the float64 restatement, teacher-forced on the device's users / acts / rews, reproduces traj.obs"""
-    act = ro.traj.act.cpu().numpy().T.copy(); rew = ro.traj.rew.cpu().numpy().T.copy()
-    ln = lengths.cpu().numpy()
-    s64 = lstm_host.states(lstm_host.cast_params(p, torch.float64), users, act, rew, L).numpy()
-    s32 = lstm_host.states(lstm_host.cast_params(p, torch.float32), users, act, rew, L).numpy()
-    live = np.arange(T + 1)[None, :] <= ln[:, None]      # an env of length n has states 0 .. n
-    got = ro.traj.obs.cpu().numpy().transpose(1, 0, 2)
-    scale = np.abs(s64[live]).max()
-    err, err32 = np.abs(got[live] - s64[live]).max() / scale, np.abs(s32[live] - s64[live]).max() / scale
-    bar = lstmcase.bar_for(lstmcase.STATE_BAR, err32)
-    print(f"rollout obs B={len(ln)}: device {err:.3e}  float32 restatement {err32:.3e}  bar {bar:.3e}")
-    assert err <= bar
 
 
 @pytest.mark.parametrize("B", [6, 70])
 @pytest.mark.parametrize("mode", ["sampled", "greedy", "remove", "force"])
-def test_collect_equals_the_steps_issued_one_at_a_time(tables, B, mode):
-    kw = dict(remove=dict(remove_recommended_ids=True), force=dict(force_length=5)).get(mode, {})
-    users = np.random.RandomState(B).randint(0, U, B)
-    ro, p = build_stack(tables, B, **kw)
-    ref_ro, _ = build_stack(tables, B, **kw)
-    want = stepwise(ref_ro, users, greedy=mode == "greedy", remove=mode == "remove", force_length=5 if mode == "force" else 0)
-    lengths = ro.collect(torch.as_tensor(users), seed=SEED, rng_base=RNG_BASE, greedy=mode == "greedy")
-    assert_same(ro, lengths, want)
-    check_contract(ro, lengths)
-    check_against_float64(ro, p, users, lengths)
-    act, ln = ro.traj.act.cpu().numpy(), lengths.cpu().numpy()
-    if mode == "remove":
-        for b in range(B):
-            a = act[:ln[b], b]
-            assert len(set(a.tolist())) == len(a), f"env {b} lists an item twice"
-    if mode == "force":
-        assert (ln == 5).all()
-    # a second collect on the same objects: every entry is rewritten, nothing is left over from the first
-    lengths2 = ro.collect(torch.as_tensor(users), seed=SEED, rng_base=RNG_BASE, greedy=mode == "greedy")
-    live = torch.arange(T + 1, device="cuda")[:, None] <= lengths[None, :].to(torch.int64)
-    assert torch.equal(lengths2, lengths) and torch.equal(ro.traj.act, want["act"]) and torch.equal(ro.traj.obs[live], want["obs"][live])
+def test_collect_equals_the_steps_issued_one_at_a_time(tables, B, mode):  # noqa: F811
+    checks.collect_equals_the_steps_issued_one_at_a_time(tables, SLOT, B, mode)
 
 
-def test_harness_noise_is_the_sampler_with_that_noise(tables):
-    B = 6
-    users = np.random.RandomState(1).randint(0, U, B)
-    ro, p = build_stack(tables, B)
-    g = -np.log(np.random.RandomState(3).exponential(size=(T, B, I))).astype(np.float32)
-    lengths = ro.collect(torch.as_tensor(users), gumbel=g)
-    ref_ro, _ = build_stack(tables, B)
-    env, trk, pol = ref_ro.env, ref_ro.tracker, ref_ro.policy
-    users_d = torch.as_tensor(users).to("cuda", torch.int32)
-    env.reset(users_d); trk.reset()
-    obs = trk.init(users_d)
-    gd = torch.as_tensor(g).cuda()
-    for t in range(T):
-        act, logp, value = pol.sample(obs, gumbel=gd[t], skip=env.done)
-        assert torch.equal(act, ro.traj.act[t]) and torch.equal(logp, ro.traj.logp[t])
-        _, r, d, c, _ = env.step(act)
-        nxt = torch.zeros_like(obs)
-        trk.step(act, r, out=nxt, out_stride=S)
-        obs = nxt
-    check_contract(ro, lengths)
+def test_harness_noise_is_the_sampler_with_that_noise(tables):  # noqa: F811
+    checks.harness_noise_is_the_sampler_with_that_noise(tables, SLOT)
 
 
-def test_what_is_not_built_is_refused(tables):
-    from cirs_hip.rollout import DeviceRollout
-    ro, _ = build_stack(tables, 6)
-    with pytest.raises(NotImplementedError, match="online-reward"):
-        DeviceRollout(ro.env, ro.tracker, ro.policy, online=object())
-    with pytest.raises(NotImplementedError, match="sync_every"):
-        ro.collect(torch.zeros(6, dtype=torch.int64), sync_every=2)
-    with pytest.raises(NotImplementedError, match=r"run_steps.*use collect\(\)"):
-        ro.run_steps(0, 1, SEED, RNG_BASE)
-    import importlib.util
-    import os
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("cirs_rl_kuaishou_synth", os.path.join(root, "examples", "cirs_rl_kuaishou_synth.py"))
-    ex = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ex)
-    args = ex.get_args(["--n-users", "60", "--n-items", "70", "--training-num", "4", "--max_turn", "6", "--tracker", "lstm"])
-    tab, train_envs, st, policy, coll = ex.build(args)
-    from core.collector import Collector
-    with pytest.raises(ValueError, match="dropout_redraw"):
-        Collector(policy, train_envs, preprocess_fn=st.build_state, dropout_redraw=True)
+def test_what_is_not_built_is_refused(tables):  # noqa: F811
+    checks.what_is_not_built_is_refused(tables, SLOT)

@@ -219,7 +219,7 @@ def device_tracker(c, p):
 
 
 def replay(trk, users, acts, rews, lens, mode, pad=0):
-    """test_gpu_gru_tracker.replay in this tracker's terms (an env may have no row at all; the state buffer may have spare columns): reset / init /
+    """slotcase.replay in this tracker's terms (an env may have no row at all; the state buffer may have spare columns): reset / init /
     step, teacher-forced, env b gets positions 0 .. lens[b] - 1.  Finished envs are dropped through env_ids (the live ones only, in descending order)
     or stay in the batch and are marked (skip on even steps, item -1 on odd ones).  Every call writes into a NaN-filled buffer of S + pad columns:
     rows of finished envs and the spare columns must keep the NaN.  Returns states [B, T + 1, S], NaN where no state was produced."""
