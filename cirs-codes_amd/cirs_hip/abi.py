@@ -134,6 +134,24 @@ class CaserState(C.Structure):      # cirs_caser_state
     _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+NEXTITNET_MAX_BLOCKS = 4
+
+
+class NextItNetCfg(C.Structure):    # cirs_nextitnet_cfg
+    _fields_ = [("n_users", C.c_int32), ("n_items", C.c_int32), ("dim_model", C.c_int32), ("dim_state", C.c_int32), ("n_blocks", C.c_int32),
+                ("max_len", C.c_int32), ("n_env", C.c_int32), ("dilations", C.c_int32 * NEXTITNET_MAX_BLOCKS)]
+
+
+class NextItNetWeights(C.Structure):    # cirs_nextitnet_weights / cirs_nextitnet_grads (same layout)
+    _fields_ = ([(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b")] +
+                [(k, C.c_void_p * NEXTITNET_MAX_BLOCKS) for k in ("conv_w", "conv_b", "ln_w", "ln_b")] +
+                [(k, C.c_void_p) for k in ("dec_w", "dec_b")])
+
+
+class NextItNetState(C.Structure):  # cirs_nextitnet_state
+    _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -432,6 +450,16 @@ SIGNATURES = {
     "cirs_rollout_collect_caser": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(CaserCfg), C.POINTER(CaserWeights),
                                              C.POINTER(CaserState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                              C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_nextitnet_tracker_init": (C.c_int, [C.POINTER(NextItNetCfg), C.POINTER(NextItNetWeights), C.POINTER(NextItNetState), _P, _P, C.c_int32, _P,
+                                              C.c_int64, _P]),
+    "cirs_nextitnet_tracker_step": (C.c_int, [C.POINTER(NextItNetCfg), C.POINTER(NextItNetWeights), C.POINTER(NextItNetState), _P, _P, _P, _P, C.c_int32,
+                                              _P, C.c_int64, _P]),
+    "cirs_nextitnet_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(NextItNetCfg), C.c_int32]),
+    "cirs_nextitnet_tracker_backward": (C.c_int, [C.POINTER(NextItNetCfg), C.POINTER(NextItNetWeights), C.POINTER(NextItNetState), _P, _P, _P, _P, _P, _P,
+                                                  _P, C.c_int32, _P, C.POINTER(NextItNetWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_nextitnet": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(NextItNetCfg),
+                                                 C.POINTER(NextItNetWeights), C.POINTER(NextItNetState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights),
+                                                 C.POINTER(Traj), C.c_int32, _P, C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

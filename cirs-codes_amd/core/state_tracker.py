@@ -1,13 +1,14 @@
 """StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
-there), StateTrackerAvg (a pooled window over the last items; no counterpart there) and StateTrackerCaser (Caser's convolutions over that
-window; no counterpart there either) on the device engines.
+there), StateTrackerAvg (a pooled window over the last items; no counterpart there), StateTrackerCaser (Caser's convolutions over that
+window; no counterpart there either) and StateTrackerNextItNet (NextItNet's dilated causal convolutions over the item slots; no counterpart
+either) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
 buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
-LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions) and the gradient arrives through
-cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward (no
-autograd graph)."""
+LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions, csrc/nextitnet_tracker.hip: the dilated
+blocks) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward /
+cirs_avg_tracker_backward / cirs_caser_tracker_backward / cirs_nextitnet_tracker_backward (no autograd graph)."""
 import numpy as np
 import torch
 from torch import nn
@@ -17,6 +18,7 @@ from cirs_hip.caser_tracker import DeviceCaserTracker, caser_param_shapes, check
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
+from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, check_nextitnet_shape, init_nextitnet_tracker_params, nextitnet_param_shapes
 from cirs_hip.tracker import DeviceTracker, flat_tracker_params, tracker_param_shapes
 
 
@@ -157,7 +159,7 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg and StateTrackerCaser share: StateTrackerTransformer's constructor keywords (a
+    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser and StateTrackerNextItNet share: StateTrackerTransformer's constructor keywords (a
     script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
     with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
     module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
@@ -265,3 +267,23 @@ class StateTrackerCaser(_RecurrentStateTracker):
         if training and self.dropout_p > 0:
             raise ValueError("StateTrackerCaser: dropout on the concatenation is not built (dropout > 0 in training mode); use dropout=0.0 or "
                              "call .eval()")
+
+
+class StateTrackerNextItNet(_RecurrentStateTracker):
+    """The dilated-convolution tracker: the same input slots, NextItNet's residual blocks -- nn.Conv1d(32, 32, 3, dilation=d_l) with causal
+    left padding, nn.LayerNorm(32), ReLU on a residual branch -- over the item slots, h_p = x_0 + the top block's last position, the same
+    decoder (the reference has no counterpart).  StateTrackerTransformer's constructor keywords plus dilations and
+    kernel_size; nhead, d_hid, nlayers and dropout are accepted and unused (the model has no dropout site).  A _RecurrentStateTracker to
+    whatever asks: the engine surface, the collect, every refusal."""
+    CELL, ENGINE, param_shapes, init_params = "NextItNet", DeviceNextItNetTracker, nextitnet_param_shapes, init_nextitnet_tracker_params
+
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len, dilations=(1, 2, 4), kernel_size=3):
+        check_nextitnet_shape(dim_model, dim_state, dilations, kernel_size, max_len)
+        self.dilations, self.kernel_size = tuple(int(d) for d in dilations), int(kernel_size)
+        self.dropout_p, self.nlayers = 0.0, 0
+
+    def _model_kw(self):
+        return dict(dilations=self.dilations)
+
+    def _engine_kw(self):
+        return dict(dilations=self.dilations, kernel_size=self.kernel_size)

@@ -925,6 +925,99 @@ int cirs_rollout_collect_caser(const cirs_env_cfg* env_cfg, const cirs_env_table
                                int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, dilated causal convolutions: StateTrackerNextItNet (csrc/nextitnet_tracker.hip)
+ * The reference has no counterpart; the model is defined here (NextItNet: a stack of residual blocks of dilated causal 1-D convolutions
+ * of width 3 over the item slots; no max-pool, nothing carried):
+ *   inputs  the other trackers' slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *           no sqrt(D) scale, no positional encoding
+ *   blocks  y^{-1}_t = x_t  (t >= 1: item slots only; x_0 is never convolved)
+ *           c^l_t = b_l + sum_{j=0..2} W_l[:,:,j] y^{l-1}_{t-(2-j) d_l}     with y^{l-1}_s = 0 for s < 1: zero padding at EVERY layer's
+ *                   input, not values computed from padding  (fp32; taps j ascending, channels ascending inside a tap)
+ *           n^l_t = LayerNorm_l(c^l_t) over the 32 channels  (eps 1e-5, biased variance: the mean, then the variance of the centred values)
+ *           y^l_t = y^{l-1}_t + relu(n^l_t)
+ *   state   h_p = x_0 + y^{n-1}_p (p >= 1), h_0 = x_0;  s_p = decoder(h_p)
+ * Only the last R = 1 + 2 sum_l d_l item slots reach position p; they are read anew from the stored slots at every step: position p depends
+ * on them and on x_0 only.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, kernel width 3, 1 <= n_blocks <= 4, every dilation in 1..4 (any order),
+ * sum of the dilations <= 7 (R <= 15: one 16-row tile), max_len <= 4096.  No dropout site.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_NEXTITNET_MAX_BLOCKS 4
+#define CIRS_NEXTITNET_MAX_DILATION 4
+#define CIRS_NEXTITNET_MAX_DILATION_SUM 7
+
+typedef struct cirs_nextitnet_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t n_blocks;  /* residual blocks, 1..4 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+    int32_t dilations[CIRS_NEXTITNET_MAX_BLOCKS]; /* d_l, each in 1..4, sum <= 7; entries >= n_blocks are ignored */
+} cirs_nextitnet_cfg;
+
+typedef struct cirs_nextitnet_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float* conv_w[CIRS_NEXTITNET_MAX_BLOCKS]; /* blocks.<l>.conv.weight [D,D,3] (out, in, tap) */
+    const float* conv_b[CIRS_NEXTITNET_MAX_BLOCKS]; /* blocks.<l>.conv.bias [D] */
+    const float* ln_w[CIRS_NEXTITNET_MAX_BLOCKS];   /* blocks.<l>.ln.weight [D] */
+    const float* ln_b[CIRS_NEXTITNET_MAX_BLOCKS];   /* blocks.<l>.ln.bias [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_nextitnet_weights;
+
+typedef struct cirs_nextitnet_state {
+    float* x_hist; /* [B, max_len, D] the input slots: the blocks of every step and the backward read them */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_nextitnet_state;
+
+typedef struct cirs_nextitnet_grads { /* same tensors, same order as cirs_nextitnet_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float* conv_w[CIRS_NEXTITNET_MAX_BLOCKS];
+    float* conv_b[CIRS_NEXTITNET_MAX_BLOCKS];
+    float* ln_w[CIRS_NEXTITNET_MAX_BLOCKS];
+    float* ln_b[CIRS_NEXTITNET_MAX_BLOCKS];
+    float *dec_w, *dec_b;
+} cirs_nextitnet_grads;
+
+/* cirs_avg_tracker_init / cirs_avg_tracker_step for the NextItNet tracker, same argument conventions: env_ids (nullable, [n]) = the env of
+ * row j (NULL: j); init writes slot 0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of range
+ * (item < 0: the env finished), a never-initialised or a full history are left untouched: neither x_hist, len nor their row of state_out
+ * is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes is refused (CIRS_E_INVALID / CIRS_E_UNSUPPORTED)
+ * with a message that names the member, before any pointer is read. */
+int cirs_nextitnet_tracker_init(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, cirs_nextitnet_state* st,
+                                const int32_t* users, const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride,
+                                void* stream);
+int cirs_nextitnet_tracker_step(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, cirs_nextitnet_state* st,
+                                const int64_t* items, const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n,
+                                float* state_out, int64_t state_stride, void* stream);
+
+/* cirs_avg_tracker_backward for the NextItNet tracker.  No sequential pass: the forward of every buffer row is recomputed from the stored
+ * slots (every block's input, normalised values and inverse standard deviation are kept), the decoder stage is the other trackers', then per
+ * row the blocks from the top down (ReLU, LayerNorm, the three taps transposed, the residual path) give a gradient per window slot, which is
+ * folded into dX[b,k] in ascending p (dX[b,0] = sum_p dH[b,p]); then the slot stage of the recurrent trackers.  Same arguments: users[B];
+ * act / rew are the time-major trajectory rows [T,B]; row_env / row_t / offsets / lens describe the buffer rows (env-major, see
+ * cirs_ppo_prepare); dstate [T+1,B,S] = d loss / d obs; of st only x_hist is read.  Every gradient tensor is OVERWRITTEN.  No float atomics;
+ * every reduction has a fixed order, so two calls give the same bits.  A workspace smaller than
+ * cirs_nextitnet_tracker_backward_workspace_bytes(cfg, n_rows), or one not 16-byte aligned, is refused before any launch. */
+int64_t cirs_nextitnet_tracker_backward_workspace_bytes(const cirs_nextitnet_cfg* cfg, int32_t n_rows);
+int cirs_nextitnet_tracker_backward(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, const cirs_nextitnet_state* st,
+                                    const int32_t* users, const int64_t* act, const double* rew, const int32_t* row_env,
+                                    const int32_t* row_t, const int32_t* offsets, const int32_t* lens, int32_t n_rows,
+                                    const float* dstate, const cirs_nextitnet_grads* grads, void* workspace, int64_t workspace_bytes,
+                                    void* stream);
+
+/* cirs_rollout_collect_gru with a NextItNet tracker: the same launch sequence (one loop serves the five, csrc/rollout.hip) with
+ * cirs_nextitnet_tracker_init / cirs_nextitnet_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_nextitnet(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                   const cirs_nextitnet_cfg* trk_cfg, const cirs_nextitnet_weights* trk_w,
+                                   cirs_nextitnet_state* trk_st, const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w,
+                                   const cirs_traj* traj, int32_t n_env, const int32_t* users, uint64_t seed, uint32_t rng_base,
+                                   uint32_t* visited, int32_t force_length, int32_t greedy, const float* gumbel, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),
