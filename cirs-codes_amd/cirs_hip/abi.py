@@ -152,6 +152,22 @@ class NextItNetState(C.Structure):  # cirs_nextitnet_state
     _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+STAMP_MAX_WINDOW = 16
+
+
+class StampCfg(C.Structure):        # cirs_stamp_cfg
+    _fields_ = list(AvgCfg._fields_)
+
+
+class StampWeights(C.Structure):    # cirs_stamp_weights / cirs_stamp_grads (same layout)
+    _fields_ = [(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b", "attn_b", "w1", "w2", "w3", "w0",
+                                          "mlp_a_w", "mlp_a_b", "mlp_b_w", "mlp_b_b", "dec_w", "dec_b")]
+
+
+class StampState(C.Structure):      # cirs_stamp_state
+    _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -460,6 +476,14 @@ SIGNATURES = {
     "cirs_rollout_collect_nextitnet": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(NextItNetCfg),
                                                  C.POINTER(NextItNetWeights), C.POINTER(NextItNetState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights),
                                                  C.POINTER(Traj), C.c_int32, _P, C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_stamp_tracker_init": (C.c_int, [C.POINTER(StampCfg), C.POINTER(StampWeights), C.POINTER(StampState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_stamp_tracker_step": (C.c_int, [C.POINTER(StampCfg), C.POINTER(StampWeights), C.POINTER(StampState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_stamp_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(StampCfg), C.c_int32]),
+    "cirs_stamp_tracker_backward": (C.c_int, [C.POINTER(StampCfg), C.POINTER(StampWeights), C.POINTER(StampState), _P, _P, _P, _P, _P, _P, _P, C.c_int32,
+                                              _P, C.POINTER(StampWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_stamp": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(StampCfg), C.POINTER(StampWeights),
+                                             C.POINTER(StampState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                             C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -1,14 +1,15 @@
 """StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
 there), StateTrackerAvg (a pooled window over the last items; no counterpart there), StateTrackerCaser (Caser's convolutions over that
-window; no counterpart there either) and StateTrackerNextItNet (NextItNet's dilated causal convolutions over the item slots; no counterpart
-either) on the device engines.
+window; no counterpart there either), StateTrackerNextItNet (NextItNet's dilated causal convolutions over the item slots; no counterpart
+either) and StateTrackerSTAMP (STAMP's attention pool over that window; no counterpart either) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
 buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
 LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions, csrc/nextitnet_tracker.hip: the dilated
-blocks) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward /
-cirs_avg_tracker_backward / cirs_caser_tracker_backward / cirs_nextitnet_tracker_backward (no autograd graph)."""
+blocks, csrc/stamp_tracker.hip: the attention pool) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward /
+cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward / cirs_nextitnet_tracker_backward /
+cirs_stamp_tracker_backward (no autograd graph)."""
 import numpy as np
 import torch
 from torch import nn
@@ -19,6 +20,7 @@ from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
 from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, check_nextitnet_shape, init_nextitnet_tracker_params, nextitnet_param_shapes
+from cirs_hip.stamp_tracker import DeviceStampTracker, check_stamp_shape, init_stamp_tracker_params, stamp_param_shapes
 from cirs_hip.tracker import DeviceTracker, flat_tracker_params, tracker_param_shapes
 
 
@@ -159,7 +161,7 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser and StateTrackerNextItNet share: StateTrackerTransformer's constructor keywords (a
+    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet and StateTrackerSTAMP share: StateTrackerTransformer's constructor keywords (a
     script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
     with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
     module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
@@ -287,3 +289,23 @@ class StateTrackerNextItNet(_RecurrentStateTracker):
 
     def _engine_kw(self):
         return dict(dilations=self.dilations, kernel_size=self.kernel_size)
+
+
+class StateTrackerSTAMP(_RecurrentStateTracker):
+    """The attention-pool tracker: the same input slots, STAMP's short-term attention over the window of the last `window_size` item slots --
+    a general-interest query (the window mean), a last-click query (the newest slot), a sigmoid gate network without softmax, the read-out
+    tanh(A m_a + b_A) * tanh(B m_t + b_B) -- h_p = x_0 + that product, the same decoder (the reference has no counterpart).
+    StateTrackerTransformer's constructor keywords plus window_size (1..16); nhead, d_hid, nlayers and dropout are accepted and unused (the
+    model has no dropout site).  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
+    CELL, ENGINE, param_shapes, init_params = "STAMP", DeviceStampTracker, stamp_param_shapes, init_stamp_tracker_params
+
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len, window_size=10):
+        check_stamp_shape(dim_model, dim_state, window_size, max_len)
+        self.window_size = int(window_size)
+        self.dropout_p, self.nlayers = 0.0, 0
+
+    def _model_kw(self):
+        return {}      # the window has no parameters
+
+    def _engine_kw(self):
+        return dict(window_size=self.window_size)

@@ -119,7 +119,7 @@ extern "C" int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const ci
                         nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, users, true);
 }
 
-// cirs_rollout_collect with a recurrent or a window tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip): the unfused sequence of
+// cirs_rollout_collect with a recurrent or a window tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip, stamp_tracker.hip): the unfused sequence of
 // rollout_impl's online-reward branch without the scorer, built from the public entry points -- about five launches per vector step against the fused
 // Transformer collect's two.  One loop for all of them: `init` / `step` are the tracker's entry points, `what` names it in the messages.
 namespace cirs {
@@ -224,6 +224,15 @@ extern "C" int cirs_rollout_collect_nextitnet(const cirs_env_cfg* env_cfg, const
     return cirs::collect_recurrent("nextitnet", cirs_nextitnet_tracker_init, cirs_nextitnet_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st,
                                    pol_cfg, pol_w, traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes,
                                    stream);
+}
+
+extern "C" int cirs_rollout_collect_stamp(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                          const cirs_stamp_cfg* trk_cfg, const cirs_stamp_weights* trk_w, cirs_stamp_state* trk_st,
+                                          const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                          const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                          int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    return cirs::collect_recurrent("stamp", cirs_stamp_tracker_init, cirs_stamp_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w,
+                                   traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cirs_rollout_steps(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,

@@ -1018,6 +1018,91 @@ int cirs_rollout_collect_nextitnet(const cirs_env_cfg* env_cfg, const cirs_env_t
                                    int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, attention pool over the window: StateTrackerSTAMP (csrc/stamp_tracker.hip)
+ * The reference has no counterpart; the model is defined here (STAMP, Liu et al., KDD 2018: a general-interest query, a last-click query, a
+ * small gate network without softmax, a multiplicative read-out; nothing carried):
+ *   inputs     the other trackers' slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *              no sqrt(D) scale, no positional encoding
+ *   window     n_p = min(window, p), the slots k = p - n_p + 1 .. p  (p >= 1)
+ *              m_s = (x_{p-n_p+1} + ... + x_p) / n_p   (fp32, k ascending, then ONE division by float(n_p): the Avg tracker's m_p, same bits)
+ *              m_t = x_p
+ *   attention  c   = W2 m_t + W3 m_s + b_a
+ *              e_k = w0 . sigmoid(W1 x_k + c)          (a scalar per window slot; no softmax)
+ *              m_a = sum_k e_k x_k                     (k ascending)
+ *   read-out   h_s = tanh(A m_a + b_A),  h_t = tanh(B m_t + b_B);  h_p = x_0 + h_s * h_t,  h_0 = x_0;  s_p = decoder(h_p)
+ * The window is read anew from the stored slots at every step: position p depends on it and on x_0 only; a slot older than the window
+ * does not reach it.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, 1 <= window <= 16 (one 16-row tile), max_len <= 4096.  No dropout site.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_STAMP_MAX_WINDOW 16
+
+typedef struct cirs_stamp_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t window;    /* W in 1..16: item slots in the window */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_stamp_cfg;
+
+typedef struct cirs_stamp_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float* attn_b;                  /* attn.bias [D] (a module's own tensor: listed before its children's, as state_dict lists it) */
+    const float *w1, *w2, *w3;            /* attn.w1.weight, attn.w2.weight, attn.w3.weight [D,D] */
+    const float* w0;                      /* attn.w0.weight [1,D] */
+    const float *mlp_a_w, *mlp_a_b;       /* mlp_a [D,D], [D] */
+    const float *mlp_b_w, *mlp_b_b;       /* mlp_b [D,D], [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_stamp_weights;
+
+typedef struct cirs_stamp_state {
+    float* x_hist; /* [B, max_len, D] the input slots: the window of every step and the backward read them */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_stamp_state;
+
+typedef struct cirs_stamp_grads { /* same tensors, same order as cirs_stamp_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float *attn_b, *w1, *w2, *w3, *w0, *mlp_a_w, *mlp_a_b, *mlp_b_w, *mlp_b_b;
+    float *dec_w, *dec_b;
+} cirs_stamp_grads;
+
+/* cirs_avg_tracker_init / cirs_avg_tracker_step for the STAMP tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of range
+ * (item < 0: the env finished), a never-initialised or a full history are left untouched: neither x_hist, len nor their row of state_out
+ * is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes (window outside 1..16 among them) is refused
+ * (CIRS_E_INVALID / CIRS_E_UNSUPPORTED) with a message that names the member, before any pointer is read. */
+int cirs_stamp_tracker_init(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, cirs_stamp_state* st, const int32_t* users,
+                            const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_stamp_tracker_step(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, cirs_stamp_state* st, const int64_t* items,
+                            const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                            int64_t state_stride, void* stream);
+
+/* cirs_avg_tracker_backward for the STAMP tracker.  No sequential pass: the forward of every buffer row is recomputed from the stored slots
+ * (the window tile, the sigmoids, e, m_s, m_a, h_s and h_t are kept), the decoder stage is the other trackers', then per row the product,
+ * the two tanh, m_a (both factors), the sigmoid tile, W1 and c give a gradient per window slot, which is folded into dX[b,k] in ascending
+ * p (dX[b,0] = sum_p dH[b,p]); then the slot stage of the recurrent trackers.  Same arguments: users[B]; act / rew are the time-major
+ * trajectory rows [T,B]; row_env / row_t / offsets / lens describe the buffer rows (env-major, see cirs_ppo_prepare); dstate [T+1,B,S] =
+ * d loss / d obs; of st only x_hist is read.  Every gradient tensor is OVERWRITTEN.  No float atomics; every reduction has a fixed order,
+ * so two calls give the same bits.  A workspace smaller than cirs_stamp_tracker_backward_workspace_bytes(cfg, n_rows), or one not 16-byte
+ * aligned, is refused before any launch. */
+int64_t cirs_stamp_tracker_backward_workspace_bytes(const cirs_stamp_cfg* cfg, int32_t n_rows);
+int cirs_stamp_tracker_backward(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, const cirs_stamp_state* st, const int32_t* users,
+                                const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                                const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                                const cirs_stamp_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with a STAMP tracker: the same launch sequence (one loop serves the six, csrc/rollout.hip) with
+ * cirs_stamp_tracker_init / cirs_stamp_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_stamp(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                               const cirs_stamp_cfg* trk_cfg, const cirs_stamp_weights* trk_w, cirs_stamp_state* trk_st,
+                               const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                               const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                               int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),

@@ -1,19 +1,20 @@
-"""The recurrent state trackers (GRU, LSTM), the pooled-window one (Avg), the convolutional one (Caser) and the dilated-convolution one (NextItNet) against the
-Transformer one at the benchmark shapes:
+"""The recurrent state trackers (GRU, LSTM), the pooled-window one (Avg), the convolutional one (Caser), the dilated-convolution one (NextItNet) and the
+attention-pool one (STAMP) against the Transformer one at the benchmark shapes:
     python tools/probe_gru_tracker.py [--workload c2|c3] [--reps 60]
 
-Nine trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
+Ten trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
 with 2 layers, the Avg tracker with a window of 3 and of 10, the Caser tracker with a window of 10 and heights (2, 3, 4),
-the NextItNet tracker with dilations (1, 2, 4).  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
+the NextItNet tracker with dilations (1, 2, 4), the STAMP tracker with a window of 10.  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
   step_us        one tracker step alone (one launch, all envs) at positions 1, 15 and 30 -- a device-event pair around the launch
   collect_ms     one DeviceRollout.collect (what Collector.collect runs on the device): the fused two-launch sequence for the Transformer,
-                 cirs_rollout_collect_gru's / _lstm's / _avg's / _caser's / _nextitnet's unfused sequence for the others -- device events around the call, enqueued behind a spin kernel (the host
+                 cirs_rollout_collect_gru's / _lstm's / _avg's / _caser's / _nextitnet's / _stamp's unfused sequence for the others -- device events around the call, enqueued behind a spin kernel (the host
                  ahead of the device, as in the training loop); collect_idle_ms: the same from an idle stream (the host's launch rate counts)
   bwd_adam_ms    the tracker backward + Adam step of one update (the learner's d loss / d obs as upstream gradient) -- device events
 Medians over --reps repetitions after a warm-up, min and max alongside; lstm_over_gru: the ratios of those medians per layer count;
 avg_over_gru: the Avg tracker's over the one-layer GRU's, per window; caser_over: the Caser tracker's over the one-layer GRU's and over the Avg tracker's at
 the same window (the two step kernels share everything except the window arithmetic); nextitnet_over: the NextItNet tracker's over the Caser tracker's and
-over the one-layer GRU's.  One JSON line.
+over the one-layer GRU's; stamp_over: the STAMP tracker's over the Avg tracker's and over the Caser tracker's at the same window (the yardsticks on either
+side of it).  One JSON line.
 --trace: no timing, a few collects and backwards per tracker -- the run to put under `rocprofv3 --kernel-trace --stats -- python ...` for kernel times
 (tracing slows the host: never in the same run as the timings above)."""
 import argparse
@@ -33,6 +34,7 @@ from cirs_hip.gru_tracker import DeviceGruTracker, gru_param_shapes, init_gru_tr
 from cirs_hip.lstm_tracker import DeviceLstmTracker, init_lstm_tracker_params, lstm_param_shapes  # noqa: E402
 from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, init_nextitnet_tracker_params, nextitnet_param_shapes  # noqa: E402
 from cirs_hip.rollout import DeviceRollout  # noqa: E402
+from cirs_hip.stamp_tracker import DeviceStampTracker, init_stamp_tracker_params, stamp_param_shapes  # noqa: E402
 from cirs_hip.tracker import flat_tracker_params  # noqa: E402
 
 
@@ -70,6 +72,14 @@ def nextitnet_engine(wl, dilations, device):
     flat, views = flat_tracker_params(nextitnet_param_shapes(U, I, 32, 20, dilations), device=device,
                                       init=init_nextitnet_tracker_params(U, I, seed=2023, dilations=dilations))
     trk = DeviceNextItNetTracker(dict(views), U, I, B, T, dilations=dilations, device=device)
+    trk.enable_training(flat)
+    return trk
+
+
+def stamp_engine(wl, window, device):
+    U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
+    flat, views = flat_tracker_params(stamp_param_shapes(U, I, 32, 20), device=device, init=init_stamp_tracker_params(U, I, seed=2023))
+    trk = DeviceStampTracker(dict(views), U, I, B, T, window_size=window, device=device)
     trk.enable_training(flat)
     return trk
 
@@ -118,6 +128,8 @@ def main():
     variants["caser_w10"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
     trk = nextitnet_engine(wl, (1, 2, 4), device)
     variants["nextitnet_d124"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
+    trk = stamp_engine(wl, 10, device)
+    variants["stamp_w10"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
     users = torch.as_tensor(np.random.RandomState(0).randint(0, U, B)).to(device, torch.int32)
     items = torch.as_tensor(np.random.RandomState(1).randint(0, I, B)).to(device)
     rews = torch.rand(B, dtype=torch.float64, device=device)
@@ -197,6 +209,9 @@ def main():
     out["nextitnet_over"] = {base: {"step_us_30": round(out["trackers"]["nextitnet_d124"]["step_us"]["30"]["median"] / out["trackers"][base]["step_us"]["30"]["median"], 3),
                                     "collect_ms": round(med("nextitnet_d124", "collect_ms") / med(base, "collect_ms"), 3),
                                     "bwd_adam_ms": round(med("nextitnet_d124", "bwd_adam_ms") / med(base, "bwd_adam_ms"), 3)} for base in ("caser_w10", "gru_l1")}
+    out["stamp_over"] = {base: {"step_us_30": round(out["trackers"]["stamp_w10"]["step_us"]["30"]["median"] / out["trackers"][base]["step_us"]["30"]["median"], 3),
+                                "collect_ms": round(med("stamp_w10", "collect_ms") / med(base, "collect_ms"), 3),
+                                "bwd_adam_ms": round(med("stamp_w10", "bwd_adam_ms") / med(base, "bwd_adam_ms"), 3)} for base in ("avg_w10", "caser_w10")}
     print(json.dumps(out), flush=True)
 
 
