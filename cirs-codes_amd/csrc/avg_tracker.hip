@@ -14,10 +14,10 @@
 //   C  G = gather(dstate);  H = the pooled rows again from the stored slots (avg_rows_h: the decoder's weight gradient needs its input);
 //      dH = G W_dec and the decoder's weight gradient in one launch (rows_gemm + dw_gemm, as the GRU's stage C)
 //   W  avg_window_bwd: dX[b,0] = sum_p dH[b,p];  dX[b,k] = sum_{p=k}^{min(len_b-1, k+W-1)} dH[b,p] / float(n_p)   -- p ascending, every row on its own
-//   E  the slot stage of the recurrent trackers (recurrent.h: slot_bwd with input scale 1, ordered embedding scatter, slab partials in slab order)
+//   E  the slot stage of the recurrent trackers (slot_tracker.h: slot_bwd with input scale 1, ordered embedding scatter, slab partials in slab order)
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -153,32 +153,25 @@ struct AvgScratch : SlotScratch {
 static size_t avg_partial_floats(long R) { return dw_list_floats(R, 32, tD) + dw_list_floats(R, tD, tD) + dw_list_floats(R, tD, tD + 1); }
 
 static AvgScratch carve_avg(void* ws, const cirs_avg_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env;
+    Carver c(ws);
     AvgScratch s;
-    s.G = take((size_t)R * 32); s.H = take((size_t)R * tD); s.dH = take((size_t)R * tD); s.dX = take((size_t)R * tD);
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(avg_partial_floats(R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+    s.G = c.take((size_t)R * 32); s.H = c.take((size_t)R * tD); s.dH = c.take((size_t)R * tD); s.dX = c.take((size_t)R * tD);
+    carve_slots(c, s, R, cfg->n_env, avg_partial_floats(R));
+    *total_floats = c.total();
     return s;
 }
 
-static int validate_avg(const cirs_avg_cfg* cfg, const cirs_avg_weights* w) {
+// the cfg first and on its own: a cfg outside the fixed sizes is refused before any pointer is read
+static int validate_avg_cfg(const cirs_avg_cfg* cfg) {
     CIRS_REQUIRE(cfg, "avg tracker: cfg null");
     CIRS_REQUIRE(cfg->window >= 1, "avg tracker: window must be at least 1");
-    if (cfg->dim_model != tD) return fail(CIRS_E_UNSUPPORTED, "avg tracker: this build supports dim_model == 32");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= 32, "avg tracker: dim_state must be in 1..32");
-    CIRS_REQUIRE(cfg->max_len >= 1 && cfg->max_len <= 4096, "avg tracker: max_len out of range");
-    CIRS_REQUIRE(cfg->n_env >= 1 && cfg->n_users >= 1 && cfg->n_items >= 1, "avg tracker: n_env / n_users / n_items must be positive");
+    return validate_slot_cfg(cfg, "avg tracker");
+}
+
+static int validate_avg(const cirs_avg_cfg* cfg, const cirs_avg_weights* w) {
+    if (int rc = validate_avg_cfg(cfg)) return rc;
     CIRS_REQUIRE(w, "avg tracker: weights null");
-    CIRS_REQUIRE(w->emb_user && w->emb_item && w->ffn_user_w && w->ffn_user_b && w->gate_w && w->gate_b && w->dec_w && w->dec_b,
-                 "avg tracker: weight pointer null");
-    return CIRS_OK;
+    return validate_slot_weights(w, "avg tracker");
 }
 
 static int launch_avg_step(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, cirs_avg_state* st, const int32_t* users, const int64_t* items,
@@ -187,7 +180,7 @@ static int launch_avg_step(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, c
     // 10.5 KB of LDS and few registers: a CU could hold eight of these workgroups, and what a workgroup stages is 7 KB, so there is little to amortise.  Four
     // per CU (four wavefronts per SIMD, what the LDS reads need to reach their rate) is the cap: up to 8 x 4 x CUs envs every pair of envs has a wavefront of
     // its own, beyond that a workgroup walks several groups of eight.  Chosen from the structure, not tuned.
-    const int walks = std::max(1, cdiv(n, (long)kAvgEnvsPerWg * 4 * device_cu_count()));
+    const int walks = slot_walks(n, kAvgEnvsPerWg, 4);
     hipLaunchKernelGGL(avg_step_kernel, dim3(cdiv(n, (long)kAvgEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, *st, users, items, rew, env_ids, skip, n,
                        state_out, state_stride, walks);
     CIRS_CHECK_LAUNCH("avg_step_kernel");
@@ -198,29 +191,16 @@ static int launch_avg_step(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, c
 
 extern "C" int cirs_avg_tracker_init(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, cirs_avg_state* st, const int32_t* users,
                                      const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_avg(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_avg_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_avg, cirs::launch_avg_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_avg_tracker_step(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, cirs_avg_state* st, const int64_t* items, const double* rew,
                                      const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_avg(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_avg_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_avg, cirs::launch_avg_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_avg_tracker_backward_workspace_bytes(const cirs_avg_cfg* cfg, int32_t n_rows) {
-    if (!cfg || n_rows <= 0 || cfg->n_env <= 0) return 0;
-    size_t total = 0;
-    (void)cirs::carve_avg(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_avg_cfg, cirs::carve_avg, cfg, n_rows);
 }
 
 extern "C" int cirs_avg_tracker_backward(const cirs_avg_cfg* cfg, const cirs_avg_weights* w, const cirs_avg_state* st, const int32_t* users,
@@ -231,8 +211,7 @@ extern "C" int cirs_avg_tracker_backward(const cirs_avg_cfg* cfg, const cirs_avg
     if (int rc = validate_avg(cfg, w)) return rc;
     CIRS_REQUIRE(st && st->x_hist && users && act && rew && row_env && row_t && offsets && lens && dstate && grads && workspace, "null argument");
     CIRS_REQUIRE(n_rows > 0, "n_rows must be positive");
-    CIRS_REQUIRE(grads->emb_user && grads->emb_item && grads->ffn_user_w && grads->ffn_user_b && grads->gate_w && grads->gate_b && grads->dec_w && grads->dec_b,
-                 "avg tracker: gradient pointer null");
+    if (int rc = validate_slot_grads(grads, "avg tracker")) return rc;
     CIRS_REQUIRE(workspace_bytes >= cirs_avg_tracker_backward_workspace_bytes(cfg, n_rows), "workspace too small");
     CIRS_REQUIRE(((uintptr_t)workspace & 15) == 0, "workspace must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
@@ -246,5 +225,5 @@ extern "C" int cirs_avg_tracker_backward(const cirs_avg_cfg* cfg, const cirs_avg
                         tD, s);
     hipLaunchKernelGGL(avg_window_bwd, dim3(cdiv(R, 8)), dim3(256), 0, s, (const float*)sc.dH, row_env, row_t, offsets, lens, R, W, sc.dX);
     CIRS_CHECK_LAUNCH("avg tracker backward pooling");
-    return recurrent_slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

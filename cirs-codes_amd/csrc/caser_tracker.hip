@@ -20,11 +20,11 @@
 //      DC_i [R W, 16] and the patches of WIN [R W, 32 h_i] (patch t = rows t .. t + h_i - 1 of a window, contiguous)
 //   X  caser_window_bwd: dX[b,0] = sum_p dH[b,p];  dX[b,k] = sum_{p=k}^{min(len_b-1, k+W-1)} dWin_p[k-p+W-1]  -- p ascending, every row on its own, with
 //      dWin_p[j] = wv[j] dV_p + sum_i sum_f [0 <= j - arg < h_i] dO_p[i,f] Wh_i[f, j - arg]  (i, f ascending)
-//   E  the slot stage of the recurrent trackers (recurrent.h)
+//   E  the slot stage of the recurrent trackers (slot_tracker.h)
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <cmath>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -410,23 +410,17 @@ static size_t caser_partial_floats(const cirs_caser_cfg* cfg, long R) {
 }
 
 static CaserScratch carve_caser(void* ws, const cirs_caser_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env, W = cfg->window, nF = cF * cfg->n_heights;
+    Carver c(ws);
+    const long W = cfg->window, nF = cF * cfg->n_heights;
     CaserScratch s;
-    s.G = take((size_t)R * 32); s.H = take((size_t)R * tD); s.Z = take((size_t)R * tD); s.dH = take((size_t)R * tD); s.dX = take((size_t)R * tD);
-    s.DZ = take((size_t)R * tD); s.CAT = take((size_t)R * (nF + tD)); s.DO = take((size_t)R * nF); s.DVP = take((size_t)R * tD);
-    s.ARG = (int32_t*)take((size_t)R * nF);
-    s.VW = take((size_t)R * (W + 1)); s.ONES = take(R);
-    s.WIN = take((size_t)R * W * tD + 3 * tD);
-    s.DC = take((size_t)cfg->n_heights * R * W * cF);
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(caser_partial_floats(cfg, R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+    s.G = c.take((size_t)R * 32); s.H = c.take((size_t)R * tD); s.Z = c.take((size_t)R * tD); s.dH = c.take((size_t)R * tD); s.dX = c.take((size_t)R * tD);
+    s.DZ = c.take((size_t)R * tD); s.CAT = c.take((size_t)R * (nF + tD)); s.DO = c.take((size_t)R * nF); s.DVP = c.take((size_t)R * tD);
+    s.ARG = (int32_t*)c.take((size_t)R * nF);
+    s.VW = c.take((size_t)R * (W + 1)); s.ONES = c.take(R);
+    s.WIN = c.take((size_t)R * W * tD + 3 * tD);
+    s.DC = c.take((size_t)cfg->n_heights * R * W * cF);
+    carve_slots(c, s, R, cfg->n_env, caser_partial_floats(cfg, R));
+    *total_floats = c.total();
     return s;
 }
 
@@ -440,19 +434,14 @@ static int validate_caser_cfg(const cirs_caser_cfg* cfg) {
         CIRS_REQUIRE(i == 0 || cfg->heights[i] > cfg->heights[i - 1], "caser tracker: heights must be strictly ascending");
     }
     CIRS_REQUIRE(cfg->heights[cfg->n_heights - 1] <= cfg->window, "caser tracker: heights must not exceed window");
-    if (cfg->dim_model != tD) return fail(CIRS_E_UNSUPPORTED, "caser tracker: this build supports dim_model == 32");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= 32, "caser tracker: dim_state must be in 1..32");
-    CIRS_REQUIRE(cfg->max_len >= 1 && cfg->max_len <= 4096, "caser tracker: max_len out of range");
-    CIRS_REQUIRE(cfg->n_env >= 1 && cfg->n_users >= 1 && cfg->n_items >= 1, "caser tracker: n_env / n_users / n_items must be positive");
-    return CIRS_OK;
+    return validate_slot_cfg(cfg, "caser tracker");
 }
 
 static int validate_caser(const cirs_caser_cfg* cfg, const cirs_caser_weights* w) {
     if (int rc = validate_caser_cfg(cfg)) return rc;
     CIRS_REQUIRE(w, "caser tracker: weights null");
-    CIRS_REQUIRE(w->emb_user && w->emb_item && w->ffn_user_w && w->ffn_user_b && w->gate_w && w->gate_b && w->dec_w && w->dec_b && w->vert_w && w->vert_b &&
-                     w->fc_w && w->fc_b,
-                 "caser tracker: weight pointer null");
+    if (int rc = validate_slot_weights(w, "caser tracker")) return rc;
+    CIRS_REQUIRE(w->vert_w && w->vert_b && w->fc_w && w->fc_b, "caser tracker: weight pointer null");
     for (int i = 0; i < cfg->n_heights; ++i) CIRS_REQUIRE(w->conv_w[i] && w->conv_b[i], "caser tracker: bank weight pointer null");
     return CIRS_OK;
 }
@@ -462,7 +451,7 @@ static int launch_caser_step(const cirs_caser_cfg* cfg, const cirs_caser_weights
     CIRS_REQUIRE(st && st->x_hist && st->len, "caser tracker: state pointer null");
     // 54 KB of LDS: two workgroups per CU.  Up to 4 x 2 x CUs envs every env has a wavefront of its own, beyond that a workgroup walks several groups of
     // four and what it staged (35 KB of weights at the default shape) serves them all.  Chosen from the structure, not tuned.
-    const int walks = std::max(1, cdiv(n, (long)cEnvsPerWg * cWgPerCu * device_cu_count()));
+    const int walks = slot_walks(n, cEnvsPerWg, cWgPerCu);
     hipLaunchKernelGGL(caser_step_kernel, dim3(cdiv(n, (long)cEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, *st, users, items, rew, env_ids, skip, n,
                        state_out, state_stride, walks);
     CIRS_CHECK_LAUNCH("caser_step_kernel");
@@ -473,29 +462,16 @@ static int launch_caser_step(const cirs_caser_cfg* cfg, const cirs_caser_weights
 
 extern "C" int cirs_caser_tracker_init(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, cirs_caser_state* st, const int32_t* users,
                                        const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_caser(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_caser_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_caser, cirs::launch_caser_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_caser_tracker_step(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, cirs_caser_state* st, const int64_t* items, const double* rew,
                                        const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_caser(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_caser_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_caser, cirs::launch_caser_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_caser_tracker_backward_workspace_bytes(const cirs_caser_cfg* cfg, int32_t n_rows) {
-    if (n_rows <= 0 || cirs::validate_caser_cfg(cfg) != CIRS_OK) return 0;
-    size_t total = 0;
-    (void)cirs::carve_caser(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_caser_cfg, cirs::carve_caser, cfg, n_rows);
 }
 
 extern "C" int cirs_caser_tracker_backward(const cirs_caser_cfg* cfg, const cirs_caser_weights* w, const cirs_caser_state* st, const int32_t* users,
@@ -506,9 +482,8 @@ extern "C" int cirs_caser_tracker_backward(const cirs_caser_cfg* cfg, const cirs
     if (int rc = validate_caser(cfg, w)) return rc;
     CIRS_REQUIRE(st && st->x_hist && users && act && rew && row_env && row_t && offsets && lens && dstate && grads && workspace, "null argument");
     CIRS_REQUIRE(n_rows > 0, "n_rows must be positive");
-    CIRS_REQUIRE(grads->emb_user && grads->emb_item && grads->ffn_user_w && grads->ffn_user_b && grads->gate_w && grads->gate_b && grads->dec_w &&
-                     grads->dec_b && grads->vert_w && grads->vert_b && grads->fc_w && grads->fc_b,
-                 "caser tracker: gradient pointer null");
+    if (int rc = validate_slot_grads(grads, "caser tracker")) return rc;
+    CIRS_REQUIRE(grads->vert_w && grads->vert_b && grads->fc_w && grads->fc_b, "caser tracker: gradient pointer null");
     for (int i = 0; i < cfg->n_heights; ++i) CIRS_REQUIRE(grads->conv_w[i] && grads->conv_b[i], "caser tracker: bank gradient pointer null");
     CIRS_REQUIRE((long)n_rows * cfg->window < (1L << 27), "caser tracker: n_rows * window out of range");
     CIRS_REQUIRE(workspace_bytes >= cirs_caser_tracker_backward_workspace_bytes(cfg, n_rows), "workspace too small");
@@ -519,7 +494,7 @@ extern "C" int cirs_caser_tracker_backward(const cirs_caser_cfg* cfg, const cirs
     CaserScratch sc = carve_caser(workspace, cfg, R, &total);
     DwList dwl{};
     hipLaunchKernelGGL(gather_dstate, dim3(cdiv((long)R * S, 256)), dim3(256), 0, s, dstate, row_env, row_t, R, S, B, sc.G);
-    const int walks = std::max(1, cdiv(R, (long)cEnvsPerWg * cWgPerCu * device_cu_count()));
+    const int walks = slot_walks(R, cEnvsPerWg, cWgPerCu);
     hipLaunchKernelGGL(caser_rows_fwd, dim3(cdiv(R, (long)cEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, (const float*)st->x_hist, row_env, row_t, R, walks,
                        sc.H, sc.Z, sc.CAT, sc.ARG, sc.WIN, sc.ONES);
     launch_rows_gemm_dw(dwl, sc.H, tD, S, tD, grads->dec_w, grads->dec_b, sc.partial, false, sc.G, S, w->dec_w, tD, nullptr, R, S, tD, 0, nullptr, 0, sc.dH,
@@ -542,5 +517,5 @@ extern "C" int cirs_caser_tracker_backward(const cirs_caser_cfg* cfg, const cirs
     hipLaunchKernelGGL(caser_window_bwd, dim3(cdiv(R, 8)), dim3(256), 0, s, *cfg, *w, (const float*)sc.dH, (const float*)sc.DO, (const float*)sc.DVP,
                        (const int32_t*)sc.ARG, row_env, row_t, offsets, lens, R, sc.dX);
     CIRS_CHECK_LAUNCH("caser tracker backward window");
-    return recurrent_slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

@@ -22,7 +22,7 @@
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <utility>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -221,27 +221,21 @@ static size_t gru_partial_floats(const cirs_gru_cfg* cfg, long R) {
 }
 
 static GruScratch carve_gru(void* ws, const cirs_gru_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env;
+    Carver c(ws);
     GruScratch s;
-    s.X = take((size_t)R * tD); s.G = take((size_t)R * 32); s.dHa = take((size_t)R * tD); s.dHb = take((size_t)R * tD);
-    s.dGi = take((size_t)R * gG); s.dGh = take((size_t)R * gG); s.Gi = take((size_t)R * gG);
+    s.X = c.take((size_t)R * tD); s.G = c.take((size_t)R * 32); s.dHa = c.take((size_t)R * tD); s.dHb = c.take((size_t)R * tD);
+    s.dGi = c.take((size_t)R * gG); s.dGh = c.take((size_t)R * gG); s.Gi = c.take((size_t)R * gG);
     for (int l = 0; l < CIRS_GRU_MAX_LAYERS; ++l) {
         GruRows& g = s.rows[l];
-        g.r = take((size_t)R * tD); g.z = take((size_t)R * tD); g.n = take((size_t)R * tD); g.hn = take((size_t)R * tD);
-        g.h = take((size_t)R * tD); g.hp = take((size_t)R * tD);
+        g.r = c.take((size_t)R * tD); g.z = c.take((size_t)R * tD); g.n = c.take((size_t)R * tD); g.hn = c.take((size_t)R * tD);
+        g.h = c.take((size_t)R * tD); g.hp = c.take((size_t)R * tD);
     }
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(gru_partial_floats(cfg, R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+    carve_slots(c, s, R, cfg->n_env, gru_partial_floats(cfg, R));
+    *total_floats = c.total();
     return s;
 }
 
+static int validate_gru_cfg(const cirs_gru_cfg* cfg) { return validate_recurrent_cfg(cfg, CIRS_GRU_MAX_LAYERS, "gru tracker"); }
 static int validate_gru(const cirs_gru_cfg* cfg, const cirs_gru_weights* w) { return validate_recurrent(cfg, w, CIRS_GRU_MAX_LAYERS, "gru tracker"); }
 
 static int launch_gru_step(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int32_t* users, const int64_t* items,
@@ -271,29 +265,16 @@ static int launch_gru_step(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, c
 
 extern "C" int cirs_gru_tracker_init(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int32_t* users,
                                      const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_gru(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_gru_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_gru, cirs::launch_gru_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_gru_tracker_step(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, cirs_gru_state* st, const int64_t* items, const double* rew,
                                      const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_gru(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_gru_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_gru, cirs::launch_gru_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_gru_tracker_backward_workspace_bytes(const cirs_gru_cfg* cfg, int32_t n_rows) {
-    if (!cfg || n_rows <= 0 || cfg->n_env <= 0 || cfg->nlayers < 1 || cfg->nlayers > CIRS_GRU_MAX_LAYERS) return 0;
-    size_t total = 0;
-    (void)cirs::carve_gru(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_gru_cfg, cirs::carve_gru, cfg, n_rows);
 }
 
 extern "C" int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru_weights* w, const cirs_gru_state* st, const int32_t* users,
@@ -337,5 +318,5 @@ extern "C" int cirs_gru_tracker_backward(const cirs_gru_cfg* cfg, const cirs_gru
         std::swap(dH, dX);
     }
     CIRS_CHECK_LAUNCH("gru tracker backward layers");
-    return recurrent_slots_backward(cfg, w, grads, dH, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, dH, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

@@ -16,11 +16,11 @@
 //   B  lstm_seq_fwd: one wavefront per env over p = 0 .. len-1, W_hh in LDS; keeps i, f, g, o, c, h and the previous c, h per row
 //   C  dH_top = gather(dstate) W_dec, the decoder's weight gradient                (rows_gemm + dw_gemm in one launch)
 //   D  lstm_seq_bwd: one wavefront per env over p = len-1 .. 0: the pre-activation gradients dG [R, 128]; the input side and the hidden side share them
-//   E  dW_ih, dW_hh and both bias gradients from dG (dw_batch); dX = dG W_ih = the lower layer's dH or the slot gradient; then the slot stage (recurrent.h)
+//   E  dW_ih, dW_hh and both bias gradients from dG (dw_batch); dX = dG W_ih = the lower layer's dH or the slot gradient; then the slot stage (slot_tracker.h)
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <utility>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -231,24 +231,18 @@ static size_t lstm_partial_floats(const cirs_lstm_cfg* cfg, long R) {
 }
 
 static LstmScratch carve_lstm(void* ws, const cirs_lstm_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env;
+    Carver c(ws);
     LstmScratch s;
-    s.X = take((size_t)R * tD); s.G = take((size_t)R * 32); s.dHa = take((size_t)R * tD); s.dHb = take((size_t)R * tD);
-    s.dG = take((size_t)R * lG); s.Gi = take((size_t)R * lG);
+    s.X = c.take((size_t)R * tD); s.G = c.take((size_t)R * 32); s.dHa = c.take((size_t)R * tD); s.dHb = c.take((size_t)R * tD);
+    s.dG = c.take((size_t)R * lG); s.Gi = c.take((size_t)R * lG);
     for (int l = 0; l < CIRS_LSTM_MAX_LAYERS; ++l)
-        for (float** q : {&s.rows[l].i, &s.rows[l].f, &s.rows[l].g, &s.rows[l].o, &s.rows[l].c, &s.rows[l].cp, &s.rows[l].h, &s.rows[l].hp}) *q = take((size_t)R * tD);
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(lstm_partial_floats(cfg, R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+        for (float** q : {&s.rows[l].i, &s.rows[l].f, &s.rows[l].g, &s.rows[l].o, &s.rows[l].c, &s.rows[l].cp, &s.rows[l].h, &s.rows[l].hp}) *q = c.take((size_t)R * tD);
+    carve_slots(c, s, R, cfg->n_env, lstm_partial_floats(cfg, R));
+    *total_floats = c.total();
     return s;
 }
 
+static int validate_lstm_cfg(const cirs_lstm_cfg* cfg) { return validate_recurrent_cfg(cfg, CIRS_LSTM_MAX_LAYERS, "lstm tracker"); }
 static int validate_lstm(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w) { return validate_recurrent(cfg, w, CIRS_LSTM_MAX_LAYERS, "lstm tracker"); }
 
 static int launch_lstm_step(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, cirs_lstm_state* st, const int32_t* users, const int64_t* items,
@@ -279,29 +273,16 @@ static int launch_lstm_step(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w
 
 extern "C" int cirs_lstm_tracker_init(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, cirs_lstm_state* st, const int32_t* users,
                                       const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_lstm(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_lstm_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_lstm, cirs::launch_lstm_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_lstm_tracker_step(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, cirs_lstm_state* st, const int64_t* items, const double* rew,
                                       const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_lstm(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_lstm_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_lstm, cirs::launch_lstm_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_lstm_tracker_backward_workspace_bytes(const cirs_lstm_cfg* cfg, int32_t n_rows) {
-    if (!cfg || n_rows <= 0 || cfg->n_env <= 0 || cfg->nlayers < 1 || cfg->nlayers > CIRS_LSTM_MAX_LAYERS) return 0;
-    size_t total = 0;
-    (void)cirs::carve_lstm(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_lstm_cfg, cirs::carve_lstm, cfg, n_rows);
 }
 
 extern "C" int cirs_lstm_tracker_backward(const cirs_lstm_cfg* cfg, const cirs_lstm_weights* w, const cirs_lstm_state* st, const int32_t* users,
@@ -345,5 +326,5 @@ extern "C" int cirs_lstm_tracker_backward(const cirs_lstm_cfg* cfg, const cirs_l
         std::swap(dH, dX);
     }
     CIRS_CHECK_LAUNCH("lstm tracker backward layers");
-    return recurrent_slots_backward(cfg, w, grads, dH, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, dH, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

@@ -25,11 +25,11 @@
 //      the shift a base-pointer offset.  3 n_blocks problems in a list of their own (into a [block][tap][out][in] buffer, transposed to torch's [out][in][tap]
 //      by nin_taps_to_torch); LayerNorm weight / bias = the diagonal / column sums of DN^T NH, in the pass's main list
 //   X  nin_window_bwd: dX[b,0] = sum_p dH[b,p];  dX[b,k] = sum_{p=k}^{min(len_b-1, k+R-1)} DWIN_p[k - p + 15]  -- p ascending, every row on its own
-//   E  the slot stage of the recurrent trackers (recurrent.h)
+//   E  the slot stage of the recurrent trackers (slot_tracker.h)
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <cmath>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -380,24 +380,18 @@ static size_t nin_partial_floats(const cirs_nextitnet_cfg* cfg, long R) {      /
 }
 
 static NinScratch carve_nin(void* ws, const cirs_nextitnet_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env, nb = cfg->n_blocks;
+    Carver c(ws);
+    const long nb = cfg->n_blocks;
     NinScratch s;
-    s.G = take((size_t)R * 32); s.H = take((size_t)R * tD); s.dH = take((size_t)R * tD); s.dX = take((size_t)R * tD);
-    s.YIN = take((size_t)nb * (256 + (size_t)R * nRows * tD));
-    s.NH = take((size_t)nb * R * nTile * tD); s.RSTD = take((size_t)nb * R * nTile); s.DN = take((size_t)nb * R * nTile * tD);
-    s.DC = take((size_t)nb * R * nRows * tD);
-    s.DWIN = take((size_t)R * nTile * tD);
-    s.TAPS = take((size_t)nb * 3 * tD * tD);
-    s.tap_partial = take((size_t)nb * 3 * dw_list_floats(R, tD, tD) + 4096);
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(nin_partial_floats(cfg, R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+    s.G = c.take((size_t)R * 32); s.H = c.take((size_t)R * tD); s.dH = c.take((size_t)R * tD); s.dX = c.take((size_t)R * tD);
+    s.YIN = c.take((size_t)nb * (256 + (size_t)R * nRows * tD));
+    s.NH = c.take((size_t)nb * R * nTile * tD); s.RSTD = c.take((size_t)nb * R * nTile); s.DN = c.take((size_t)nb * R * nTile * tD);
+    s.DC = c.take((size_t)nb * R * nRows * tD);
+    s.DWIN = c.take((size_t)R * nTile * tD);
+    s.TAPS = c.take((size_t)nb * 3 * tD * tD);
+    s.tap_partial = c.take((size_t)nb * 3 * dw_list_floats(R, tD, tD) + 4096);
+    carve_slots(c, s, R, cfg->n_env, nin_partial_floats(cfg, R));
+    *total_floats = c.total();
     return s;
 }
 
@@ -414,18 +408,13 @@ static int validate_nin_cfg(const cirs_nextitnet_cfg* cfg) {
     for (int l = 0; l < cfg->n_blocks; ++l)
         CIRS_REQUIRE(cfg->dilations[l] >= 1 && cfg->dilations[l] <= CIRS_NEXTITNET_MAX_DILATION, "nextitnet tracker: dilations must be in 1..4");
     CIRS_REQUIRE(nin_receptive_field(cfg) <= nTile - 1, "nextitnet tracker: the dilations must sum to at most 7");
-    if (cfg->dim_model != tD) return fail(CIRS_E_UNSUPPORTED, "nextitnet tracker: this build supports dim_model == 32");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= 32, "nextitnet tracker: dim_state must be in 1..32");
-    CIRS_REQUIRE(cfg->max_len >= 1 && cfg->max_len <= 4096, "nextitnet tracker: max_len out of range");
-    CIRS_REQUIRE(cfg->n_env >= 1 && cfg->n_users >= 1 && cfg->n_items >= 1, "nextitnet tracker: n_env / n_users / n_items must be positive");
-    return CIRS_OK;
+    return validate_slot_cfg(cfg, "nextitnet tracker");
 }
 
 static int validate_nin(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w) {
     if (int rc = validate_nin_cfg(cfg)) return rc;
     CIRS_REQUIRE(w, "nextitnet tracker: weights null");
-    CIRS_REQUIRE(w->emb_user && w->emb_item && w->ffn_user_w && w->ffn_user_b && w->gate_w && w->gate_b && w->dec_w && w->dec_b,
-                 "nextitnet tracker: weight pointer null");
+    if (int rc = validate_slot_weights(w, "nextitnet tracker")) return rc;
     for (int l = 0; l < cfg->n_blocks; ++l)
         CIRS_REQUIRE(w->conv_w[l] && w->conv_b[l] && w->ln_w[l] && w->ln_b[l], "nextitnet tracker: block weight pointer null");
     return CIRS_OK;
@@ -437,7 +426,7 @@ static int launch_nin_step(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_w
     CIRS_REQUIRE(st && st->x_hist && st->len, "nextitnet tracker: state pointer null");
     // 73 KB of LDS (50 KB of it the four blocks' weights, staged whatever n_blocks is): two workgroups per CU.  Up to 4 x 2 x CUs envs every env has a
     // wavefront of its own, beyond that a workgroup walks several groups of four and what it staged serves them all.  Chosen from the structure, not tuned.
-    const int walks = std::max(1, cdiv(n, (long)nEnvsPerWg * nWgPerCu * device_cu_count()));
+    const int walks = slot_walks(n, nEnvsPerWg, nWgPerCu);
     hipLaunchKernelGGL(nin_step_kernel, dim3(cdiv(n, (long)nEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, *st, users, items, rew, env_ids, skip, n,
                        state_out, state_stride, walks, nin_receptive_field(cfg));
     CIRS_CHECK_LAUNCH("nin_step_kernel");
@@ -448,30 +437,17 @@ static int launch_nin_step(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_w
 
 extern "C" int cirs_nextitnet_tracker_init(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, cirs_nextitnet_state* st, const int32_t* users,
                                            const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_nin(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_nin_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_nin, cirs::launch_nin_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_nextitnet_tracker_step(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, cirs_nextitnet_state* st, const int64_t* items,
                                            const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out, int64_t state_stride,
                                            void* stream) {
-    using namespace cirs;
-    if (int rc = validate_nin(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_nin_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_nin, cirs::launch_nin_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_nextitnet_tracker_backward_workspace_bytes(const cirs_nextitnet_cfg* cfg, int32_t n_rows) {
-    if (n_rows <= 0 || cirs::validate_nin_cfg(cfg) != CIRS_OK) return 0;
-    size_t total = 0;
-    (void)cirs::carve_nin(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_nin_cfg, cirs::carve_nin, cfg, n_rows);
 }
 
 extern "C" int cirs_nextitnet_tracker_backward(const cirs_nextitnet_cfg* cfg, const cirs_nextitnet_weights* w, const cirs_nextitnet_state* st,
@@ -482,9 +458,7 @@ extern "C" int cirs_nextitnet_tracker_backward(const cirs_nextitnet_cfg* cfg, co
     if (int rc = validate_nin(cfg, w)) return rc;
     CIRS_REQUIRE(st && st->x_hist && users && act && rew && row_env && row_t && offsets && lens && dstate && grads && workspace, "null argument");
     CIRS_REQUIRE(n_rows > 0, "n_rows must be positive");
-    CIRS_REQUIRE(grads->emb_user && grads->emb_item && grads->ffn_user_w && grads->ffn_user_b && grads->gate_w && grads->gate_b && grads->dec_w &&
-                     grads->dec_b,
-                 "nextitnet tracker: gradient pointer null");
+    if (int rc = validate_slot_grads(grads, "nextitnet tracker")) return rc;
     for (int l = 0; l < cfg->n_blocks; ++l)
         CIRS_REQUIRE(grads->conv_w[l] && grads->conv_b[l] && grads->ln_w[l] && grads->ln_b[l], "nextitnet tracker: block gradient pointer null");
     CIRS_REQUIRE((long)n_rows * nRows < (1L << 27), "nextitnet tracker: n_rows * 24 out of range");
@@ -496,7 +470,7 @@ extern "C" int cirs_nextitnet_tracker_backward(const cirs_nextitnet_cfg* cfg, co
     NinScratch sc = carve_nin(workspace, cfg, R, &total);
     DwList dwl{};
     hipLaunchKernelGGL(gather_dstate, dim3(cdiv((long)R * S, 256)), dim3(256), 0, s, dstate, row_env, row_t, R, S, B, sc.G);
-    const int walks = std::max(1, cdiv(R, (long)nEnvsPerWg * nWgPerCu * device_cu_count()));
+    const int walks = slot_walks(R, nEnvsPerWg, nWgPerCu);
     hipLaunchKernelGGL(nin_rows_fwd, dim3(cdiv(R, (long)nEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, (const float*)st->x_hist, row_env, row_t, R, walks, rf,
                        sc.H, NinKeep{sc.YIN, sc.NH, sc.RSTD});
     launch_rows_gemm_dw(dwl, sc.H, tD, S, tD, grads->dec_w, grads->dec_b, sc.partial, false, sc.G, S, w->dec_w, tD, nullptr, R, S, tD, 0, nullptr, 0, sc.dH,
@@ -530,5 +504,5 @@ extern "C" int cirs_nextitnet_tracker_backward(const cirs_nextitnet_cfg* cfg, co
     hipLaunchKernelGGL(nin_window_bwd, dim3(cdiv(R, 8)), dim3(256), 0, s, (const float*)sc.dH, (const float*)sc.DWIN, row_env, row_t, offsets, lens, R, rf,
                        sc.dX);
     CIRS_CHECK_LAUNCH("nextitnet tracker backward window");
-    return recurrent_slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

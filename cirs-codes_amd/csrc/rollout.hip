@@ -119,10 +119,57 @@ extern "C" int cirs_rollout_collect_greedy(const cirs_env_cfg* env_cfg, const ci
                         nullptr, nullptr, workspace, workspace_bytes, stream, nullptr, users, true);
 }
 
-// cirs_rollout_collect with a recurrent or a window tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip, stamp_tracker.hip): the unfused sequence of
-// rollout_impl's online-reward branch without the scorer, built from the public entry points -- about five launches per vector step against the fused
-// Transformer collect's two.  One loop for all of them: `init` / `step` are the tracker's entry points, `what` names it in the messages.
 namespace cirs {
+// One unfused vector step: policy(obs_t), visited bit, the optional user-model scorer, env step, forced length, tracker step.  `tracker_step(act_t, rew_t,
+// obs_n)` appends one position for every env that acted; `online` (nullable) scores the chosen pairs between the policy and the env step.
+template <class TrackerStep>
+static int unfused_vector_step(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st, const cirs_policy_cfg* pol_cfg,
+                               const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env, long S, int t, uint64_t seed, uint32_t rng_base,
+                               uint32_t* visited, int32_t force_length, bool greedy, const float* gumbel, const cirs_online_reward* online, void* workspace,
+                               int64_t workspace_bytes, void* stream, TrackerStep tracker_step) {
+    const long B = n_env;
+    hipStream_t s = (hipStream_t)stream;
+    float* obs_t = traj->obs + (size_t)t * B * S;
+    float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
+    int64_t* act_t = traj->act + (size_t)t * B;
+    double* rew_t = traj->rew + (size_t)t * B;
+    uint8_t* done_t = traj->done + (size_t)t * B;
+    // policy(obs_t): finished envs (env_st->done) are skipped and get act = -1
+    if (greedy) {
+        if (int rc = cirs_actor_greedy(pol_cfg, pol_w, obs_t, S, n_env, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
+                                       traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
+            return rc;
+    } else {
+        if (int rc = cirs_actor_sample(pol_cfg, pol_w, obs_t, S, n_env, gumbel ? gumbel + (size_t)t * B * pol_cfg->n_items : nullptr, seed,
+                                       rng_base + (uint32_t)t, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
+                                       traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
+            return rc;
+    }
+    if (visited) {
+        hipLaunchKernelGGL(mark_visited_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, act_t, n_env, pol_cfg->n_items, visited);
+        CIRS_CHECK_LAUNCH("mark_visited_kernel");
+    }
+    if (online) {   // score the chosen (user, item) pairs with the DeepFM user model
+        hipLaunchKernelGGL(online_pairs_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->user, act_t, n_env, *online);
+        CIRS_CHECK_LAUNCH("online_pairs_kernel");
+        if (int rc = cirs_deepfm_forward(online->cfg, online->w, online->uid_buf, online->pid_buf, online->feat_buf, online->dur_buf, n_env, online->pred_buf,
+                                         stream))
+            return rc;
+    }
+    // env.step: obs_next id == action, so the int64 obs row doubles as scratch we do not keep
+    if (int rc = cirs_env_step(env_cfg, env_tab, env_st, act_t, nullptr, n_env, (int64_t*)workspace, rew_t, done_t, traj->ctr + (size_t)t * B, nullptr, stream))
+        return rc;
+    if (force_length > 0) {
+        hipLaunchKernelGGL(force_done_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->done, done_t, act_t, n_env, (t + 1 >= force_length) ? 1 : 0);
+        CIRS_CHECK_LAUNCH("force_done_kernel");
+    }
+    // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
+    return tracker_step(act_t, rew_t, obs_n);
+}
+
+// cirs_rollout_collect with a slot tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip, stamp_tracker.hip):
+// unfused_vector_step without the scorer, built from the public entry points -- about five launches per vector step against the fused Transformer
+// collect's two.  One loop for all of them: `init` / `step` are the tracker's entry points, `what` names it in the messages.
 template <class Cfg, class Weights, class State>
 static int collect_recurrent(const char* what, int (*init)(const Cfg*, const Weights*, State*, const int32_t*, const int32_t*, int32_t, float*, int64_t, void*),
                              int (*step)(const Cfg*, const Weights*, State*, const int64_t*, const double*, const int32_t*, const uint8_t*, int32_t, float*,
@@ -142,40 +189,16 @@ static int collect_recurrent(const char* what, int (*init)(const Cfg*, const Wei
     CIRS_REQUIRE(trk_cfg->max_len >= env_cfg->max_turn + 1, "tracker max_len < max_turn + 1");
     CIRS_REQUIRE(pol_cfg->n_items == env_cfg->n_items && trk_cfg->n_items == env_cfg->n_items, "policy/env/tracker n_items mismatch");
     CIRS_REQUIRE(workspace_bytes >= cirs_policy_workspace_bytes(pol_cfg, n_env) && workspace_bytes >= (int64_t)sizeof(int64_t) * n_env, "workspace too small");
-    const long B = n_env, S = trk_cfg->dim_state;
-    hipStream_t s = (hipStream_t)stream;
+    const long S = trk_cfg->dim_state;
     if (int rc = cirs_env_reset(env_cfg, env_st, users, nullptr, n_env, nullptr, stream)) return rc;
     if (int rc = init(trk_cfg, trk_w, trk_st, users, nullptr, n_env, traj->obs, S, stream)) return rc;
-    for (int t = 0; t < env_cfg->max_turn; ++t) {
-        float* obs_t = traj->obs + (size_t)t * B * S;
-        float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
-        int64_t* act_t = traj->act + (size_t)t * B;
-        double* rew_t = traj->rew + (size_t)t * B;
-        uint8_t* done_t = traj->done + (size_t)t * B;
-        // policy(obs_t): finished envs (env_st->done) are skipped and get act = -1
-        if (greedy) {
-            if (int rc = cirs_actor_greedy(pol_cfg, pol_w, obs_t, S, n_env, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
-                                           traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
-                return rc;
-        } else {
-            if (int rc = cirs_actor_sample(pol_cfg, pol_w, obs_t, S, n_env, gumbel ? gumbel + (size_t)t * B * pol_cfg->n_items : nullptr, seed,
-                                           rng_base + (uint32_t)t, nullptr, visited, env_st->done, act_t, traj->logp + (size_t)t * B,
-                                           traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
-                return rc;
-        }
-        if (visited) {
-            hipLaunchKernelGGL(mark_visited_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, act_t, n_env, pol_cfg->n_items, visited);
-            CIRS_CHECK_LAUNCH("mark_visited_kernel");
-        }
-        if (int rc = cirs_env_step(env_cfg, env_tab, env_st, act_t, nullptr, n_env, (int64_t*)workspace, rew_t, done_t, traj->ctr + (size_t)t * B, nullptr, stream))
+    auto tracker_step = [&](const int64_t* act_t, const double* rew_t, float* obs_n) {
+        return step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream);
+    };
+    for (int t = 0; t < env_cfg->max_turn; ++t)
+        if (int rc = unfused_vector_step(env_cfg, env_tab, env_st, pol_cfg, pol_w, traj, n_env, S, t, seed, rng_base, visited, force_length, greedy != 0, gumbel,
+                                         nullptr, workspace, workspace_bytes, stream, tracker_step))
             return rc;
-        if (force_length > 0) {
-            hipLaunchKernelGGL(force_done_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->done, done_t, act_t, n_env, (t + 1 >= force_length) ? 1 : 0);
-            CIRS_CHECK_LAUNCH("force_done_kernel");
-        }
-        // preprocess_fn(obs_next, rew): the tracker appends one position for every env that acted this step
-        if (int rc = step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream)) return rc;
-    }
     return CIRS_OK;
 }
 }  // namespace cirs
@@ -285,41 +308,13 @@ static int rollout_impl(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_
     const long B = n_env, S = trk_cfg->dim_state;
     hipStream_t s = (hipStream_t)stream;
     if (online) {  // per-step user-model scoring sits between the policy and the env step: unfused launch sequence
-        for (int t = t_begin; t < t_end; ++t) {
-            float* obs_t = traj->obs + (size_t)t * B * S;
-            float* obs_n = traj->obs + (size_t)(t + 1) * B * S;
-            int64_t* act_t = traj->act + (size_t)t * B;
-            double* rew_t = traj->rew + (size_t)t * B;
-            uint8_t* done_t = traj->done + (size_t)t * B;
-            // policy(obs_t): finished envs (env_st->done) are skipped and get act = -1
-            if (int rc = cirs_actor_sample(pol_cfg, pol_w, obs_t, S, n_env, gumbel ? gumbel + (size_t)t * B * pol_cfg->n_items : nullptr, seed, rng_base + (uint32_t)t, nullptr,
-                                           visited, env_st->done, act_t, traj->logp + (size_t)t * B,
-                                           traj->value + (size_t)t * B, workspace, workspace_bytes, stream))
+        auto tracker_step = [&](const int64_t* act_t, const double* rew_t, float* obs_n) {
+            return cirs_tracker_step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream);
+        };
+        for (int t = t_begin; t < t_end; ++t)
+            if (int rc = unfused_vector_step(env_cfg, env_tab, env_st, pol_cfg, pol_w, traj, n_env, S, t, seed, rng_base, visited, force_length, false, gumbel,
+                                             online, workspace, workspace_bytes, stream, tracker_step))
                 return rc;
-            if (visited) {
-                hipLaunchKernelGGL(mark_visited_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, act_t, n_env,
-                                   pol_cfg->n_items, visited);
-                CIRS_CHECK_LAUNCH("mark_visited_kernel");
-            }
-            // score the chosen (user, item) pairs with the DeepFM user model
-            hipLaunchKernelGGL(online_pairs_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->user, act_t, n_env, *online);
-            CIRS_CHECK_LAUNCH("online_pairs_kernel");
-            if (int rc = cirs_deepfm_forward(online->cfg, online->w, online->uid_buf, online->pid_buf, online->feat_buf, online->dur_buf,
-                                             n_env, online->pred_buf, stream))
-                return rc;
-            // env.step: obs_next id == action, so the int64 obs row doubles as scratch we do not keep
-            if (int rc = cirs_env_step(env_cfg, env_tab, env_st, act_t, nullptr, n_env, (int64_t*)workspace, rew_t, done_t,
-                                       traj->ctr + (size_t)t * B, nullptr, stream))
-                return rc;
-            if (force_length > 0) {
-                hipLaunchKernelGGL(force_done_kernel, dim3(cdiv(n_env, 256)), dim3(256), 0, s, env_st->done, done_t, act_t,
-                                   n_env, (t + 1 >= force_length) ? 1 : 0);
-                CIRS_CHECK_LAUNCH("force_done_kernel");
-            }
-            // preprocess_fn(obs_next, rew): tracker appends one position for every env that acted this step
-            if (int rc = cirs_tracker_step(trk_cfg, trk_w, trk_st, act_t, rew_t, nullptr, nullptr, n_env, obs_n, S, stream))
-                return rc;
-        }
         return CIRS_OK;
     }
     // ---- fused sequence: 2 launches per vector step ------------------------------------------------------------

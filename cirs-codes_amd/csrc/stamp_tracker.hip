@@ -24,11 +24,11 @@
 //   W  weight gradients through the slab partials: attn.w1 = DG^T XWIN and attn.w0 = DE^T SIG over the R 16 (row, tile row) pairs; attn.w2 (+ attn.bias),
 //      attn.w3, mlp_a, mlp_b per row
 //   X  stamp_window_bwd: dX[b,0] = sum_p dH[b,p];  dX[b,k] = sum_{p=k}^{min(len_b-1, k+W-1)} DWIN_p[k - p + 15]  -- p ascending, every row on its own
-//   E  the slot stage of the recurrent trackers (recurrent.h)
+//   E  the slot stage of the recurrent trackers (slot_tracker.h)
 // No floating-point atomics; every reduction has a fixed order.
 #include <algorithm>
 #include <cmath>
-#include "recurrent.h"
+#include "slot_tracker.h"
 
 namespace cirs {
 
@@ -445,22 +445,15 @@ static size_t stamp_partial_floats(long R) {
 }
 
 static StampScratch carve_stamp(void* ws, const cirs_stamp_cfg* cfg, long R, size_t* total_floats) {
-    float* p = (float*)ws;
-    auto take = [&](size_t n) { float* r = p; p += (n + 3) & ~(size_t)3; return r; };
-    const long B = cfg->n_env;
+    Carver c(ws);
     StampScratch s;
-    s.G = take((size_t)R * 32); s.H = take((size_t)R * tD); s.dH = take((size_t)R * tD); s.dX = take((size_t)R * tD);
-    s.XWIN = take((size_t)R * sTile * tD); s.SIG = take((size_t)R * sTile * tD); s.DG = take((size_t)R * sTile * tD); s.DWIN = take((size_t)R * sTile * tD);
-    s.E = take((size_t)R * sTile); s.DE = take((size_t)R * sTile);
-    s.MS = take((size_t)R * tD); s.MA = take((size_t)R * tD); s.HS = take((size_t)R * tD); s.HT = take((size_t)R * tD);
-    s.DPA = take((size_t)R * tD); s.DPB = take((size_t)R * tD); s.DC = take((size_t)R * tD);
-    s.DU = take((size_t)R * tD); s.EU = take((size_t)R * tD); s.DPRE = take((size_t)R * tD); s.CU = take((size_t)R * tD);
-    s.CI = take((size_t)(R + B) * tD);      // item rows, then one user row per env (the merged scatter's layout)
-    s.GIN = take((size_t)R * (tD + 1));
-    s.key_user = (int32_t*)take(R); s.key_item = (int32_t*)take(R);
-    s.partial = take(stamp_partial_floats(R) + 4096);
-    s.sort = (void*)take(emb_sort_bytes(R + B) / 4 + 64);
-    *total_floats = (size_t)(p - (float*)ws) + 64;
+    s.G = c.take((size_t)R * 32); s.H = c.take((size_t)R * tD); s.dH = c.take((size_t)R * tD); s.dX = c.take((size_t)R * tD);
+    s.XWIN = c.take((size_t)R * sTile * tD); s.SIG = c.take((size_t)R * sTile * tD); s.DG = c.take((size_t)R * sTile * tD); s.DWIN = c.take((size_t)R * sTile * tD);
+    s.E = c.take((size_t)R * sTile); s.DE = c.take((size_t)R * sTile);
+    s.MS = c.take((size_t)R * tD); s.MA = c.take((size_t)R * tD); s.HS = c.take((size_t)R * tD); s.HT = c.take((size_t)R * tD);
+    s.DPA = c.take((size_t)R * tD); s.DPB = c.take((size_t)R * tD); s.DC = c.take((size_t)R * tD);
+    carve_slots(c, s, R, cfg->n_env, stamp_partial_floats(R));
+    *total_floats = c.total();
     return s;
 }
 
@@ -468,18 +461,13 @@ static StampScratch carve_stamp(void* ws, const cirs_stamp_cfg* cfg, long R, siz
 static int validate_stamp_cfg(const cirs_stamp_cfg* cfg) {
     CIRS_REQUIRE(cfg, "stamp tracker: cfg null");
     CIRS_REQUIRE(cfg->window >= 1 && cfg->window <= sTile, "stamp tracker: window must be in 1..16");
-    if (cfg->dim_model != tD) return fail(CIRS_E_UNSUPPORTED, "stamp tracker: this build supports dim_model == 32");
-    CIRS_REQUIRE(cfg->dim_state >= 1 && cfg->dim_state <= 32, "stamp tracker: dim_state must be in 1..32");
-    CIRS_REQUIRE(cfg->max_len >= 1 && cfg->max_len <= 4096, "stamp tracker: max_len out of range");
-    CIRS_REQUIRE(cfg->n_env >= 1 && cfg->n_users >= 1 && cfg->n_items >= 1, "stamp tracker: n_env / n_users / n_items must be positive");
-    return CIRS_OK;
+    return validate_slot_cfg(cfg, "stamp tracker");
 }
 
 static int validate_stamp(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w) {
     if (int rc = validate_stamp_cfg(cfg)) return rc;
     CIRS_REQUIRE(w, "stamp tracker: weights null");
-    CIRS_REQUIRE(w->emb_user && w->emb_item && w->ffn_user_w && w->ffn_user_b && w->gate_w && w->gate_b && w->dec_w && w->dec_b,
-                 "stamp tracker: weight pointer null");
+    if (int rc = validate_slot_weights(w, "stamp tracker")) return rc;
     CIRS_REQUIRE(w->w1 && w->w2 && w->w3 && w->attn_b && w->w0, "stamp tracker: attention weight pointer null (w1 / w2 / w3 / attn_b / w0)");
     CIRS_REQUIRE(w->mlp_a_w && w->mlp_a_b && w->mlp_b_w && w->mlp_b_b, "stamp tracker: read-out weight pointer null (mlp_a / mlp_b)");
     return CIRS_OK;
@@ -490,7 +478,7 @@ static int launch_stamp_step(const cirs_stamp_cfg* cfg, const cirs_stamp_weights
     CIRS_REQUIRE(st && st->x_hist && st->len, "stamp tracker: state pointer null");
     // 40 448 bytes of LDS (30 KB of it the seven staged matrices): four workgroups per CU, four wavefronts per SIMD.  Up to 4 x 4 x CUs envs every env has a
     // wavefront of its own, beyond that a workgroup walks several groups of four and what it staged serves them all.  Chosen from the structure, not tuned.
-    const int walks = std::max(1, cdiv(n, (long)sEnvsPerWg * sWgPerCu * device_cu_count()));
+    const int walks = slot_walks(n, sEnvsPerWg, sWgPerCu);
     hipLaunchKernelGGL(stamp_step_kernel, dim3(cdiv(n, (long)sEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, *st, users, items, rew, env_ids, skip, n,
                        state_out, state_stride, walks);
     CIRS_CHECK_LAUNCH("stamp_step_kernel");
@@ -501,30 +489,17 @@ static int launch_stamp_step(const cirs_stamp_cfg* cfg, const cirs_stamp_weights
 
 extern "C" int cirs_stamp_tracker_init(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, cirs_stamp_state* st, const int32_t* users,
                                        const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_stamp(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(users && state_out, "users/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_stamp_step(cfg, w, st, users, nullptr, nullptr, env_ids, nullptr, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_init(cirs::validate_stamp, cirs::launch_stamp_step, cfg, w, st, users, env_ids, n, state_out, state_stride, stream);
 }
 
 extern "C" int cirs_stamp_tracker_step(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, cirs_stamp_state* st, const int64_t* items,
                                        const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
                                        int64_t state_stride, void* stream) {
-    using namespace cirs;
-    if (int rc = validate_stamp(cfg, w)) return rc;
-    if (n <= 0) return CIRS_OK;
-    CIRS_REQUIRE(items && rew && state_out, "items/rew/state_out null");
-    CIRS_REQUIRE(state_stride >= cfg->dim_state, "state_stride < dim_state");
-    return launch_stamp_step(cfg, w, st, nullptr, items, rew, env_ids, skip, n, state_out, (long)state_stride, (hipStream_t)stream);
+    return cirs::slot_tracker_step(cirs::validate_stamp, cirs::launch_stamp_step, cfg, w, st, items, rew, env_ids, skip, n, state_out, state_stride, stream);
 }
 
 extern "C" int64_t cirs_stamp_tracker_backward_workspace_bytes(const cirs_stamp_cfg* cfg, int32_t n_rows) {
-    if (n_rows <= 0 || cirs::validate_stamp_cfg(cfg) != CIRS_OK) return 0;
-    size_t total = 0;
-    (void)cirs::carve_stamp(nullptr, cfg, n_rows, &total);
-    return (int64_t)total * 4;
+    return cirs::slot_tracker_workspace_bytes(cirs::validate_stamp_cfg, cirs::carve_stamp, cfg, n_rows);
 }
 
 extern "C" int cirs_stamp_tracker_backward(const cirs_stamp_cfg* cfg, const cirs_stamp_weights* w, const cirs_stamp_state* st, const int32_t* users,
@@ -535,9 +510,7 @@ extern "C" int cirs_stamp_tracker_backward(const cirs_stamp_cfg* cfg, const cirs
     if (int rc = validate_stamp(cfg, w)) return rc;
     CIRS_REQUIRE(st && st->x_hist && users && act && rew && row_env && row_t && offsets && lens && dstate && grads && workspace, "null argument");
     CIRS_REQUIRE(n_rows > 0, "n_rows must be positive");
-    CIRS_REQUIRE(grads->emb_user && grads->emb_item && grads->ffn_user_w && grads->ffn_user_b && grads->gate_w && grads->gate_b && grads->dec_w &&
-                     grads->dec_b,
-                 "stamp tracker: gradient pointer null");
+    if (int rc = validate_slot_grads(grads, "stamp tracker")) return rc;
     CIRS_REQUIRE(grads->w1 && grads->w2 && grads->w3 && grads->attn_b && grads->w0 && grads->mlp_a_w && grads->mlp_a_b && grads->mlp_b_w && grads->mlp_b_b,
                  "stamp tracker: attention / read-out gradient pointer null");
     CIRS_REQUIRE((long)n_rows * sTile < (1L << 27), "stamp tracker: n_rows * 16 out of range");
@@ -550,7 +523,7 @@ extern "C" int cirs_stamp_tracker_backward(const cirs_stamp_cfg* cfg, const cirs
     DwList dwl{};
     const StampKeep keep{sc.XWIN, sc.SIG, sc.E, sc.MS, sc.MA, sc.HS, sc.HT};
     hipLaunchKernelGGL(gather_dstate, dim3(cdiv((long)R * S, 256)), dim3(256), 0, s, dstate, row_env, row_t, R, S, B, sc.G);
-    const int walks = std::max(1, cdiv(R, (long)sEnvsPerWg * sWgPerCu * device_cu_count()));
+    const int walks = slot_walks(R, sEnvsPerWg, sWgPerCu);
     hipLaunchKernelGGL(stamp_rows_fwd, dim3(cdiv(R, (long)sEnvsPerWg * walks)), dim3(256), 0, s, *cfg, *w, (const float*)st->x_hist, row_env, row_t, R, walks,
                        sc.H, keep);
     launch_rows_gemm_dw(dwl, sc.H, tD, S, tD, grads->dec_w, grads->dec_b, sc.partial, false, sc.G, S, w->dec_w, tD, nullptr, R, S, tD, 0, nullptr, 0, sc.dH,
@@ -576,5 +549,5 @@ extern "C" int cirs_stamp_tracker_backward(const cirs_stamp_cfg* cfg, const cirs
     hipLaunchKernelGGL(stamp_window_bwd, dim3(cdiv(R, 8)), dim3(256), 0, s, (const float*)sc.dH, (const float*)sc.DWIN, row_env, row_t, offsets, lens, R, W,
                        sc.dX);
     CIRS_CHECK_LAUNCH("stamp tracker backward window");
-    return recurrent_slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
+    return slots_backward(cfg, w, grads, sc.dX, users, act, rew, row_env, row_t, lens, R, dwl, sc, s);
 }

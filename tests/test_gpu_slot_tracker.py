@@ -1,9 +1,9 @@
-"""GPU: a slot tracker (csrc/{gru,lstm,avg,caser}_tracker.hip) against its float64 restatement (cirs_hip/*_host.py): every state of every live
-(env, position) through reset / init / step, what the LSTM carries, every gradient tensor of the backward against float64 autograd.
+"""GPU: a slot tracker (csrc/{gru,lstm,avg,caser,nextitnet,stamp}_tracker.hip) against its float64 restatement (cirs_hip/*_host.py): every state of
+every live (env, position) through reset / init / step, what the LSTM carries, every gradient tensor of the backward against float64 autograd.
 
-The checks are written once here, over a record of tests/slotcase.py; tests/test_gpu_{gru,lstm,avg,caser}_tracker.py bind them to their
-tracker under the test names and ids those files have always had.  (This file is named like a test module so that pytest rewrites its
-assertions; it collects no item of its own.)  The Caser cases' inputs are ones where float64 itself is unambiguous at every max and ReLU
+The checks are written once here, over a record of tests/slotcase.py (nextitnetcase.py and stampcase.py for those two);
+tests/test_gpu_{gru,lstm,avg,caser,nextitnet,stamp}_tracker.py bind them to their tracker under the test names and ids those files have
+always had.  (This file is named like a test module so that pytest rewrites its assertions; it collects no item of its own.)  The Caser cases' inputs are ones where float64 itself is unambiguous at every max and ReLU
 (tests/test_caser_host_cpu.py checks that on the CPU): no case and no element is skipped or masked."""
 import ctypes as C
 
