@@ -168,6 +168,22 @@ class StampState(C.Structure):      # cirs_stamp_state
     _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+NARM_MAX_LAYERS = 1
+
+
+class NarmCfg(C.Structure):         # cirs_narm_cfg
+    _fields_ = list(GruCfg._fields_)
+
+
+class NarmWeights(C.Structure):     # cirs_narm_weights / cirs_narm_grads (same layout)
+    _fields_ = [(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b", "w_ih", "w_hh", "b_ih", "b_hh",
+                                          "a1", "a2", "v", "bw", "dec_w", "dec_b")]
+
+
+class NarmState(C.Structure):       # cirs_narm_state
+    _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("h_hist", C.c_void_p), ("q_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -484,6 +500,14 @@ SIGNATURES = {
     "cirs_rollout_collect_stamp": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(StampCfg), C.POINTER(StampWeights),
                                              C.POINTER(StampState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                              C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_narm_tracker_init": (C.c_int, [C.POINTER(NarmCfg), C.POINTER(NarmWeights), C.POINTER(NarmState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_narm_tracker_step": (C.c_int, [C.POINTER(NarmCfg), C.POINTER(NarmWeights), C.POINTER(NarmState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_narm_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(NarmCfg), C.c_int32]),
+    "cirs_narm_tracker_backward": (C.c_int, [C.POINTER(NarmCfg), C.POINTER(NarmWeights), C.POINTER(NarmState), _P, _P, _P, _P, _P, _P, _P, C.c_int32,
+                                             _P, C.POINTER(NarmWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_narm": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(NarmCfg), C.POINTER(NarmWeights),
+                                            C.POINTER(NarmState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                            C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

@@ -1,15 +1,16 @@
 """StateTrackerTransformer (reference core/state_tracker.py:128-250), StateTrackerGRU and StateTrackerLSTM (:282-289, declared empty
 there), StateTrackerAvg (a pooled window over the last items; no counterpart there), StateTrackerCaser (Caser's convolutions over that
 window; no counterpart there either), StateTrackerNextItNet (NextItNet's dilated causal convolutions over the item slots; no counterpart
-either) and StateTrackerSTAMP (STAMP's attention pool over that window; no counterpart either) on the device engines.
+either), StateTrackerSTAMP (STAMP's attention pool over that window; no counterpart either) and StateTrackerNARM (NARM's GRU encoder with
+attention over its hidden states; no counterpart either) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
 buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
 LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions, csrc/nextitnet_tracker.hip: the dilated
-blocks, csrc/stamp_tracker.hip: the attention pool) and the gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward /
-cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward / cirs_nextitnet_tracker_backward /
-cirs_stamp_tracker_backward (no autograd graph)."""
+blocks, csrc/stamp_tracker.hip: the attention pool, csrc/narm_tracker.hip: the GRU cell and the attention over its hidden states) and the
+gradient arrives through cirs_tracker_backward / cirs_gru_tracker_backward / cirs_lstm_tracker_backward / cirs_avg_tracker_backward /
+cirs_caser_tracker_backward / cirs_nextitnet_tracker_backward / cirs_stamp_tracker_backward / cirs_narm_tracker_backward (no autograd graph)."""
 import numpy as np
 import torch
 from torch import nn
@@ -19,6 +20,7 @@ from cirs_hip.caser_tracker import DeviceCaserTracker, caser_param_shapes, check
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
+from cirs_hip.narm_tracker import DeviceNarmTracker, check_narm_shape, init_narm_tracker_params, narm_param_shapes
 from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, check_nextitnet_shape, init_nextitnet_tracker_params, nextitnet_param_shapes
 from cirs_hip.stamp_tracker import DeviceStampTracker, check_stamp_shape, init_stamp_tracker_params, stamp_param_shapes
 from cirs_hip.tracker import DeviceTracker, flat_tracker_params, tracker_param_shapes
@@ -161,7 +163,7 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet and StateTrackerSTAMP share: StateTrackerTransformer's constructor keywords (a
+    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet, StateTrackerSTAMP and StateTrackerNARM share: StateTrackerTransformer's constructor keywords (a
     script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
     with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
     module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
@@ -309,3 +311,17 @@ class StateTrackerSTAMP(_RecurrentStateTracker):
 
     def _engine_kw(self):
         return dict(window_size=self.window_size)
+
+
+class StateTrackerNARM(_RecurrentStateTracker):
+    """The GRU encoder with attention over its hidden states: the same input slots, torch.nn.GRU(dim_model, dim_model, 1) with h_{-1} = 0 over
+    them, NARM's additive attention of position p over every hidden state so far -- alpha_{p,j} = v . sigmoid(A1 h_p + A2 h_j), no softmax,
+    c_p = sum_j alpha_{p,j} h_j -- the bilinear read-out Bw [h_p ; c_p], the same decoder (the reference has no counterpart).
+    StateTrackerTransformer's constructor keywords; nhead and d_hid are accepted and unused; nlayers must be 1 (one encoder layer is built).
+    dropout is accepted and unused: the paper's two dropout sites (on the item embeddings and in front of the bilinear read-out) are not
+    built.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
+    CELL, ENGINE, param_shapes, init_params = "NARM", DeviceNarmTracker, narm_param_shapes, init_narm_tracker_params
+
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len):
+        check_narm_shape(dim_model, dim_state, nlayers, max_len)
+        self.dropout_p, self.nlayers = 0.0, int(nlayers)

@@ -1,5 +1,5 @@
-// slot_tracker.h -- what the six slot trackers (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip,
-// stamp_tracker.hip) share besides tracker_rows.h.  Device: the sigmoid and the gather of the stored input slots (the recurrent two).  Host: the checks of a
+// slot_tracker.h -- what the seven slot trackers (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip,
+// stamp_tracker.hip, narm_tracker.hip) share besides tracker_rows.h.  Device: the sigmoid and the gather of the stored input slots (the recurrent three).  Host: the checks of a
 // cfg / weights / grads triple (the six trackers' structs have the same members around a different cell), the carving of a backward's workspace, the bodies
 // of the entry points (init, step, workspace size), the walk count of a step launch, and the last stage of the backward (input
 // slots + embeddings).

@@ -1,5 +1,5 @@
-// tracker_rows.h -- what the backward passes of the Transformer tracker (tracker_bwd.hip) and of the six slot trackers (through slot_tracker.h: gru_, lstm_,
-// avg_, caser_, nextitnet_, stamp_tracker.hip) run on the buffer rows:
+// tracker_rows.h -- what the backward passes of the Transformer tracker (tracker_bwd.hip) and of the seven slot trackers (through slot_tracker.h: gru_, lstm_,
+// avg_, caser_, nextitnet_, stamp_, narm_tracker.hip) run on the buffer rows:
 //   dw_batch_*            several weight-gradient problems over the same rows in one launch (slab partials, summed by dw_list_final)
 //   gather_dstate         upstream gradient rows from dstate [T+1, B, S]
 //   slot_bwd              backward of the input slots (user projection / gated action) down to the per-row embedding contributions

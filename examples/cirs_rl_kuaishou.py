@@ -36,7 +36,7 @@ from core.inputs import get_dataset_columns  # noqa: E402
 from torch.utils.tensorboard import SummaryWriter  # noqa: E402
 
 from core.collector import Collector  # noqa: E402
-from core.state_tracker import StateTrackerTransformer  # noqa: E402
+from core.state_tracker import StateTrackerNARM, StateTrackerTransformer  # noqa: E402
 from core.user_model import compute_input_dim  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
 from core.user_model_pairwise import UserModel_Pairwise  # noqa: E402
@@ -87,6 +87,8 @@ def get_args(argv=None):
     p.add_argument("--dim_state", default=20, type=int)
     p.add_argument("--dim_model", default=32, type=int)
     p.add_argument("--nhead", default=4, type=int)
+    p.add_argument("--tracker", choices=["transformer", "narm"], default="transformer",
+                   help="state tracker: the reference's Transformer, or NARM's GRU encoder with attention over its hidden states (StateTrackerNARM)")
     p.add_argument("--force_length", type=int, default=10)
     p.add_argument("--top_rate", type=float, default=0.8)
     # trainer
@@ -194,12 +196,20 @@ def main(args):
     user_columns, action_columns, feedback_columns, has_user_embedding, has_action_embedding, has_feedback_embedding = \
         get_dataset_columns(args.dim_model, envname=args.env, env=env)
     assert args.dim_model == compute_input_dim(action_columns)
-    state_tracker = StateTrackerTransformer(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
-                                            dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),
-                                            dataset=args.env, has_user_embedding=has_user_embedding,
-                                            has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
-                                            nhead=args.nhead, d_hid=128, nlayers=2, dropout=0.1, device=device, seed=args.seed,
-                                            MAX_TURN=args.max_turn).to(device)
+    if args.tracker == "narm":      # the same keywords; one encoder layer, and the model has no dropout site
+        state_tracker = StateTrackerNARM(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
+                                         dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),
+                                         dataset=args.env, has_user_embedding=has_user_embedding,
+                                         has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
+                                         nhead=args.nhead, d_hid=128, nlayers=1, dropout=0.0, device=device, seed=args.seed,
+                                         MAX_TURN=args.max_turn).to(device)
+    else:
+        state_tracker = StateTrackerTransformer(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
+                                                dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),
+                                                dataset=args.env, has_user_embedding=has_user_embedding,
+                                                has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
+                                                nhead=args.nhead, d_hid=128, nlayers=2, dropout=0.1, device=device, seed=args.seed,
+                                                MAX_TURN=args.max_turn).to(device)
     net = Net(args.dim_state, hidden_sizes=args.hidden_sizes, device=device)
     actor = Actor(net, env.mat.shape[1], device=device).to(device)
     critic = Critic(net, device=device).to(device)

@@ -25,8 +25,8 @@ from core.collector_set import CollectorSet  # noqa: E402
 from core.trainer.onpolicy import onpolicy_trainer  # noqa: E402
 from core.inputs import get_dataset_columns  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
-from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerGRU, StateTrackerLSTM, StateTrackerNextItNet,  # noqa: E402
-                                StateTrackerSTAMP, StateTrackerTransformer)
+from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerGRU, StateTrackerLSTM, StateTrackerNARM,  # noqa: E402
+                                StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerTransformer)
 from core.user_model import compute_input_dim  # noqa: E402
 from tianshou.data import VectorReplayBuffer  # noqa: E402
 from tianshou.env import DummyVectorEnv  # noqa: E402
@@ -71,11 +71,11 @@ def get_args(argv=None):
                         "dropout site is not built: a positive value is refused)")
     p.add_argument("--deterministic-eval", action="store_true",
                    help="test collectors take the policy's arg-max item instead of a sample (PPOPolicy(deterministic_eval=True))")
-    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp"], default="transformer",
+    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp", "narm"], default="transformer",
                    help="state tracker: the reference's Transformer, a recurrent one it announces (StateTrackerGRU, StateTrackerLSTM), "
                         "the pooled window over the last items (StateTrackerAvg), Caser's convolutions over that window (StateTrackerCaser), "
-                        "NextItNet's dilated causal convolutions over the item slots (StateTrackerNextItNet), or STAMP's attention pool over "
-                        "that window (StateTrackerSTAMP)")
+                        "NextItNet's dilated causal convolutions over the item slots (StateTrackerNextItNet), STAMP's attention pool over "
+                        "that window (StateTrackerSTAMP), or NARM's GRU encoder with attention over its hidden states (StateTrackerNARM)")
     p.add_argument("--gru-layers", type=int, default=1, help="layers of --tracker gru (1 or 2; 2 needs --dropout 0)")
     p.add_argument("--lstm-layers", type=int, default=1, choices=[1, 2], help="layers of --tracker lstm (2 needs --dropout 0)")
     p.add_argument("--window-size", type=int, default=10, help="item slots in the window of --tracker avg / caser / stamp (stamp: 1..16)")
@@ -118,7 +118,7 @@ def build(args, table_seed=0):
     tracker_cls, tracker_layers = {"gru": (StateTrackerGRU, args.gru_layers), "lstm": (StateTrackerLSTM, args.lstm_layers),
                                    "transformer": (StateTrackerTransformer, 2), "avg": (StateTrackerAvg, 1),
                                    "caser": (StateTrackerCaser, 1), "nextitnet": (StateTrackerNextItNet, 1),
-                                   "stamp": (StateTrackerSTAMP, 1)}[args.tracker]
+                                   "stamp": (StateTrackerSTAMP, 1), "narm": (StateTrackerNARM, 1)}[args.tracker]
     tracker_kw = {"avg": {"window_size": args.window_size},
                   "caser": {"window_size": args.window_size, "filter_sizes": args.filter_sizes},
                   "nextitnet": {"dilations": args.dilations}, "stamp": {"window_size": args.window_size}}.get(args.tracker, {})

@@ -1103,6 +1103,90 @@ int cirs_rollout_collect_stamp(const cirs_env_cfg* env_cfg, const cirs_env_table
                                int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, a GRU encoder with attention over its hidden states: StateTrackerNARM (csrc/narm_tracker.hip)
+ * The reference has no counterpart; the model is defined here (NARM, Li et al., CIKM 2017: the last hidden state as the global
+ * encoder, an additive attention over every hidden state of the session as the local one, a bilinear read-out):
+ *   inputs     the GRU tracker's slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k
+ *   encoder    h_p = GRU cell(x_p, h_{p-1}), h_{-1} = 0: torch.nn.GRU(D, D, 1), gate order r, z, n, both bias vectors
+ *   attention  for position p over j = 0 .. p (the whole session so far, position 0 and p itself included):
+ *                q_j = A2 h_j,  a_p = A1 h_p
+ *                alpha_{p,j} = v . sigmoid(a_p + q_j)          (a scalar; no softmax, as in the paper)
+ *                c_p = sum_{j=0}^{p} alpha_{p,j} h_j
+ *   read-out   m_p = Bw [h_p ; c_p]                            (Bw: D x 2D; global = h_p, local = c_p);  s_p = decoder(m_p)
+ * A1, A2, v and Bw have no bias (the paper has none).  The attention spans the whole session: a step costs O(p) at position p.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, ONE encoder layer (the cfg keeps the GRU tracker's `nlayers` member so
+ * that the two cfgs have one layout; any value but 1 is refused), max_len <= 4096.  The paper's two dropout sites are not built.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_NARM_MAX_LAYERS 1
+
+typedef struct cirs_narm_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t nlayers;   /* 1 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_narm_cfg;
+
+typedef struct cirs_narm_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float *w_ih, *w_hh, *b_ih, *b_hh; /* gru.weight_ih_l0, gru.weight_hh_l0 [3D,D]; gru.bias_ih_l0, gru.bias_hh_l0 [3D]; rows r | z | n */
+    const float *a1, *a2;                 /* attn.a1.weight, attn.a2.weight [D,D] */
+    const float* v;                       /* attn.v.weight [1,D] */
+    const float* bw;                      /* bilinear.weight [D,2D]: columns [0,D) read h_p, [D,2D) read c_p */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_narm_weights;
+
+typedef struct cirs_narm_state {
+    float* x_hist; /* [B, max_len, D] the input slots (what the backward recomputes from) */
+    float* h;      /* [1, B, D] the carried hidden state */
+    float* h_hist; /* [B, max_len, D] h_j of every position appended so far */
+    float* q_hist; /* [B, max_len, D] q_j = A2 h_j: A2 is applied once per position, not once per pair */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_narm_state;
+
+typedef struct cirs_narm_grads { /* same tensors, same order as cirs_narm_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float *w_ih, *w_hh, *b_ih, *b_hh, *a1, *a2, *v, *bw;
+    float *dec_w, *dec_b;
+} cirs_narm_grads;
+
+/* cirs_gru_tracker_init / cirs_gru_tracker_step for the NARM tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, h_0, q_0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of
+ * range (item < 0: the env finished), a never-initialised or a full history are left untouched: neither the tracker state nor their row of
+ * state_out is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes is refused (CIRS_E_INVALID /
+ * CIRS_E_UNSUPPORTED) with a message prefixed "narm tracker:", before any pointer is read. */
+int cirs_narm_tracker_init(const cirs_narm_cfg* cfg, const cirs_narm_weights* w, cirs_narm_state* st, const int32_t* users,
+                           const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_narm_tracker_step(const cirs_narm_cfg* cfg, const cirs_narm_weights* w, cirs_narm_state* st, const int64_t* items,
+                           const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                           int64_t state_stride, void* stream);
+
+/* cirs_gru_tracker_backward for the NARM tracker: the encoder is recomputed from the stored slots by the GRU tracker's sequential
+ * kernels, the attention per buffer row (nothing per (p, j) pair is stored: the workspace is O(n_rows)); its backward runs once by query
+ * row and once by key row, both parallel over the rows, and feeds dH into the GRU's sequential back-propagation through time.  Same
+ * arguments as cirs_gru_tracker_backward; of st only x_hist is read.  Every gradient tensor is OVERWRITTEN.  No float atomics; every
+ * reduction has a fixed order, so two calls give the same bits.  A workspace smaller than
+ * cirs_narm_tracker_backward_workspace_bytes(cfg, n_rows) (0 for a cfg that is refused), or one not 16-byte aligned, is refused before any
+ * launch. */
+int64_t cirs_narm_tracker_backward_workspace_bytes(const cirs_narm_cfg* cfg, int32_t n_rows);
+int cirs_narm_tracker_backward(const cirs_narm_cfg* cfg, const cirs_narm_weights* w, const cirs_narm_state* st, const int32_t* users,
+                               const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                               const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                               const cirs_narm_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with a NARM tracker: the same launch sequence (one loop serves the seven, csrc/rollout.hip) with
+ * cirs_narm_tracker_init / cirs_narm_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_narm(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                              const cirs_narm_cfg* trk_cfg, const cirs_narm_weights* trk_w, cirs_narm_state* trk_st,
+                              const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                              const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                              int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),
