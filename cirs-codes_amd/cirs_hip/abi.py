@@ -184,6 +184,24 @@ class NarmState(C.Structure):       # cirs_narm_state
     _fields_ = [("x_hist", C.c_void_p), ("h", C.c_void_p), ("h_hist", C.c_void_p), ("q_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+FMLP_MAX_WINDOW, FMLP_MAX_LAYERS, FMLP_HIDDEN = 16, 2, 128
+FMLP_LAYER_MEMBERS = ("cw", "fln_w", "fln_b", "d1_w", "d1_b", "d2_w", "d2_b", "ln_w", "ln_b")
+
+
+class FmlpCfg(C.Structure):         # cirs_fmlp_cfg
+    _fields_ = [("n_users", C.c_int32), ("n_items", C.c_int32), ("dim_model", C.c_int32), ("dim_state", C.c_int32),
+                ("window", C.c_int32), ("nlayers", C.c_int32), ("max_len", C.c_int32), ("n_env", C.c_int32)]
+
+
+class FmlpWeights(C.Structure):     # cirs_fmlp_weights / cirs_fmlp_grads (same layout): every layer member is an array over the layers
+    _fields_ = ([(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b")] +
+                [(k, C.c_void_p * FMLP_MAX_LAYERS) for k in FMLP_LAYER_MEMBERS] + [("dec_w", C.c_void_p), ("dec_b", C.c_void_p)])
+
+
+class FmlpState(C.Structure):       # cirs_fmlp_state
+    _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -507,6 +525,14 @@ SIGNATURES = {
                                              _P, C.POINTER(NarmWeights), _P, C.c_int64, _P]),
     "cirs_rollout_collect_narm": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(NarmCfg), C.POINTER(NarmWeights),
                                             C.POINTER(NarmState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                            C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_fmlp_tracker_init": (C.c_int, [C.POINTER(FmlpCfg), C.POINTER(FmlpWeights), C.POINTER(FmlpState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_fmlp_tracker_step": (C.c_int, [C.POINTER(FmlpCfg), C.POINTER(FmlpWeights), C.POINTER(FmlpState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_fmlp_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(FmlpCfg), C.c_int32]),
+    "cirs_fmlp_tracker_backward": (C.c_int, [C.POINTER(FmlpCfg), C.POINTER(FmlpWeights), C.POINTER(FmlpState), _P, _P, _P, _P, _P, _P, _P, C.c_int32,
+                                             _P, C.POINTER(FmlpWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_fmlp": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(FmlpCfg), C.POINTER(FmlpWeights),
+                                            C.POINTER(FmlpState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                             C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),

@@ -167,8 +167,8 @@ static int unfused_vector_step(const cirs_env_cfg* env_cfg, const cirs_env_table
     return tracker_step(act_t, rew_t, obs_n);
 }
 
-// cirs_rollout_collect with a slot tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip, stamp_tracker.hip):
-// unfused_vector_step without the scorer, built from the public entry points -- about five launches per vector step against the fused Transformer
+// cirs_rollout_collect with a slot tracker (gru_tracker.hip, lstm_tracker.hip, avg_tracker.hip, caser_tracker.hip, nextitnet_tracker.hip, stamp_tracker.hip,
+// narm_tracker.hip, fmlp_tracker.hip): unfused_vector_step without the scorer, built from the public entry points -- about five launches per vector step against the fused Transformer
 // collect's two.  One loop for all of them: `init` / `step` are the tracker's entry points, `what` names it in the messages.
 template <class Cfg, class Weights, class State>
 static int collect_recurrent(const char* what, int (*init)(const Cfg*, const Weights*, State*, const int32_t*, const int32_t*, int32_t, float*, int64_t, void*),
@@ -264,6 +264,15 @@ extern "C" int cirs_rollout_collect_narm(const cirs_env_cfg* env_cfg, const cirs
                                          const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
                                          int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
     return cirs::collect_recurrent("narm", cirs_narm_tracker_init, cirs_narm_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w,
+                                   traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cirs_rollout_collect_fmlp(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                         const cirs_fmlp_cfg* trk_cfg, const cirs_fmlp_weights* trk_w, cirs_fmlp_state* trk_st,
+                                         const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                         const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                         int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    return cirs::collect_recurrent("fmlp", cirs_fmlp_tracker_init, cirs_fmlp_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w,
                                    traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
 }
 

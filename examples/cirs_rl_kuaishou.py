@@ -36,7 +36,7 @@ from core.inputs import get_dataset_columns  # noqa: E402
 from torch.utils.tensorboard import SummaryWriter  # noqa: E402
 
 from core.collector import Collector  # noqa: E402
-from core.state_tracker import StateTrackerNARM, StateTrackerTransformer  # noqa: E402
+from core.state_tracker import StateTrackerFMLP, StateTrackerNARM, StateTrackerTransformer  # noqa: E402
 from core.user_model import compute_input_dim  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
 from core.user_model_pairwise import UserModel_Pairwise  # noqa: E402
@@ -87,8 +87,11 @@ def get_args(argv=None):
     p.add_argument("--dim_state", default=20, type=int)
     p.add_argument("--dim_model", default=32, type=int)
     p.add_argument("--nhead", default=4, type=int)
-    p.add_argument("--tracker", choices=["transformer", "narm"], default="transformer",
-                   help="state tracker: the reference's Transformer, or NARM's GRU encoder with attention over its hidden states (StateTrackerNARM)")
+    p.add_argument("--tracker", choices=["transformer", "narm", "fmlp"], default="transformer",
+                   help="state tracker: the reference's Transformer, NARM's GRU encoder with attention over its hidden states (StateTrackerNARM), "
+                        "or FMLP-Rec's learnable filter and feed-forward block over the last items (StateTrackerFMLP)")
+    p.add_argument("--window-size", type=int, default=10, help="item slots in the window of --tracker fmlp (1..16)")
+    p.add_argument("--fmlp-layers", type=int, default=2, help="layers of --tracker fmlp (1 or 2)")
     p.add_argument("--force_length", type=int, default=10)
     p.add_argument("--top_rate", type=float, default=0.8)
     # trainer
@@ -203,6 +206,13 @@ def main(args):
                                          has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
                                          nhead=args.nhead, d_hid=128, nlayers=1, dropout=0.0, device=device, seed=args.seed,
                                          MAX_TURN=args.max_turn).to(device)
+    elif args.tracker == "fmlp":    # the Transformer's keywords plus the window; the model's dropout sites are not built
+        state_tracker = StateTrackerFMLP(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
+                                         dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),
+                                         dataset=args.env, has_user_embedding=has_user_embedding,
+                                         has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
+                                         nhead=args.nhead, d_hid=128, nlayers=args.fmlp_layers, dropout=0.0, device=device, seed=args.seed,
+                                         MAX_TURN=args.max_turn, window_size=args.window_size).to(device)
     else:
         state_tracker = StateTrackerTransformer(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
                                                 dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),

@@ -25,7 +25,7 @@ from core.collector_set import CollectorSet  # noqa: E402
 from core.trainer.onpolicy import onpolicy_trainer  # noqa: E402
 from core.inputs import get_dataset_columns  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
-from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerGRU, StateTrackerLSTM, StateTrackerNARM,  # noqa: E402
+from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerFMLP, StateTrackerGRU, StateTrackerLSTM, StateTrackerNARM,  # noqa: E402
                                 StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerTransformer)
 from core.user_model import compute_input_dim  # noqa: E402
 from tianshou.data import VectorReplayBuffer  # noqa: E402
@@ -71,14 +71,17 @@ def get_args(argv=None):
                         "dropout site is not built: a positive value is refused)")
     p.add_argument("--deterministic-eval", action="store_true",
                    help="test collectors take the policy's arg-max item instead of a sample (PPOPolicy(deterministic_eval=True))")
-    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp", "narm"], default="transformer",
+    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp", "narm", "fmlp"], default="transformer",
                    help="state tracker: the reference's Transformer, a recurrent one it announces (StateTrackerGRU, StateTrackerLSTM), "
                         "the pooled window over the last items (StateTrackerAvg), Caser's convolutions over that window (StateTrackerCaser), "
                         "NextItNet's dilated causal convolutions over the item slots (StateTrackerNextItNet), STAMP's attention pool over "
-                        "that window (StateTrackerSTAMP), or NARM's GRU encoder with attention over its hidden states (StateTrackerNARM)")
+                        "that window (StateTrackerSTAMP), NARM's GRU encoder with attention over its hidden states (StateTrackerNARM), or "
+                        "FMLP-Rec's learnable filter and feed-forward block over that window (StateTrackerFMLP)")
     p.add_argument("--gru-layers", type=int, default=1, help="layers of --tracker gru (1 or 2; 2 needs --dropout 0)")
     p.add_argument("--lstm-layers", type=int, default=1, choices=[1, 2], help="layers of --tracker lstm (2 needs --dropout 0)")
-    p.add_argument("--window-size", type=int, default=10, help="item slots in the window of --tracker avg / caser / stamp (stamp: 1..16)")
+    p.add_argument("--window-size", type=int, default=10,
+                   help="item slots in the window of --tracker avg / caser / stamp / fmlp (stamp, fmlp: 1..16)")
+    p.add_argument("--fmlp-layers", type=int, default=2, help="layers of --tracker fmlp (1 or 2)")
     p.add_argument("--filter-sizes", type=lambda t: tuple(int(h) for h in t.split(",")), default=(2, 3, 4),
                    help="heights of the horizontal filter banks of --tracker caser, ascending, comma-separated (each in 1..4)")
     p.add_argument("--dilations", type=lambda t: tuple(int(d) for d in t.split(",")), default=(1, 2, 4),
@@ -118,10 +121,12 @@ def build(args, table_seed=0):
     tracker_cls, tracker_layers = {"gru": (StateTrackerGRU, args.gru_layers), "lstm": (StateTrackerLSTM, args.lstm_layers),
                                    "transformer": (StateTrackerTransformer, 2), "avg": (StateTrackerAvg, 1),
                                    "caser": (StateTrackerCaser, 1), "nextitnet": (StateTrackerNextItNet, 1),
-                                   "stamp": (StateTrackerSTAMP, 1), "narm": (StateTrackerNARM, 1)}[args.tracker]
+                                   "stamp": (StateTrackerSTAMP, 1), "narm": (StateTrackerNARM, 1),
+                                   "fmlp": (StateTrackerFMLP, args.fmlp_layers)}[args.tracker]
     tracker_kw = {"avg": {"window_size": args.window_size},
                   "caser": {"window_size": args.window_size, "filter_sizes": args.filter_sizes},
-                  "nextitnet": {"dilations": args.dilations}, "stamp": {"window_size": args.window_size}}.get(args.tracker, {})
+                  "nextitnet": {"dilations": args.dilations}, "stamp": {"window_size": args.window_size},
+                  "fmlp": {"window_size": args.window_size}}.get(args.tracker, {})
     state_tracker = tracker_cls(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
                                 dim_state=args.dim_state, dim_max_batch=args.training_num, dataset=args.env,
                                 has_user_embedding=has_user_embedding, has_action_embedding=has_action_embedding,

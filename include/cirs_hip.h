@@ -1187,6 +1187,105 @@ int cirs_rollout_collect_narm(const cirs_env_cfg* env_cfg, const cirs_env_tables
                               int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, a learnable frequency-domain filter and an MLP: StateTrackerFMLP (csrc/fmlp_tracker.hip)
+ * The reference has no counterpart; the model is defined here (FMLP-Rec, Zhou et al., WWW 2022: self-attention replaced by a learned
+ * per-channel circular filter, then the Transformer's LayerNorm / GELU feed-forward block; nothing carried):
+ *   inputs     the other trackers' slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k;
+ *              no sqrt(D) scale, no positional encoding, no LayerNorm on the input
+ *   tile       Y^{-1}[i] = x_{p-W+1+i} if p-W+1+i >= 1 else 0, i = 0 .. W-1   (left zero padding; row W-1 is the newest item)
+ *   layer l    w_l = complex_weight_l [W/2+1, D] complex (stored [W/2+1, D, 2]: re, im);  h_l = irfft(w_l, n = W)  [W, D]
+ *              F[i,d]  = sum_{m<W} h_l[(i-m) mod W, d] Y^{l-1}[m,d]           (= irfft(rfft(Y, ortho) w_l, n = W, ortho) over the rows)
+ *              A       = LayerNorm(Y^{l-1} + F)                              (filter.ln, eps 1e-5)
+ *              M       = dense_2(gelu(dense_1(A)))                           (D -> 128 -> D, the exact erf GELU)
+ *              Y^l     = LayerNorm(A + M)                                    (ffn.ln)
+ *   state      h_p = x_0 + Y^{L-1}[W-1]  (p >= 1),  h_0 = x_0;  s_p = decoder(h_p)
+ * Rows before the first item are zero at the input of layer 0 only: the circular filter writes into them and the next layer reads them
+ * (FMLP-Rec masks nothing).  The imaginary parts of the DC bin and, for even W, of the Nyquist bin have no effect; their gradient is
+ * exactly 0.  The taps h_l are formed from complex_weight on the device, the phase index k n reduced modulo W as an integer first.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, 1 <= window <= 16 (one 16-row tile), nlayers in {1, 2}, the hidden width
+ * 128, max_len <= 4096.  FMLP-Rec's two dropout sites are not built.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_FMLP_MAX_WINDOW 16
+#define CIRS_FMLP_MAX_LAYERS 2
+#define CIRS_FMLP_HIDDEN 128
+
+typedef struct cirs_fmlp_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t window;    /* W in 1..16: rows of the tile */
+    int32_t nlayers;   /* L in {1, 2} */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_fmlp_cfg;
+
+typedef struct cirs_fmlp_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    /* per layer l (entries l >= nlayers are not read): */
+    const float* cw[CIRS_FMLP_MAX_LAYERS];    /* layers.l.filter.complex_weight [W/2+1, D, 2] */
+    const float* fln_w[CIRS_FMLP_MAX_LAYERS]; /* layers.l.filter.ln.weight [D] */
+    const float* fln_b[CIRS_FMLP_MAX_LAYERS]; /* layers.l.filter.ln.bias [D] */
+    const float* d1_w[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.dense_1.weight [128,D] */
+    const float* d1_b[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.dense_1.bias [128] */
+    const float* d2_w[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.dense_2.weight [D,128] */
+    const float* d2_b[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.dense_2.bias [D] */
+    const float* ln_w[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.ln.weight [D] */
+    const float* ln_b[CIRS_FMLP_MAX_LAYERS];  /* layers.l.ffn.ln.bias [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_fmlp_weights;
+
+typedef struct cirs_fmlp_state {
+    float* x_hist; /* [B, max_len, D] the input slots: the tile of every step and the backward read them */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_fmlp_state;
+
+typedef struct cirs_fmlp_grads { /* same tensors, same order as cirs_fmlp_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float *cw[CIRS_FMLP_MAX_LAYERS], *fln_w[CIRS_FMLP_MAX_LAYERS], *fln_b[CIRS_FMLP_MAX_LAYERS], *d1_w[CIRS_FMLP_MAX_LAYERS],
+        *d1_b[CIRS_FMLP_MAX_LAYERS], *d2_w[CIRS_FMLP_MAX_LAYERS], *d2_b[CIRS_FMLP_MAX_LAYERS], *ln_w[CIRS_FMLP_MAX_LAYERS],
+        *ln_b[CIRS_FMLP_MAX_LAYERS];
+    float *dec_w, *dec_b;
+} cirs_fmlp_grads;
+
+/* cirs_avg_tracker_init / cirs_avg_tracker_step for the FMLP tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id out of range
+ * (item < 0: the env finished), a never-initialised or a full history are left untouched: neither x_hist, len nor their row of state_out
+ * is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes (window outside 1..16, nlayers outside {1, 2}
+ * among them) is refused (CIRS_E_INVALID / CIRS_E_UNSUPPORTED) with a message prefixed "fmlp tracker:" that names the member, before any
+ * pointer is read. */
+int cirs_fmlp_tracker_init(const cirs_fmlp_cfg* cfg, const cirs_fmlp_weights* w, cirs_fmlp_state* st, const int32_t* users,
+                           const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_fmlp_tracker_step(const cirs_fmlp_cfg* cfg, const cirs_fmlp_weights* w, cirs_fmlp_state* st, const int64_t* items,
+                           const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                           int64_t state_stride, void* stream);
+
+/* cirs_avg_tracker_backward for the FMLP tracker.  No sequential pass: the forward of every buffer row is recomputed from the stored slots
+ * (per layer the input tile, both LayerNorms' normalised values and inverse deviations, A and the hidden pre-activations are kept), the
+ * decoder stage is the other trackers', then per row, top layer down, both LayerNorms, the two dense products transposed, the exact
+ * GELU's derivative and the filter's two correlations give a gradient per tile row, which is folded into dX[b,k] in ascending p
+ * (dX[b,0] = sum_p dH[b,p]); then the slot stage of the recurrent trackers.  The gradient of complex_weight is the closed form of
+ * d irfft applied to the summed tap gradient; the entries without effect receive an exact 0.  Same arguments as
+ * cirs_avg_tracker_backward; of st only x_hist is read.  Every gradient tensor is OVERWRITTEN.  No float atomics; every reduction has a
+ * fixed order, so two calls give the same bits.  A workspace smaller than cirs_fmlp_tracker_backward_workspace_bytes(cfg, n_rows)
+ * (0 for a cfg that is refused), or one not 16-byte aligned, is refused before any launch. */
+int64_t cirs_fmlp_tracker_backward_workspace_bytes(const cirs_fmlp_cfg* cfg, int32_t n_rows);
+int cirs_fmlp_tracker_backward(const cirs_fmlp_cfg* cfg, const cirs_fmlp_weights* w, const cirs_fmlp_state* st, const int32_t* users,
+                               const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                               const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                               const cirs_fmlp_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with an FMLP tracker: the same launch sequence (one loop serves the eight, csrc/rollout.hip) with
+ * cirs_fmlp_tracker_init / cirs_fmlp_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_fmlp(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                              const cirs_fmlp_cfg* trk_cfg, const cirs_fmlp_weights* trk_w, cirs_fmlp_state* trk_st,
+                              const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                              const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                              int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),
