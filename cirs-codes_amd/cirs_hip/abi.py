@@ -202,6 +202,22 @@ class FmlpState(C.Structure):       # cirs_fmlp_state
     _fields_ = [("x_hist", C.c_void_p), ("len", C.c_void_p)]
 
 
+LRU_MAX_LAYERS, LRU_HIDDEN = 1, 128
+LRU_MEMBERS = ("nu_log", "theta_log", "gamma_log", "in_w", "in_b", "out_w", "out_b", "lln_w", "lln_b", "d1_w", "d1_b", "d2_w", "d2_b", "ln_w", "ln_b")
+
+
+class LruCfg(C.Structure):          # cirs_lru_cfg
+    _fields_ = list(GruCfg._fields_)
+
+
+class LruWeights(C.Structure):      # cirs_lru_weights / cirs_lru_grads (same layout)
+    _fields_ = [(k, C.c_void_p) for k in ("emb_user", "emb_item", "ffn_user_w", "ffn_user_b", "gate_w", "gate_b") + LRU_MEMBERS + ("dec_w", "dec_b")]
+
+
+class LruState(C.Structure):        # cirs_lru_state
+    _fields_ = [("x_hist", C.c_void_p), ("h_re", C.c_void_p), ("h_im", C.c_void_p), ("len", C.c_void_p)]
+
+
 class PolicyCfg(C.Structure):
     _fields_ = [("n_items", C.c_int32), ("dim_state", C.c_int32), ("hidden", C.c_int32)]
 
@@ -534,6 +550,14 @@ SIGNATURES = {
     "cirs_rollout_collect_fmlp": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(FmlpCfg), C.POINTER(FmlpWeights),
                                             C.POINTER(FmlpState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
                                             C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
+    "cirs_lru_tracker_init": (C.c_int, [C.POINTER(LruCfg), C.POINTER(LruWeights), C.POINTER(LruState), _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_lru_tracker_step": (C.c_int, [C.POINTER(LruCfg), C.POINTER(LruWeights), C.POINTER(LruState), _P, _P, _P, _P, C.c_int32, _P, C.c_int64, _P]),
+    "cirs_lru_tracker_backward_workspace_bytes": (C.c_int64, [C.POINTER(LruCfg), C.c_int32]),
+    "cirs_lru_tracker_backward": (C.c_int, [C.POINTER(LruCfg), C.POINTER(LruWeights), C.POINTER(LruState), _P, _P, _P, _P, _P, _P, _P, C.c_int32,
+                                            _P, C.POINTER(LruWeights), _P, C.c_int64, _P]),
+    "cirs_rollout_collect_lru": (C.c_int, [C.POINTER(EnvCfg), C.POINTER(EnvTables), C.POINTER(EnvState), C.POINTER(LruCfg), C.POINTER(LruWeights),
+                                           C.POINTER(LruState), C.POINTER(PolicyCfg), C.POINTER(PolicyWeights), C.POINTER(Traj), C.c_int32, _P,
+                                           C.c_uint64, C.c_uint32, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_embedding_scatter_workspace_bytes": (C.c_int64, [C.c_int64]),
     "cirs_embedding_scatter": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, _P, C.c_int64, _P]),
     "cirs_deepfm_forward": (C.c_int, [C.POINTER(DeepFMCfg), C.POINTER(DeepFMWeights), _P, _P, _P, _P, C.c_int32, _P, _P]),

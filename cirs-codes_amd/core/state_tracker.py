@@ -2,17 +2,20 @@
 there), StateTrackerAvg (a pooled window over the last items; no counterpart there), StateTrackerCaser (Caser's convolutions over that
 window; no counterpart there either), StateTrackerNextItNet (NextItNet's dilated causal convolutions over the item slots; no counterpart
 either), StateTrackerSTAMP (STAMP's attention pool over that window; no counterpart either), StateTrackerNARM (NARM's GRU encoder with
-attention over its hidden states; no counterpart either) and StateTrackerFMLP (FMLP-Rec's learnable filter and feed-forward block over that
-window; no counterpart either) on the device engines.
+attention over its hidden states; no counterpart either), StateTrackerFMLP (FMLP-Rec's learnable filter and feed-forward block over that
+window; no counterpart either) and StateTrackerLRU (a linear recurrent unit, the diagonal complex recurrence of LRURec, with that
+feed-forward block; no counterpart either) on the device engines.
 
 Same constructor keywords and the same three `build_state` call forms the Collector uses (collector.py:127-134,261-269).
 Parameters are exposed under state_dict names (the reference's; torch.nn.GRU's / nn.LSTM's for the recurrence) but live in ONE flat device
 buffer; the forward is a one-launch step kernel (csrc/tracker.hip: KV-cached decode, csrc/gru_tracker.hip: GRU cells, csrc/lstm_tracker.hip:
 LSTM cells, csrc/avg_tracker.hip: the window mean, csrc/caser_tracker.hip: the window's convolutions, csrc/nextitnet_tracker.hip: the dilated
 blocks, csrc/stamp_tracker.hip: the attention pool, csrc/narm_tracker.hip: the GRU cell and the attention over its hidden states,
-csrc/fmlp_tracker.hip: the filter and the feed-forward block) and the gradient arrives through cirs_tracker_backward /
+csrc/fmlp_tracker.hip: the filter and the feed-forward block, csrc/lru_tracker.hip: the linear recurrence and the feed-forward block) and the
+gradient arrives through cirs_tracker_backward /
 cirs_gru_tracker_backward / cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward /
-cirs_nextitnet_tracker_backward / cirs_stamp_tracker_backward / cirs_narm_tracker_backward / cirs_fmlp_tracker_backward (no autograd graph)."""
+cirs_nextitnet_tracker_backward / cirs_stamp_tracker_backward / cirs_narm_tracker_backward / cirs_fmlp_tracker_backward /
+cirs_lru_tracker_backward (no autograd graph)."""
 import inspect
 
 import numpy as np
@@ -24,6 +27,7 @@ from cirs_hip.caser_tracker import DeviceCaserTracker, caser_param_shapes, check
 from cirs_hip.engine import init_tracker_params
 from cirs_hip.fmlp_tracker import DeviceFmlpTracker, check_fmlp_shape, fmlp_param_shapes, init_fmlp_tracker_params
 from cirs_hip.gru_tracker import DeviceGruTracker, check_gru_shape, gru_param_shapes, init_gru_tracker_params
+from cirs_hip.lru_tracker import DeviceLruTracker, check_lru_shape, init_lru_tracker_params, lru_param_shapes
 from cirs_hip.lstm_tracker import DeviceLstmTracker, check_lstm_shape, init_lstm_tracker_params, lstm_param_shapes
 from cirs_hip.narm_tracker import DeviceNarmTracker, check_narm_shape, init_narm_tracker_params, narm_param_shapes
 from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, check_nextitnet_shape, init_nextitnet_tracker_params, nextitnet_param_shapes
@@ -168,7 +172,7 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerNARM and StateTrackerFMLP share: StateTrackerTransformer's constructor keywords (a
+    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerNARM, StateTrackerFMLP and StateTrackerLRU share: StateTrackerTransformer's constructor keywords (a
     script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
     with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
     module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
@@ -355,3 +359,25 @@ class StateTrackerFMLP(_RecurrentStateTracker):
 
     def _model_kw(self):
         return dict(window_size=self.window_size, nlayers=self.nlayers)
+
+
+class StateTrackerLRU(_RecurrentStateTracker):
+    """The linear-recurrence tracker: the same input slots, a linear recurrent unit over them -- the diagonal complex recurrence
+    h_p = lambda * h_{p-1} + gamma * (W_in x_p + b_in) with lambda = exp(-exp(nu_log) + i exp(theta_log)), |lambda| < 1 by construction, 64 carried
+    floats per env whatever the position -- the real read-out W_out [h_re ; h_im] + b_out, LayerNorm on the residual, the 32 -> 128 -> 32
+    feed-forward block with the exact GELU, LayerNorm, the same decoder (the reference has no counterpart).
+    StateTrackerTransformer's constructor keywords; nlayers must be 1 and d_hid 128; nhead is accepted and unused.  dropout is accepted and
+    unused: LRURec's dropout sites are not built.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
+    CELL, ENGINE, param_shapes, init_params = "LRU", DeviceLruTracker, lru_param_shapes, init_lru_tracker_params
+
+    def __init__(self, *args, **kw):
+        # d_hid is a keyword of the shared constructor that this tracker reads, as StateTrackerFMLP does: kept for _check_model
+        bound = inspect.signature(_RecurrentStateTracker.__init__).bind(self, *args, **kw)
+        bound.apply_defaults()
+        object.__setattr__(self, "_d_hid", bound.arguments["d_hid"])
+        super().__init__(*args, **kw)
+
+    def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len):
+        check_lru_shape(dim_model, dim_state, nlayers, self._d_hid, max_len)
+        self.d_hid = int(self._d_hid)
+        self.dropout_p, self.nlayers = 0.0, int(nlayers)

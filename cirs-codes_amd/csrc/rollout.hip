@@ -276,6 +276,15 @@ extern "C" int cirs_rollout_collect_fmlp(const cirs_env_cfg* env_cfg, const cirs
                                    traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
 }
 
+extern "C" int cirs_rollout_collect_lru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                                        const cirs_lru_cfg* trk_cfg, const cirs_lru_weights* trk_w, cirs_lru_state* trk_st,
+                                        const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                                        const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                                        int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream) {
+    return cirs::collect_recurrent("lru", cirs_lru_tracker_init, cirs_lru_tracker_step, env_cfg, env_tab, env_st, trk_cfg, trk_w, trk_st, pol_cfg, pol_w,
+                                   traj, n_env, users, seed, rng_base, visited, force_length, greedy, gumbel, workspace, workspace_bytes, stream);
+}
+
 extern "C" int cirs_rollout_steps(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
                                   const cirs_tracker_cfg* trk_cfg, const cirs_tracker_weights* trk_w,
                                   cirs_tracker_state* trk_st, const cirs_policy_cfg* pol_cfg,

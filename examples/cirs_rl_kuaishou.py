@@ -36,7 +36,7 @@ from core.inputs import get_dataset_columns  # noqa: E402
 from torch.utils.tensorboard import SummaryWriter  # noqa: E402
 
 from core.collector import Collector  # noqa: E402
-from core.state_tracker import StateTrackerFMLP, StateTrackerNARM, StateTrackerTransformer  # noqa: E402
+from core.state_tracker import StateTrackerFMLP, StateTrackerLRU, StateTrackerNARM, StateTrackerTransformer  # noqa: E402
 from core.user_model import compute_input_dim  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
 from core.user_model_pairwise import UserModel_Pairwise  # noqa: E402
@@ -87,9 +87,10 @@ def get_args(argv=None):
     p.add_argument("--dim_state", default=20, type=int)
     p.add_argument("--dim_model", default=32, type=int)
     p.add_argument("--nhead", default=4, type=int)
-    p.add_argument("--tracker", choices=["transformer", "narm", "fmlp"], default="transformer",
+    p.add_argument("--tracker", choices=["transformer", "narm", "fmlp", "lru"], default="transformer",
                    help="state tracker: the reference's Transformer, NARM's GRU encoder with attention over its hidden states (StateTrackerNARM), "
-                        "or FMLP-Rec's learnable filter and feed-forward block over the last items (StateTrackerFMLP)")
+                        "FMLP-Rec's learnable filter and feed-forward block over the last items (StateTrackerFMLP), or a linear recurrent unit "
+                        "with that feed-forward block (StateTrackerLRU)")
     p.add_argument("--window-size", type=int, default=10, help="item slots in the window of --tracker fmlp (1..16)")
     p.add_argument("--fmlp-layers", type=int, default=2, help="layers of --tracker fmlp (1 or 2)")
     p.add_argument("--force_length", type=int, default=10)
@@ -213,6 +214,13 @@ def main(args):
                                          has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
                                          nhead=args.nhead, d_hid=128, nlayers=args.fmlp_layers, dropout=0.0, device=device, seed=args.seed,
                                          MAX_TURN=args.max_turn, window_size=args.window_size).to(device)
+    elif args.tracker == "lru":     # the Transformer's keywords; one recurrence layer, and the model's dropout sites are not built
+        state_tracker = StateTrackerLRU(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
+                                        dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),
+                                        dataset=args.env, has_user_embedding=has_user_embedding,
+                                        has_action_embedding=has_action_embedding, has_feedback_embedding=has_feedback_embedding,
+                                        nhead=args.nhead, d_hid=128, nlayers=1, dropout=0.0, device=device, seed=args.seed,
+                                        MAX_TURN=args.max_turn).to(device)
     else:
         state_tracker = StateTrackerTransformer(user_columns, action_columns, feedback_columns, dim_model=args.dim_model,
                                                 dim_state=args.dim_state, dim_max_batch=max(args.training_num, args.test_num),

@@ -25,8 +25,8 @@ from core.collector_set import CollectorSet  # noqa: E402
 from core.trainer.onpolicy import onpolicy_trainer  # noqa: E402
 from core.inputs import get_dataset_columns  # noqa: E402
 from core.policy.ppo import PPOPolicy  # noqa: E402
-from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerFMLP, StateTrackerGRU, StateTrackerLSTM, StateTrackerNARM,  # noqa: E402
-                                StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerTransformer)
+from core.state_tracker import (StateTrackerAvg, StateTrackerCaser, StateTrackerFMLP, StateTrackerGRU, StateTrackerLRU, StateTrackerLSTM,  # noqa: E402
+                                StateTrackerNARM, StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerTransformer)
 from core.user_model import compute_input_dim  # noqa: E402
 from tianshou.data import VectorReplayBuffer  # noqa: E402
 from tianshou.env import DummyVectorEnv  # noqa: E402
@@ -71,12 +71,14 @@ def get_args(argv=None):
                         "dropout site is not built: a positive value is refused)")
     p.add_argument("--deterministic-eval", action="store_true",
                    help="test collectors take the policy's arg-max item instead of a sample (PPOPolicy(deterministic_eval=True))")
-    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp", "narm", "fmlp"], default="transformer",
+    p.add_argument("--tracker", choices=["transformer", "gru", "lstm", "avg", "caser", "nextitnet", "stamp", "narm", "fmlp", "lru"],
+                   default="transformer",
                    help="state tracker: the reference's Transformer, a recurrent one it announces (StateTrackerGRU, StateTrackerLSTM), "
                         "the pooled window over the last items (StateTrackerAvg), Caser's convolutions over that window (StateTrackerCaser), "
                         "NextItNet's dilated causal convolutions over the item slots (StateTrackerNextItNet), STAMP's attention pool over "
-                        "that window (StateTrackerSTAMP), NARM's GRU encoder with attention over its hidden states (StateTrackerNARM), or "
-                        "FMLP-Rec's learnable filter and feed-forward block over that window (StateTrackerFMLP)")
+                        "that window (StateTrackerSTAMP), NARM's GRU encoder with attention over its hidden states (StateTrackerNARM), "
+                        "FMLP-Rec's learnable filter and feed-forward block over that window (StateTrackerFMLP), or a linear recurrent unit with "
+                        "that feed-forward block (StateTrackerLRU)")
     p.add_argument("--gru-layers", type=int, default=1, help="layers of --tracker gru (1 or 2; 2 needs --dropout 0)")
     p.add_argument("--lstm-layers", type=int, default=1, choices=[1, 2], help="layers of --tracker lstm (2 needs --dropout 0)")
     p.add_argument("--window-size", type=int, default=10,
@@ -122,7 +124,7 @@ def build(args, table_seed=0):
                                    "transformer": (StateTrackerTransformer, 2), "avg": (StateTrackerAvg, 1),
                                    "caser": (StateTrackerCaser, 1), "nextitnet": (StateTrackerNextItNet, 1),
                                    "stamp": (StateTrackerSTAMP, 1), "narm": (StateTrackerNARM, 1),
-                                   "fmlp": (StateTrackerFMLP, args.fmlp_layers)}[args.tracker]
+                                   "fmlp": (StateTrackerFMLP, args.fmlp_layers), "lru": (StateTrackerLRU, 1)}[args.tracker]
     tracker_kw = {"avg": {"window_size": args.window_size},
                   "caser": {"window_size": args.window_size, "filter_sizes": args.filter_sizes},
                   "nextitnet": {"dilations": args.dilations}, "stamp": {"window_size": args.window_size},

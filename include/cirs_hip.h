@@ -1286,6 +1286,95 @@ int cirs_rollout_collect_fmlp(const cirs_env_cfg* env_cfg, const cirs_env_tables
                               int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * State tracker, a linear recurrent unit: StateTrackerLRU (csrc/lru_tracker.hip)
+ * The reference has no counterpart; the model is defined here (the diagonal complex recurrence of LRU / S4-style sequence models, as
+ * LRURec, Yue et al., 2023, uses it for sequential recommendation, followed by FMLP's feed-forward block).  All arithmetic is real; a
+ * complex number is a (re, im) pair:
+ *   inputs     the GRU tracker's slots, unchanged: slot 0 = ffn_user(Emb_user[u]), slot k >= 1 = sigmoid(fnn_gate([r_k, a_k])) * a_k
+ *   lambda     = exp(-exp(nu_log)) (cos phi, sin phi), phi = exp(theta_log);  gamma = exp(gamma_log)      (|lambda| < 1 by construction)
+ *   v_p        = W_in x_p + b_in                  (W_in [2D, D]: rows 0..D-1 the real part, D..2D-1 the imaginary part)
+ *   h_p        = lambda * h_{p-1} + gamma * v_p, h_{-1} = 0     (the complex product per feature d; gamma scales both parts of feature d):
+ *                  h_re' = lr h_re - li h_im + gamma v_re      h_im' = lr h_im + li h_re + gamma v_im
+ *   y_p        = W_out [h_re ; h_im] + b_out      (W_out [D, 2D]: the real part of a complex read-out)
+ *   z_p        = LayerNorm(y_p + x_p)             (lru.ln, eps 1e-5)
+ *   m_p        = LayerNorm(z_p + W2 gelu(W1 z_p + b1) + b2)     (D -> 128 -> D, the exact (erf) GELU, ffn.ln);  s_p = decoder(m_p)
+ * Position 0 (the user slot) is the first input of the recurrence.  An env carries 2 D floats whatever its position.
+ * Fixed dims of this build: dim_model == 32, dim_state <= 32, ONE layer (the cfg keeps the GRU tracker's `nlayers` member so that the two
+ * cfgs have one layout; any value but 1 is refused), hidden width 128, max_len <= 4096.  LRURec's dropout sites are not built.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CIRS_LRU_MAX_LAYERS 1
+#define CIRS_LRU_HIDDEN 128
+
+typedef struct cirs_lru_cfg {
+    int32_t n_users, n_items;
+    int32_t dim_model; /* D = 32 */
+    int32_t dim_state; /* S <= 32 */
+    int32_t nlayers;   /* 1 */
+    int32_t max_len;   /* MAX_TURN + 1 */
+    int32_t n_env;     /* B: leading dimension of the state arrays */
+} cirs_lru_cfg;
+
+typedef struct cirs_lru_weights {
+    const float* emb_user;                /* embedding_dict.feat_user.weight [U,D] */
+    const float* emb_item;                /* embedding_dict.feat_item.weight [I,D] */
+    const float *ffn_user_w, *ffn_user_b; /* [D,D], [D] */
+    const float *gate_w, *gate_b;         /* fnn_gate [D,1+D] (input order [r, a]), [D] */
+    const float *nu_log, *theta_log, *gamma_log; /* lru.nu_log, lru.theta_log, lru.gamma_log [D] */
+    const float *in_w, *in_b;             /* lru.in_proj [2D,D] (rows: real part | imaginary part), [2D] */
+    const float *out_w, *out_b;           /* lru.out_proj [D,2D] (columns: real part | imaginary part), [D] */
+    const float *lln_w, *lln_b;           /* lru.ln [D], [D] */
+    const float *d1_w, *d1_b;             /* ffn.dense_1 [128,D], [128] */
+    const float *d2_w, *d2_b;             /* ffn.dense_2 [D,128], [D] */
+    const float *ln_w, *ln_b;             /* ffn.ln [D], [D] */
+    const float *dec_w, *dec_b;           /* decoder [S,D], [S] */
+} cirs_lru_weights;
+
+typedef struct cirs_lru_state {
+    float* x_hist; /* [B, max_len, D] the input slots (what the backward recomputes from) */
+    float* h_re;   /* [1, B, D] the carried state, real part */
+    float* h_im;   /* [1, B, D] the carried state, imaginary part */
+    int32_t* len;  /* [B] positions appended so far */
+} cirs_lru_state;
+
+typedef struct cirs_lru_grads { /* same tensors, same order as cirs_lru_weights */
+    float *emb_user, *emb_item, *ffn_user_w, *ffn_user_b, *gate_w, *gate_b;
+    float *nu_log, *theta_log, *gamma_log, *in_w, *in_b, *out_w, *out_b, *lln_w, *lln_b;
+    float *d1_w, *d1_b, *d2_w, *d2_b, *ln_w, *ln_b;
+    float *dec_w, *dec_b;
+} cirs_lru_grads;
+
+/* cirs_gru_tracker_init / cirs_gru_tracker_step for the LRU tracker, same argument conventions: env_ids (nullable, [n]) = the env of row j
+ * (NULL: j); init writes slot 0, h_0 = gamma * v_0, len = 1; step appends one position.  Rows with skip != 0 (step), an env / user / item id
+ * out of range (item < 0: the env finished), a never-initialised or a full history are left untouched: neither the tracker state nor their
+ * row of state_out is written.  state_out row stride = state_stride floats.  A cfg outside the fixed sizes is refused (CIRS_E_INVALID /
+ * CIRS_E_UNSUPPORTED) with a message prefixed "lru tracker:", before any pointer is read. */
+int cirs_lru_tracker_init(const cirs_lru_cfg* cfg, const cirs_lru_weights* w, cirs_lru_state* st, const int32_t* users,
+                          const int32_t* env_ids, int32_t n, float* state_out, int64_t state_stride, void* stream);
+int cirs_lru_tracker_step(const cirs_lru_cfg* cfg, const cirs_lru_weights* w, cirs_lru_state* st, const int64_t* items,
+                          const double* rew, const int32_t* env_ids, const uint8_t* skip, int32_t n, float* state_out,
+                          int64_t state_stride, void* stream);
+
+/* cirs_gru_tracker_backward for the LRU tracker: recomputed from the stored slots; every dense product runs over all buffer rows at once,
+ * the only sequential work is one complex multiply-add per position in the forward scan and in its adjoint (one env per wavefront).  Same
+ * arguments as cirs_gru_tracker_backward; of st only x_hist is read.  The workspace is O(n_rows) + O(n_env) and does not depend on max_len.
+ * Every gradient tensor is OVERWRITTEN.  No float atomics; every reduction has a fixed order, so two calls give the same bits.  A workspace
+ * smaller than cirs_lru_tracker_backward_workspace_bytes(cfg, n_rows) (0 for a cfg that is refused), or one not 16-byte aligned, is refused
+ * before any launch. */
+int64_t cirs_lru_tracker_backward_workspace_bytes(const cirs_lru_cfg* cfg, int32_t n_rows);
+int cirs_lru_tracker_backward(const cirs_lru_cfg* cfg, const cirs_lru_weights* w, const cirs_lru_state* st, const int32_t* users,
+                              const int64_t* act, const double* rew, const int32_t* row_env, const int32_t* row_t,
+                              const int32_t* offsets, const int32_t* lens, int32_t n_rows, const float* dstate,
+                              const cirs_lru_grads* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* cirs_rollout_collect_gru with an LRU tracker: the same launch sequence (one loop serves the nine, csrc/rollout.hip) with
+ * cirs_lru_tracker_init / cirs_lru_tracker_step, the same arguments and the same trajectory contract. */
+int cirs_rollout_collect_lru(const cirs_env_cfg* env_cfg, const cirs_env_tables* env_tab, cirs_env_state* env_st,
+                             const cirs_lru_cfg* trk_cfg, const cirs_lru_weights* trk_w, cirs_lru_state* trk_st,
+                             const cirs_policy_cfg* pol_cfg, const cirs_policy_weights* pol_w, const cirs_traj* traj, int32_t n_env,
+                             const int32_t* users, uint64_t seed, uint32_t rng_base, uint32_t* visited, int32_t force_length,
+                             int32_t greedy, const float* gumbel, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * DeepFM user model (UserModel_Pairwise) and the full-catalogue sweep
  * replaces  core/user_model_pairwise.py:98-154 (_deepfm/forward), core/user_model.py:419-447 (input_from_feature_columns),
  *           core/layers.py:43-72 (Linear), DeepCTR-Torch deepctr_torch/layers/interaction.py:26-34 (FM),

@@ -1,15 +1,15 @@
 """The recurrent state trackers (GRU, LSTM), the pooled-window one (Avg), the convolutional one (Caser), the dilated-convolution one (NextItNet), the
-attention-pool one (STAMP), the GRU encoder with attention over its hidden states (NARM) and the filter-MLP one (FMLP) against the Transformer one at
-the benchmark shapes:
+attention-pool one (STAMP), the GRU encoder with attention over its hidden states (NARM), the filter-MLP one (FMLP) and the linear-recurrence one
+(LRU) against the Transformer one at the benchmark shapes:
     python tools/probe_gru_tracker.py [--workload c2|c3] [--reps 60]
 
-Twelve trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
+Thirteen trackers over the same env, policy and learner (bench.py's engine at dropout 0): the Transformer (2 layers), the GRU and the LSTM with 1 and
 with 2 layers, the Avg tracker with a window of 3 and of 10, the Caser tracker with a window of 10 and heights (2, 3, 4),
 the NextItNet tracker with dilations (1, 2, 4), the STAMP tracker with a window of 10, the NARM tracker (one encoder layer, attention over the whole
-session), the FMLP tracker with a window of 10 and 2 layers.  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
+session), the FMLP tracker with a window of 10 and 2 layers, the LRU tracker (one linear recurrent unit).  Per tracker, alternated inside every repetition so that drift of the machine hits all alike:
   step_us        one tracker step alone (one launch, all envs) at positions 1, 15 and 30 -- a device-event pair around the launch
   collect_ms     one DeviceRollout.collect (what Collector.collect runs on the device): the fused two-launch sequence for the Transformer,
-                 cirs_rollout_collect_gru's / _lstm's / _avg's / _caser's / _nextitnet's / _stamp's / _narm's / _fmlp's unfused sequence for the others -- device events around the call, enqueued behind a spin kernel (the host
+                 cirs_rollout_collect_gru's / _lstm's / _avg's / _caser's / _nextitnet's / _stamp's / _narm's / _fmlp's / _lru's unfused sequence for the others -- device events around the call, enqueued behind a spin kernel (the host
                  ahead of the device, as in the training loop); collect_idle_ms: the same from an idle stream (the host's launch rate counts)
   bwd_adam_ms    the tracker backward + Adam step of one update (the learner's d loss / d obs as upstream gradient) -- device events
 Medians over --reps repetitions after a warm-up, min and max alongside; lstm_over_gru: the ratios of those medians per layer count;
@@ -18,7 +18,9 @@ the same window (the two step kernels share everything except the window arithme
 over the one-layer GRU's; stamp_over: the STAMP tracker's over the Avg tracker's and over the Caser tracker's at the same window (the yardsticks on either
 side of it); narm_over: the NARM tracker's over the one-layer GRU's (its encoder alone) and over the STAMP tracker's, with the step at positions 1, 15
 and 30 (its attention term grows with the position); fmlp_over: the FMLP tracker's over the NextItNet, the Caser and the Transformer tracker's (the
-other dense-tile trackers and the model it is the ablation partner of), with the step at positions 1, 15 and 30.  One JSON line.
+other dense-tile trackers and the model it is the ablation partner of), with the step at positions 1, 15 and 30; lru_over: the LRU tracker's over
+the one-layer GRU's, the NARM and the Transformer tracker's (the carried-state trackers and the model whose KV cache it does without), with the step at
+positions 1, 15 and 30 (its step should not depend on the position).  One JSON line.
 --trace: no timing, a few collects and backwards per tracker -- the run to put under `rocprofv3 --kernel-trace --stats -- python ...` for kernel times
 (tracing slows the host: never in the same run as the timings above)."""
 import argparse
@@ -36,6 +38,7 @@ from cirs_hip.avg_tracker import DeviceAvgTracker, avg_param_shapes, init_avg_tr
 from cirs_hip.caser_tracker import DeviceCaserTracker, caser_param_shapes, init_caser_tracker_params  # noqa: E402
 from cirs_hip.fmlp_tracker import DeviceFmlpTracker, fmlp_param_shapes, init_fmlp_tracker_params  # noqa: E402
 from cirs_hip.gru_tracker import DeviceGruTracker, gru_param_shapes, init_gru_tracker_params  # noqa: E402
+from cirs_hip.lru_tracker import DeviceLruTracker, init_lru_tracker_params, lru_param_shapes  # noqa: E402
 from cirs_hip.lstm_tracker import DeviceLstmTracker, init_lstm_tracker_params, lstm_param_shapes  # noqa: E402
 from cirs_hip.narm_tracker import DeviceNarmTracker, init_narm_tracker_params, narm_param_shapes  # noqa: E402
 from cirs_hip.nextitnet_tracker import DeviceNextItNetTracker, init_nextitnet_tracker_params, nextitnet_param_shapes  # noqa: E402
@@ -107,6 +110,14 @@ def fmlp_engine(wl, window, layers, device):
     return trk
 
 
+def lru_engine(wl, device):
+    U, I, B, T = wl["U"], wl["I"], wl["B"], wl["T"]
+    flat, views = flat_tracker_params(lru_param_shapes(U, I, 32, 20), device=device, init=init_lru_tracker_params(U, I, seed=2023))
+    trk = DeviceLruTracker(dict(views), U, I, B, T, device=device)
+    trk.enable_training(flat)
+    return trk
+
+
 def stats(xs):
     xs = np.asarray(xs, dtype=np.float64)
     return {"median": round(float(np.median(xs)), 3), "min": round(float(xs.min()), 3), "max": round(float(xs.max()), 3)}
@@ -157,6 +168,8 @@ def main():
     variants["narm"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
     trk = fmlp_engine(wl, 10, 2, device)
     variants["fmlp_w10_l2"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
+    trk = lru_engine(wl, device)
+    variants["lru"] = (trk, DeviceRollout(eng.env, trk, eng.policy))
     users = torch.as_tensor(np.random.RandomState(0).randint(0, U, B)).to(device, torch.int32)
     items = torch.as_tensor(np.random.RandomState(1).randint(0, I, B)).to(device)
     rews = torch.rand(B, dtype=torch.float64, device=device)
@@ -248,6 +261,11 @@ def main():
                                "collect_ms": round(med("fmlp_w10_l2", "collect_ms") / med(base, "collect_ms"), 3),
                                "bwd_adam_ms": round(med("fmlp_w10_l2", "bwd_adam_ms") / med(base, "bwd_adam_ms"), 3)}
                         for base in ("nextitnet_d124", "caser_w10", "transformer_l2")}
+    out["lru_over"] = {base: {**{f"step_us_{p}": round(out["trackers"]["lru"]["step_us"][str(p)]["median"] / out["trackers"][base]["step_us"][str(p)]["median"], 3)
+                                 for p in (1, 15, 30)},
+                              "collect_ms": round(med("lru", "collect_ms") / med(base, "collect_ms"), 3),
+                              "bwd_adam_ms": round(med("lru", "bwd_adam_ms") / med(base, "bwd_adam_ms"), 3)}
+                       for base in ("gru_l1", "narm", "transformer_l2")}
     print(json.dumps(out), flush=True)
 
 
