@@ -1,17 +1,16 @@
 """Device engine of the convolutional window state tracker (csrc/caser_tracker.hip): the input slots of the other trackers, the window of the
 last `window_size` item slots through Caser's horizontal filter banks (max-pooled over time) and its vertical filter, one fc layer, h_p = x_0 +
 z, the same decoder.  One launch per step and nothing carried besides the stored slots; the gradient arrives through
-cirs_caser_tracker_backward (no sequential pass).  The engine itself is gru_tracker.DeviceRecurrentTracker with the Caser structs and entry
+cirs_caser_tracker_backward (no sequential pass).  The engine itself is slot_engine.DeviceSlotTracker with the Caser structs and entry
 points, so the rollout, the learner and the plugin classes drive it as they drive the GRU's."""
 from typing import Dict
 
 import torch
 
 from . import abi
-from .gru_tracker import TOP_FIELDS, DeviceRecurrentTracker
+from .slot_engine import (DeviceSlotTracker, add_module_params, check_dims, check_max_len, decoder_shapes, head_shapes, own_stream,
+                          shared_init_params)
 
-DIM_MODEL = 32
-MAX_LEN = 4096
 NUM_FILTERS = 16
 MAX_WINDOW = 16
 MAX_HEIGHT = 4
@@ -19,10 +18,7 @@ MAX_HEIGHT = 4
 
 def check_caser_shape(dim_model, dim_state, window_size, filter_sizes, num_filters=NUM_FILTERS, max_len=None):
     """The fixed sizes of this build (include/cirs_hip.h); raises before any device use."""
-    if int(dim_model) != DIM_MODEL:
-        raise ValueError(f"the Caser tracker is built for dim_model == {DIM_MODEL}, got {dim_model}")
-    if not 1 <= int(dim_state) <= 32:
-        raise ValueError(f"the Caser tracker is built for dim_state in 1..32, got {dim_state}")
+    check_dims("Caser", dim_model, dim_state)
     if int(num_filters) != NUM_FILTERS:
         raise ValueError(f"the Caser tracker is built for num_filters == {NUM_FILTERS}, got {num_filters}")
     hs = [int(h) for h in filter_sizes]
@@ -31,20 +27,18 @@ def check_caser_shape(dim_model, dim_state, window_size, filter_sizes, num_filte
     if not hs[-1] <= int(window_size) <= MAX_WINDOW:
         raise ValueError(f"the Caser tracker is built for window_size in max(filter_sizes)..{MAX_WINDOW}, got window_size {window_size} with "
                          f"filter_sizes {tuple(hs)}")
-    if max_len is not None and not 1 <= int(max_len) <= MAX_LEN:
-        raise ValueError(f"the Caser tracker is built for max_len (MAX_TURN + 1) in 1..{MAX_LEN}, got {max_len}")
+    check_max_len("Caser", max_len)
 
 
 def caser_param_shapes(n_users, n_items, dim_model=32, dim_state=20, window_size=10, filter_sizes=(2, 3, 4), num_filters=NUM_FILTERS):
     """Ordered {state_dict name: shape} of the trainable tensors: the other trackers' names for what all share, then the filter banks, the
     vertical filter and fc under names that load into nn.Conv2d(1, F, (h, D)) / nn.Conv2d(1, 1, (W, 1)) / nn.Linear by name, decoder last."""
-    D, S, F = dim_model, dim_state, num_filters
-    sh = {"embedding_dict.feat_user.weight": (n_users, D), "embedding_dict.feat_item.weight": (n_items, D),
-          "ffn_user.weight": (D, D), "ffn_user.bias": (D,), "fnn_gate.weight": (D, D + 1), "fnn_gate.bias": (D,)}
+    D, F = dim_model, num_filters
+    sh = head_shapes(n_users, n_items, D)
     for i, h in enumerate(filter_sizes):
         sh.update({f"horizontal_cnn.{i}.weight": (F, 1, int(h), D), f"horizontal_cnn.{i}.bias": (F,)})
     sh.update({"vertical_cnn.weight": (1, 1, int(window_size), 1), "vertical_cnn.bias": (1,),
-               "fc.weight": (D, F * len(filter_sizes) + D), "fc.bias": (D,), "decoder.weight": (S, D), "decoder.bias": (S,)})
+               "fc.weight": (D, F * len(filter_sizes) + D), "fc.bias": (D,), **decoder_shapes(D, dim_state)})
     return sh
 
 
@@ -52,52 +46,35 @@ def init_caser_tracker_params(n_users, n_items, seed=2021, dim_model=32, dim_sta
                               num_filters=NUM_FILTERS, init_std=1e-4) -> Dict[str, torch.Tensor]:
     """Fresh parameters: what all trackers share exactly as engine.init_tracker_params draws it (same seed -> same tensors), the filters and fc
     with torch's default init from a generator stream of their own.  torch modules are parameter factories only."""
-    from .engine import init_tracker_params
-    shared = init_tracker_params(n_users, n_items, 1, seed=seed, dim_model=dim_model, dim_state=dim_state, nlayers=1, init_std=init_std)
-    shapes = caser_param_shapes(n_users, n_items, dim_model, dim_state, window_size, filter_sizes, num_filters)
-    p = {k: shared[k] for k in shapes if k in shared}
-    torch_state = torch.random.get_rng_state()
-    torch.manual_seed(int(seed) + 0x63617372)      # a stream of its own: the shared tensors do not move with the window or the banks
-    try:
+    p = shared_init_params(n_users, n_items, seed, dim_model, dim_state, init_std)
+    with own_stream(int(seed) + 0x63617372):      # the shared tensors do not move with the window or the banks
         mods = {f"horizontal_cnn.{i}": torch.nn.Conv2d(1, num_filters, (int(h), dim_model)) for i, h in enumerate(filter_sizes)}
         mods["vertical_cnn"] = torch.nn.Conv2d(1, 1, (int(window_size), 1))
         mods["fc"] = torch.nn.Linear(num_filters * len(filter_sizes) + dim_model, dim_model)
-        for name, m in mods.items():
-            for k, v in m.state_dict().items():
-                p[f"{name}.{k}"] = v.detach().clone().float()
-    finally:
-        torch.random.set_rng_state(torch_state)
-    return {k: p[k] for k in shapes}
+        add_module_params(p, mods)
+    return {k: p[k] for k in caser_param_shapes(n_users, n_items, dim_model, dim_state, window_size, filter_sizes, num_filters)}
 
 
-class DeviceCaserTracker(DeviceRecurrentTracker):
+class DeviceCaserTracker(DeviceSlotTracker):
     """`params` maps state_dict names (caser_param_shapes) to device tensors.  Carries nothing: the window is read from x_hist."""
-    CFG, WEIGHTS, STATE, LAYER_FIELDS, ENTRY = abi.CaserCfg, abi.CaserWeights, abi.CaserState, (), "cirs_caser_tracker"
+    CFG, WEIGHTS, STATE, ENTRY, param_shapes = abi.CaserCfg, abi.CaserWeights, abi.CaserState, "cirs_caser_tracker", caser_param_shapes
+    FIELDS = [("conv_w[]", "horizontal_cnn.{}.weight"), ("conv_b[]", "horizontal_cnn.{}.bias"), ("vert_w", "vertical_cnn.weight"),
+              ("vert_b", "vertical_cnn.bias"), ("fc_w", "fc.weight"), ("fc_b", "fc.bias")]
     CARRY = ()
     COLLECT, NAME = "cirs_rollout_collect_caser", "Caser"
 
     def __init__(self, params: Dict[str, torch.Tensor], n_users, n_items, n_env, max_turn, *, dim_model=32, dim_state=20, window_size=10,
                  filter_sizes=(2, 3, 4), num_filters=NUM_FILTERS, device="cuda"):
         self.window_size, self.filter_sizes, self.num_filters = int(window_size), tuple(int(h) for h in filter_sizes), int(num_filters)
-        self._max_len = max_turn + 1
         super().__init__(params, n_users, n_items, n_env, max_turn, dim_model=dim_model, dim_state=dim_state, nlayers=0, device=device)
 
     def _cell_cfg(self, dim_model, dim_state, nlayers):
-        check_caser_shape(dim_model, dim_state, self.window_size, self.filter_sizes, self.num_filters, self._max_len)
+        check_caser_shape(dim_model, dim_state, self.window_size, self.filter_sizes, self.num_filters, self.max_len)
         hs = self.filter_sizes + (0,) * (abi.CASER_MAX_HEIGHTS - len(self.filter_sizes))
         return {"window": self.window_size, "n_heights": len(self.filter_sizes), "heights": (abi.C.c_int32 * abi.CASER_MAX_HEIGHTS)(*hs)}
 
-    def _weights(self, tensors):
-        """cirs_caser_weights (or cirs_caser_grads: same layout): weights_struct knows the shared fields and per-layer cells only."""
-        w = self.WEIGHTS()
+    def _shape_kw(self):
+        return {"window_size": self.window_size, "filter_sizes": self.filter_sizes, "num_filters": self.num_filters}
 
-        def ptr(name):
-            t = tensors[name]
-            assert t.dtype == torch.float32 and t.is_contiguous(), name
-            return t.data_ptr()
-        for f, name in TOP_FIELDS:
-            setattr(w, f, ptr(name))
-        for i in range(len(self.filter_sizes)):
-            w.conv_w[i], w.conv_b[i] = ptr(f"horizontal_cnn.{i}.weight"), ptr(f"horizontal_cnn.{i}.bias")
-        w.vert_w, w.vert_b, w.fc_w, w.fc_b = ptr("vertical_cnn.weight"), ptr("vertical_cnn.bias"), ptr("fc.weight"), ptr("fc.bias")
-        return w
+    def _live(self):
+        return len(self.filter_sizes)

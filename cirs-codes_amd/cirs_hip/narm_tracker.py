@@ -3,33 +3,24 @@ carried as 32 floats per env, NARM's additive attention over every hidden state 
 bilinear read-out m_p = Bw [h_p ; c_p], the same decoder.  One launch per step; besides h an env keeps its hidden states and their A2
 projections (h_hist, q_hist: [n_env, max_len, 32] each), so a step costs O(position).  The gradient arrives through cirs_narm_tracker_backward
 (the attention's backward in parallel over the rows, fed into the GRU's sequential back-propagation through time).  The engine itself is
-gru_tracker.DeviceRecurrentTracker with the NARM structs and entry points, so the rollout, the learner and the plugin classes drive it as they
+slot_engine.DeviceSlotTracker with the NARM structs and entry points, so the rollout, the learner and the plugin classes drive it as they
 drive the GRU's."""
 from typing import Dict
 
 import torch
 
 from . import abi
-from .gru_tracker import TOP_FIELDS, DeviceRecurrentTracker
+from .slot_engine import DeviceSlotTracker, add_module_params, check_dims, check_max_len, decoder_shapes, head_shapes, own_stream
 
-DIM_MODEL = 32
-MAX_LEN = 4096
 MAX_LAYERS = abi.NARM_MAX_LAYERS
-# the struct members of the eight tensors between the shared ones and the decoder, and their state_dict names
-NARM_FIELDS = [("w_ih", "gru.weight_ih_l0"), ("w_hh", "gru.weight_hh_l0"), ("b_ih", "gru.bias_ih_l0"), ("b_hh", "gru.bias_hh_l0"),
-               ("a1", "attn.a1.weight"), ("a2", "attn.a2.weight"), ("v", "attn.v.weight"), ("bw", "bilinear.weight")]
 
 
 def check_narm_shape(dim_model, dim_state, nlayers=1, max_len=None):
     """The fixed sizes of this build (include/cirs_hip.h); raises before any device use."""
-    if int(dim_model) != DIM_MODEL:
-        raise ValueError(f"the NARM tracker is built for dim_model == {DIM_MODEL}, got {dim_model}")
-    if not 1 <= int(dim_state) <= 32:
-        raise ValueError(f"the NARM tracker is built for dim_state in 1..32, got {dim_state}")
+    check_dims("NARM", dim_model, dim_state)
     if int(nlayers) != MAX_LAYERS:
         raise ValueError(f"the NARM tracker is built for nlayers == {MAX_LAYERS} (one encoder layer), got {nlayers}")
-    if max_len is not None and not 1 <= int(max_len) <= MAX_LEN:
-        raise ValueError(f"the NARM tracker is built for max_len (MAX_TURN + 1) in 1..{MAX_LEN}, got {max_len}")
+    check_max_len("NARM", max_len)
 
 
 def narm_param_shapes(n_users, n_items, dim_model=32, dim_state=20, nlayers=1):
@@ -37,12 +28,11 @@ def narm_param_shapes(n_users, n_items, dim_model=32, dim_state=20, nlayers=1):
     for the encoder, so that they load into nn.GRU(dim_model, dim_model, 1) by name, then the attention (nn.Linear(D, D, bias=False) under
     attn.a1 / attn.a2, nn.Linear(D, 1, bias=False) under attn.v) and the read-out (nn.Linear(2 D, D, bias=False) under bilinear), decoder
     last."""
-    D, S = dim_model, dim_state
-    return {"embedding_dict.feat_user.weight": (n_users, D), "embedding_dict.feat_item.weight": (n_items, D),
-            "ffn_user.weight": (D, D), "ffn_user.bias": (D,), "fnn_gate.weight": (D, D + 1), "fnn_gate.bias": (D,),
+    D = dim_model
+    return {**head_shapes(n_users, n_items, D),
             "gru.weight_ih_l0": (3 * D, D), "gru.weight_hh_l0": (3 * D, D), "gru.bias_ih_l0": (3 * D,), "gru.bias_hh_l0": (3 * D,),
             "attn.a1.weight": (D, D), "attn.a2.weight": (D, D), "attn.v.weight": (1, D), "bilinear.weight": (D, 2 * D),
-            "decoder.weight": (S, D), "decoder.bias": (S,)}
+            **decoder_shapes(D, dim_state)}
 
 
 def init_narm_tracker_params(n_users, n_items, seed=2021, dim_model=32, dim_state=20, nlayers=1, init_std=1e-4) -> Dict[str, torch.Tensor]:
@@ -52,41 +42,23 @@ def init_narm_tracker_params(n_users, n_items, seed=2021, dim_model=32, dim_stat
     from .gru_tracker import init_gru_tracker_params
     p = init_gru_tracker_params(n_users, n_items, seed=seed, dim_model=dim_model, dim_state=dim_state, nlayers=1, init_std=init_std)
     D = dim_model
-    torch_state = torch.random.get_rng_state()
-    torch.manual_seed(int(seed) + 0x6E61726D)      # a stream of its own: nothing shared moves with the attention
-    try:
-        mods = {"attn.a1": torch.nn.Linear(D, D, bias=False), "attn.a2": torch.nn.Linear(D, D, bias=False),
-                "attn.v": torch.nn.Linear(D, 1, bias=False), "bilinear": torch.nn.Linear(2 * D, D, bias=False)}
-        for name, m in mods.items():
-            p[f"{name}.weight"] = m.weight.detach().clone().float()
-    finally:
-        torch.random.set_rng_state(torch_state)
+    with own_stream(int(seed) + 0x6E61726D):      # nothing shared moves with the attention
+        add_module_params(p, {"attn.a1": torch.nn.Linear(D, D, bias=False), "attn.a2": torch.nn.Linear(D, D, bias=False),
+                              "attn.v": torch.nn.Linear(D, 1, bias=False), "bilinear": torch.nn.Linear(2 * D, D, bias=False)})
     return {k: p[k] for k in narm_param_shapes(n_users, n_items, dim_model, dim_state)}
 
 
-class DeviceNarmTracker(DeviceRecurrentTracker):
+class DeviceNarmTracker(DeviceSlotTracker):
     """`params` maps state_dict names (narm_param_shapes) to device tensors.  Carries h; keeps h_hist and q_hist next to x_hist."""
-    CFG, WEIGHTS, STATE, LAYER_FIELDS, ENTRY, check_shape = abi.NarmCfg, abi.NarmWeights, abi.NarmState, (), "cirs_narm_tracker", check_narm_shape
+    CFG, WEIGHTS, STATE, ENTRY, check_shape, param_shapes = abi.NarmCfg, abi.NarmWeights, abi.NarmState, "cirs_narm_tracker", check_narm_shape, narm_param_shapes
+    FIELDS = [("w_ih", "gru.weight_ih_l0"), ("w_hh", "gru.weight_hh_l0"), ("b_ih", "gru.bias_ih_l0"), ("b_hh", "gru.bias_hh_l0"),
+              ("a1", "attn.a1.weight"), ("a2", "attn.a2.weight"), ("v", "attn.v.weight"), ("bw", "bilinear.weight")]
     CARRY = ("h",)
     COLLECT, NAME = "cirs_rollout_collect_narm", "NARM"
 
-    def __init__(self, params: Dict[str, torch.Tensor], n_users, n_items, n_env, max_turn, *, dim_model=32, dim_state=20, nlayers=1,
-                 device="cuda"):
-        self._max_len = max_turn + 1
-        super().__init__(params, n_users, n_items, n_env, max_turn, dim_model=dim_model, dim_state=dim_state, nlayers=nlayers, device=device)
-
     def _cell_cfg(self, dim_model, dim_state, nlayers):
-        check_narm_shape(dim_model, dim_state, nlayers, self._max_len)
+        check_narm_shape(dim_model, dim_state, nlayers, self.max_len)
         return {"nlayers": nlayers}
-
-    def _weights(self, tensors):
-        """cirs_narm_weights (or cirs_narm_grads: same layout): weights_struct knows the shared fields and per-layer cells only."""
-        w = self.WEIGHTS()
-        for f, name in TOP_FIELDS + NARM_FIELDS:
-            t = tensors[name]
-            assert t.dtype == torch.float32 and t.is_contiguous(), name
-            setattr(w, f, t.data_ptr())
-        return w
 
     def _state(self, x_hist):
         """The engine's own histories go with every x_hist: the backward over a buffer with another env count reads x_hist only."""

@@ -13,7 +13,7 @@ import torch
 from . import abi
 from .env import DeviceEnv
 from .policy import DevicePolicy
-from .gru_tracker import DeviceRecurrentTracker
+from .slot_engine import DeviceSlotTracker
 from .tracker import DeviceTracker
 
 
@@ -74,7 +74,7 @@ class DeviceRollout:
         assert env.n_env == tracker.cfg.n_env
         self.env, self.tracker, self.policy = env, tracker, policy
         # a recurrent tracker has a collect of its own (cirs_rollout_collect_gru / _lstm: the unfused launch sequence)
-        self.gru = isinstance(tracker, DeviceRecurrentTracker)
+        self.gru = isinstance(tracker, DeviceSlotTracker)
         if self.gru and online is not None:
             raise NotImplementedError(f"the online-reward rollout is not built for the {tracker.NAME} tracker (out of scope: precompute the reward table)")
         self.device = env.device

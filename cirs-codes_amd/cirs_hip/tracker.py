@@ -6,15 +6,13 @@ from typing import Dict, Optional
 import torch
 
 from . import abi
+from .slot_engine import TOP_FIELDS, decoder_shapes, head_shapes
 
 LAYER_FIELDS = [("in_proj_w", "self_attn.in_proj_weight"), ("in_proj_b", "self_attn.in_proj_bias"),
                 ("out_proj_w", "self_attn.out_proj.weight"), ("out_proj_b", "self_attn.out_proj.bias"),
                 ("lin1_w", "linear1.weight"), ("lin1_b", "linear1.bias"), ("lin2_w", "linear2.weight"),
                 ("lin2_b", "linear2.bias"), ("norm1_w", "norm1.weight"), ("norm1_b", "norm1.bias"),
                 ("norm2_w", "norm2.weight"), ("norm2_b", "norm2.bias")]
-TOP_FIELDS = [("emb_user", "embedding_dict.feat_user.weight"), ("emb_item", "embedding_dict.feat_item.weight"),
-              ("ffn_user_w", "ffn_user.weight"), ("ffn_user_b", "ffn_user.bias"), ("gate_w", "fnn_gate.weight"),
-              ("gate_b", "fnn_gate.bias"), ("dec_w", "decoder.weight"), ("dec_b", "decoder.bias")]
 
 
 def positional_encoding(max_len: int, d_model: int) -> torch.Tensor:
@@ -45,9 +43,8 @@ def weights_struct(params: Dict[str, torch.Tensor], pe: torch.Tensor, nlayers: i
 
 def tracker_param_shapes(n_users, n_items, dim_model=32, dim_state=20, d_hid=128, nlayers=2):
     """Ordered {reference state_dict name: shape} of the trainable tracker tensors."""
-    D, S, H = dim_model, dim_state, d_hid
-    sh = {"embedding_dict.feat_user.weight": (n_users, D), "embedding_dict.feat_item.weight": (n_items, D),
-          "ffn_user.weight": (D, D), "ffn_user.bias": (D,), "fnn_gate.weight": (D, D + 1), "fnn_gate.bias": (D,)}
+    D, H = dim_model, d_hid
+    sh = head_shapes(n_users, n_items, D)
     for l in range(nlayers):
         pre = f"transformer_encoder.layers.{l}."
         sh.update({pre + "self_attn.in_proj_weight": (3 * D, D), pre + "self_attn.in_proj_bias": (3 * D,),
@@ -55,7 +52,7 @@ def tracker_param_shapes(n_users, n_items, dim_model=32, dim_state=20, d_hid=128
                    pre + "linear1.weight": (H, D), pre + "linear1.bias": (H,), pre + "linear2.weight": (D, H),
                    pre + "linear2.bias": (D,), pre + "norm1.weight": (D,), pre + "norm1.bias": (D,),
                    pre + "norm2.weight": (D,), pre + "norm2.bias": (D,)})
-    sh.update({"decoder.weight": (S, D), "decoder.bias": (S,)})
+    sh.update(decoder_shapes(D, dim_state))
     return sh
 
 

@@ -16,8 +16,6 @@ gradient arrives through cirs_tracker_backward /
 cirs_gru_tracker_backward / cirs_lstm_tracker_backward / cirs_avg_tracker_backward / cirs_caser_tracker_backward /
 cirs_nextitnet_tracker_backward / cirs_stamp_tracker_backward / cirs_narm_tracker_backward / cirs_fmlp_tracker_backward /
 cirs_lru_tracker_backward (no autograd graph)."""
-import inspect
-
 import numpy as np
 import torch
 from torch import nn
@@ -172,11 +170,12 @@ class StateTrackerTransformer(_DeviceStateTracker):
 
 
 class _RecurrentStateTracker(_DeviceStateTracker):
-    """What StateTrackerGRU, StateTrackerLSTM, StateTrackerAvg, StateTrackerCaser, StateTrackerNextItNet, StateTrackerSTAMP, StateTrackerNARM, StateTrackerFMLP and StateTrackerLRU share: StateTrackerTransformer's constructor keywords (a
-    script changes the class name only; nhead and d_hid are accepted and unused) plus the subclass's own (the keywords of its _check_model,
-    with their defaults), the refusals, the engine.  A subclass names itself (CELL), its device engine and the functions of its cirs_hip
-    module; one whose model is not "nlayers cells" says in _check_model and _model_kw what it is instead.  dropout: torch applies it between the layers only -- without
-    effect at nlayers == 1 (as in torch); at nlayers == 2 it is not built and training mode with dropout > 0 raises."""
+    """What the plugin classes of the slot trackers (every subclass below) share: StateTrackerTransformer's constructor keywords (a script
+    changes the class name only; nhead is accepted and unused, d_hid is kept as an attribute for the _check_model that reads it) plus the
+    subclass's own (the keywords of its _check_model, with their defaults), the refusals, the engine.  A subclass names itself (CELL), its
+    device engine and the functions of its cirs_hip module; one whose model is not "nlayers cells" says in _check_model and _model_kw what
+    it is instead.  dropout: torch applies it between the layers only -- without effect at nlayers == 1 (as in torch); at nlayers == 2 it
+    is not built and training mode with dropout > 0 raises."""
     CELL = ENGINE = check_shape = param_shapes = init_params = None
 
     def __init__(self, user_columns, action_columns, feedback_columns, dim_model, dim_state, dim_max_batch, dropout=0.0,
@@ -184,6 +183,7 @@ class _RecurrentStateTracker(_DeviceStateTracker):
                  nhead=8, d_hid=128, nlayers=1, device="cpu", seed=2021, init_std=0.0001, padding_idx=None, MAX_TURN=100, **model_kw):
         super().__init__()
         cls = type(self)
+        self.d_hid = d_hid
         if dataset != "KuaishouEnv-v0":
             raise NotImplementedError(f"StateTracker{self.CELL} serves KuaishouEnv-v0 only (VirtualTB-v0 is out of scope)")
         self._check_model(dim_model, dim_state, nlayers, dropout, MAX_TURN + 1, **model_kw)
@@ -345,16 +345,9 @@ class StateTrackerFMLP(_RecurrentStateTracker):
     the filter, after dense_2) are not built.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
     CELL, ENGINE, param_shapes, init_params = "FMLP", DeviceFmlpTracker, fmlp_param_shapes, init_fmlp_tracker_params
 
-    def __init__(self, *args, **kw):
-        # d_hid is a keyword of the shared constructor that only this tracker reads: kept for _check_model
-        bound = inspect.signature(_RecurrentStateTracker.__init__).bind(self, *args, **kw)
-        bound.apply_defaults()
-        object.__setattr__(self, "_d_hid", bound.arguments["d_hid"])
-        super().__init__(*args, **kw)
-
     def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len, window_size=10):
-        check_fmlp_shape(dim_model, dim_state, window_size, nlayers, self._d_hid, max_len)
-        self.window_size, self.d_hid = int(window_size), int(self._d_hid)
+        check_fmlp_shape(dim_model, dim_state, window_size, nlayers, self.d_hid, max_len)
+        self.window_size, self.d_hid = int(window_size), int(self.d_hid)
         self.dropout_p, self.nlayers = 0.0, int(nlayers)
 
     def _model_kw(self):
@@ -370,14 +363,7 @@ class StateTrackerLRU(_RecurrentStateTracker):
     unused: LRURec's dropout sites are not built.  A _RecurrentStateTracker to whatever asks: the engine surface, the collect, every refusal."""
     CELL, ENGINE, param_shapes, init_params = "LRU", DeviceLruTracker, lru_param_shapes, init_lru_tracker_params
 
-    def __init__(self, *args, **kw):
-        # d_hid is a keyword of the shared constructor that this tracker reads, as StateTrackerFMLP does: kept for _check_model
-        bound = inspect.signature(_RecurrentStateTracker.__init__).bind(self, *args, **kw)
-        bound.apply_defaults()
-        object.__setattr__(self, "_d_hid", bound.arguments["d_hid"])
-        super().__init__(*args, **kw)
-
     def _check_model(self, dim_model, dim_state, nlayers, dropout, max_len):
-        check_lru_shape(dim_model, dim_state, nlayers, self._d_hid, max_len)
-        self.d_hid = int(self._d_hid)
+        check_lru_shape(dim_model, dim_state, nlayers, self.d_hid, max_len)
+        self.d_hid = int(self.d_hid)
         self.dropout_p, self.nlayers = 0.0, int(nlayers)
